@@ -7,17 +7,23 @@ A step = one pass of the hot path over one batch: CGDSubspaceOptimizer::optimize
 is already resident in HBM, including the D2H of the results.  An iteration = one
 Frprmn outer iteration (one line minimisation), summed over components.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds
+everything else the line has carried (CPU baselines, the comparisons with the committed CPU
+fixtures, the latency floor, the objective band, the strong-scaling, all-components, configs,
+large-component and normal-equations blocks).  --dump-outputs DIR writes what the last timed
+step returned (solution, per-component results, objective) as DIR/<name>.npy in float64.
 
 Workloads (--workload):
   ladybug-full   BASELINE config 4 (default, the metric's configuration): all 23769
                  variables and 31843 factors of ladybug-49-7776 as one component.
                  For N > 1 every rank solves one such component (N independent
                  components of a block-diagonal problem; weak scaling) and the
-                 top-level objective is summed with an RCCL all-reduce.  The line
-                 also carries a "strong_scaling" block for every N: north_star's fixed
+                 top-level objective is summed with an RCCL all-reduce.  With --full the
+                 line also carries a "strong_scaling" block for every N: north_star's fixed
                  1000-component synthetic decomposition shared out over the N ranks
                  (STRONG below), and at N = 1 "cpu_baseline" and "objective_band".
   synthetic-S    BASELINE config 5: 1000 independent 3-camera x 40-point components
@@ -81,6 +87,11 @@ def parse():
     ap.add_argument("--opt", action="append", default=[], help="plan option name=value")
     ap.add_argument("--collective", default="c-abi", choices=["c-abi", "torch"],
                     help="how the ranks' objective all-reduce runs: the library's own RCCL entry points (default; no torch in the process) or torch.distributed")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: CPU baselines, comparisons with the CPU fixtures, latency floor, objective band and the other "
+                         "blocks (strong scaling, all components, configs, large component, normal equations); the --no-* options trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float64, at most 64 MB in all)")
     return ap.parse_args()
 
 
@@ -862,6 +873,26 @@ def algorithmic_bytes(pp, nfeval: int, ngeval: int) -> float:
     return tot
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(directory: str, arrays: dict, suffix: str = "", limit: int = DUMP_LIMIT_BYTES) -> None:
+    """--dump-outputs: every array as directory/<name><suffix>.npy in float64.  When they would exceed `limit` bytes together, an
+    array longer than its share is replaced by a sample at sorted indices drawn with a fixed seed (the same indices for the same
+    length in every run), written beside it as <name>_sample_index."""
+    os.makedirs(directory, exist_ok=True)
+    out = {k: np.ascontiguousarray(v, dtype=np.float64).ravel() for k, v in arrays.items() if v is not None}
+    if sum(v.nbytes for v in out.values()) > limit:
+        cap = max(1, (limit - 4096) // 8 // (2 * len(out)))   # (4096: the .npy headers)
+        for k in list(out):
+            if out[k].size > cap:
+                idx = np.sort(np.random.default_rng(20260101).choice(out[k].size, cap, replace=False))
+                out[k] = out[k][idx]
+                out[k + "_sample_index"] = idx.astype(np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(directory, k + suffix + ".npy"), v)
+
+
 def cpu_baseline(pp, maxiters: int):
     """the oracle (a port of the reference's algorithm) on this box's host cores,
     single-threaded like the reference; bounded to a few tens of seconds"""
@@ -1042,13 +1073,18 @@ def main():
     else:
         total_iters, total_nfe, total_nge = float(iters_done), float(nfe.sum()), float(nge.sum())
 
+    if a.dump_outputs:   # what a caller of the timed path receives from its last step (rank 0 unsuffixed, every other rank _rank<r>)
+        dump_outputs(a.dump_outputs, {"x": r.x, "fret": r.fret, "delta": r.delta, "iters": r.iters, "status": r.status,
+                                      "nfeval": r.nfeval, "ngeval": r.ngeval, "objective": np.array([objective_sum])},
+                     suffix="" if rank == 0 else "_rank%d" % rank, limit=DUMP_LIMIT_BYTES // world)
+
     if rank == 0:
         abytes = algorithmic_bytes(pp, nfe, nge)
         achieved = abytes / (kms * 1e-3) / 1e9 if kms > 0 else 0.0
         line = {
             "metric": "subspace-solver iters/sec (all components), ladybug BA",
             "value": total_iters / dt, "unit": "iters/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": a.scaling,
+            "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": a.scaling, "full": bool(a.full),
             "vs_baseline": None, "dtype": "f64", "data": "synthetic" if a.workload.startswith("synthetic") else "ladybug-49-7776 (BAL file)",
             "config": {"workload": ("ladybug-49-7776 full, CGD over all 23769 variables / 31843 factors, SSmaxit 25, ftol 3e-8; "
                                     "one such component per GPU") if a.workload == "ladybug-full" else
@@ -1079,7 +1115,7 @@ def main():
                                               "governs a single-component solve: DESIGN.md 3.2b; cycle stamps of the pipeline's three sides: profiles/r02_g_pipe_ladybug_stamps.txt)"}
                                      if pp.ncomp == 1 else None)},
         }
-        if world == 1 and pp.ncomp == 1 and line["roofline"]["latency"] is not None:
+        if a.full and world == 1 and pp.ncomp == 1 and line["roofline"]["latency"] is not None:
             fl = latency_floor()
             if fl is not None:
                 lat = line["roofline"]["latency"]
@@ -1089,7 +1125,7 @@ def main():
                 lat["floor_note"] = ("the floor is that of a strictly serial chain (step -> arithmetic -> reduce -> hop); the pipelined solver evaluates "
                                      "guessed Brent steps ahead of its control logic (84 % of them hold), which is how the measured figure reaches the "
                                      "serial floor although every evaluation also pays a sweep over 1000 granules and a request hand-over")
-        if a.workload == "ladybug-full" and a.maxiters == 25 and not a.opt:
+        if a.full and a.workload == "ladybug-full" and a.maxiters == 25 and not a.opt:
             # the headline solve against the committed CPU fixture: what the oracle returns with its four named switches on (the
             # device's factor arithmetic x 3 and the cooperative solvers' sum trees; tests/golden/make_parity_end_values.py, pinned by
             # the CPU suite, asserted live under -m gpu by tests/test_gpu_parity.py).  Nothing under oracle/ runs here.
@@ -1104,29 +1140,29 @@ def main():
                             "sweep, the device's sum trees): DESIGN.md section 6.0; the reference's own arithmetic ends at 83227.604227756252"}
             except (OSError, KeyError, ValueError):
                 pass
-        if world == 1:
+        if a.full and world == 1:
             line["plugin_call"] = plugin_call(prob, pp, a.maxiters)
             if a.workload == "ladybug-full" and a.maxiters == 25:
                 line["value_parity_option"] = parity_option(plan, pp, a.maxiters)
-        if not a.no_cpu_baseline and world == 1:   # the CPU leg is timed at N = 1 only
+        if a.full and not a.no_cpu_baseline and world == 1:   # the CPU leg is timed at N = 1 only
             line["cpu_baseline"] = cpu_baseline(pp, a.maxiters)
             if a.workload == "ladybug-full" and not a.no_objective_band and a.maxiters == 25:
                 line["objective_band"] = objective_band(plan, pp, a.maxiters)
     plan.close()
     prob.close()
-    # north_star's scaling workload, in the command the driver runs: for every N, N = 1 included
-    if a.workload == "ladybug-full" and not a.no_strong_scaling:
+    # (--full) north_star's scaling workload, in the command the driver runs: for every N, N = 1 included
+    if a.full and a.workload == "ladybug-full" and not a.no_strong_scaling:
         STRONG.clear(); STRONG.update(STRONG_SIZES[a.strong_size])
         ss = run_strong_scaling(ctx, rank, world, coll, a.maxiters, cpu=not a.no_cpu_baseline and world == 1)
         if rank == 0:
             line["strong_scaling"] = ss
-    if a.workload == "ladybug-full" and world == 1 and not a.no_all_components:
+    if a.full and a.workload == "ladybug-full" and world == 1 and not a.no_all_components:
         line["all_components"] = all_components(local_rank, a.maxiters)
-    if a.workload == "ladybug-full" and world == 1 and not a.no_configs:
+    if a.full and a.workload == "ladybug-full" and world == 1 and not a.no_configs:
         line["configs"] = configs_block(ctx, a.maxiters, cpu=not a.no_cpu_baseline)
-    if a.workload == "ladybug-full" and world == 1 and not a.no_large_component:
+    if a.full and a.workload == "ladybug-full" and world == 1 and not a.no_large_component:
         line["large_component"] = large_component(ctx, a.maxiters, cpu=not a.no_cpu_baseline)
-    if a.workload == "ladybug-full" and world == 1 and not a.no_configs:
+    if a.full and a.workload == "ladybug-full" and world == 1 and not a.no_configs:
         line["normal_equations"] = lm_block(ctx, a.maxiters)
     import ctypes
     ctypes.CDLL(None).fflush(None)   # every rank: nothing buffered (RCCL's banner) may surface after rank 0's JSON

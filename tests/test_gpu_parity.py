@@ -199,6 +199,28 @@ def test_default_cooperative_path_equals_the_oracle_with_the_sum_trees(gctx, lay
     assert r.fret[0] == w["fret"] and int(r.nfeval[0]) == w["nfeval"]      # (the committed CPU fixture: what bench.py compares with)
 
 
+def test_plain_bench_run_dumps_the_fixtures_end_state(tmp_path):
+    """`bench.py --steps 2 --warmup 1 --dump-outputs DIR` (no --full): one JSON line with the headline alone, and the arrays the
+    last timed step returned are the committed CPU fixture's end state of config 4, ==."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "iters/s" and line["dtype"] == "f64"
+    assert line["higher_is_better"] is True and line["full"] is False
+    assert not {"strong_scaling", "cpu_baseline", "objective_band", "configs", "plugin_call"} & set(line)
+    with open(os.path.join(root, "tests", "golden", "parity_end_values.json")) as fh:
+        w = json.load(fh)["ladybug_full_default_path"]
+    x, fret, nfeval = (np.load(str(tmp_path / (k + ".npy"))) for k in ("x", "fret", "nfeval"))
+    assert x.dtype == np.float64 and x.shape == (23769,)
+    assert fret[0] == w["fret"] and int(nfeval[0]) == w["nfeval"] and [float(v) for v in x[:3]] == w["x_0_2"] and float(x[-1]) == w["x_last"]
+    assert np.load(str(tmp_path / "objective.npy"))[0] == fret[0] == line["final_objective"]
+
+
 def test_default_cooperative_path_on_other_components_and_starts(gctx):
     """the same on ladybug's 49 cameras with 500 and with 2000 points from x0 and from two starts moved by 1e-12, and with
     speculation off (which must not change a bit).  With 500 points the group has 64 waves for 441 camera variables of some 80

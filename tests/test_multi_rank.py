@@ -336,3 +336,21 @@ def test_bench_fallback_collective_over_host_files(tmp_path):
     assert outs[0][-1] == [(0.1 + 0.2) + 0.30000000000000004]
     base = "/dev/shm" if os.path.isdir("/dev/shm") else "/tmp"
     assert not [f for f in os.listdir(base) if f.startswith("rdis_bench_fc_%d_" % port)]
+
+
+def test_bench_dump_outputs_float64_and_a_fixed_sample_under_the_cap(tmp_path):
+    """bench.py --dump-outputs: every array as <name>.npy in float64; over the cap the long ones become a sample at the same sorted
+    indices in every run, the indices written beside them, and the files stay within the cap"""
+    import bench
+    x, it = np.random.default_rng(1).standard_normal(100000), np.arange(7, dtype=np.int32)
+    bench.dump_outputs(str(tmp_path / "a"), {"x": x, "iters": it, "none": None})
+    assert sorted(os.listdir(tmp_path / "a")) == ["iters.npy", "x.npy"]
+    got = np.load(str(tmp_path / "a" / "x.npy"))
+    assert got.dtype == np.float64 and np.array_equal(got, x) and np.array_equal(np.load(str(tmp_path / "a" / "iters.npy")), it)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"x": x, "iters": it}, suffix="_rank1", limit=200000)
+        assert sum(os.path.getsize(str(tmp_path / d / f)) for f in os.listdir(tmp_path / d)) <= 200000
+    assert sorted(os.listdir(tmp_path / "b")) == ["iters_rank1.npy", "x_rank1.npy", "x_sample_index_rank1.npy"]
+    idx = np.load(str(tmp_path / "b" / "x_sample_index_rank1.npy"))
+    assert np.array_equal(idx, np.load(str(tmp_path / "c" / "x_sample_index_rank1.npy"))) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "x_rank1.npy")), x[idx.astype(np.int64)])

@@ -5,6 +5,7 @@
 * against the reference's own documented minima of data/testpoly.txt,
 * bit for bit against the reference's minimize_nrc.h built as oracle/_ref.
 """
+import json
 import os
 
 import numpy as np
@@ -204,25 +205,16 @@ def _rosen_g(x):
     return g
 
 
-@pytest.mark.skipif(not O.ref_available(), reason="oracle/_ref not built")
-@pytest.mark.parametrize("maxiters", [1, 2, 7, 25, 400])
-def test_minimiser_bit_exact_vs_reference_header(maxiters):
-    """restated Frprmn/linmin/Dbrent/bracket == the reference's minimize_nrc.h"""
+def _minimiser_cases(maxiters):
     rng = np.random.default_rng(maxiters)
-    cases = [(_rosen, _rosen_g, rng.uniform(-2, 2, 6)),
-             (lambda x: float(np.sum(np.cos(x) + 0.05 * x * x)), lambda x: -np.sin(x) + 0.1 * x,
-              rng.uniform(-6, 6, 9)),
-             (lambda x: float(np.sum((x - 1.5) ** 4)), lambda x: 4 * (x - 1.5) ** 3, rng.uniform(-3, 3, 3)),
-             (lambda x: 0.0 * x[0] + 7.0, lambda x: np.zeros_like(x), np.array([1.0, 2.0]))]
-    for f, g, x0 in cases:
-        a = O.frprmn(f, g, x0, maxiters, 3e-8)
-        b = O.ref_frprmn(f, g, x0, maxiters, 3e-8)
-        assert a[0] == b[0] or (b[0] == 0 and a[0] in (0, 1, 2))
-        assert np.array_equal(a[1], b[1]) and a[2] == b[2] and a[3] == b[3]
+    return [(_rosen, _rosen_g, rng.uniform(-2, 2, 6)),
+            (lambda x: float(np.sum(np.cos(x) + 0.05 * x * x)), lambda x: -np.sin(x) + 0.1 * x,
+             rng.uniform(-6, 6, 9)),
+            (lambda x: float(np.sum((x - 1.5) ** 4)), lambda x: 4 * (x - 1.5) ** 3, rng.uniform(-3, 3, 3)),
+            (lambda x: 0.0 * x[0] + 7.0, lambda x: np.zeros_like(x), np.array([1.0, 2.0]))]
 
 
-@pytest.mark.skipif(not O.ref_available(), reason="oracle/_ref not built")
-def test_minimiser_bit_exact_on_bundle_adjustment():
+def _ba_minimiser_case():
     p = P.load_bal(ncams=5, npts=30)
     o = O.OracleProblem(p, emulate_stale_cache=False)
 
@@ -233,8 +225,38 @@ def test_minimiser_bit_exact_on_bundle_adjustment():
     def g(x):
         o.assign(None, np.clip(x, p.lo, p.hi))
         return o.gradient()
-    a = O.frprmn(f, g, p.x0, 25, 3e-8)
-    b = O.ref_frprmn(f, g, p.x0, 25, 3e-8)
+    return f, g, p.x0
+
+
+def _reference_frprmn(key, f, g, x0, maxiters):
+    """the reference's minimiser on (f, g, x0): run live from oracle/_ref where it is built (and then the recorded result must be
+    the same), else the recorded result of the same case"""
+    # what the reference's nrc::Frprmn (oracle/_ref) returned on the same case, recorded by tests/golden/make_reference_frprmn.py
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_frprmn.json")) as fh:
+        rec = json.load(fh)[key]
+    assert np.array_equal(np.array(rec["x0"]), x0)
+    want = (rec["reason"], np.array(rec["x"]), rec["fret"], rec["iter"])
+    if O.ref_available():
+        b = O.ref_frprmn(f, g, x0, maxiters, 3e-8)
+        assert b[0] == want[0] and np.array_equal(b[1], want[1]) and b[2] == want[2] and b[3] == want[3]
+        return b
+    return want
+
+
+@pytest.mark.parametrize("maxiters", [1, 2, 7, 25, 400])
+def test_minimiser_bit_exact_vs_reference_header(maxiters):
+    """restated Frprmn/linmin/Dbrent/bracket == the reference's minimize_nrc.h"""
+    for k, (f, g, x0) in enumerate(_minimiser_cases(maxiters)):
+        a = O.frprmn(f, g, x0, maxiters, 3e-8)
+        b = _reference_frprmn("maxiters_%d_case_%d" % (maxiters, k), f, g, x0, maxiters)
+        assert a[0] == b[0] or (b[0] == 0 and a[0] in (0, 1, 2))
+        assert np.array_equal(a[1], b[1]) and a[2] == b[2] and a[3] == b[3]
+
+
+def test_minimiser_bit_exact_on_bundle_adjustment():
+    f, g, x0 = _ba_minimiser_case()
+    a = O.frprmn(f, g, x0, 25, 3e-8)
+    b = _reference_frprmn("ladybug_5_30", f, g, x0, 25)
     assert a[0] == b[0] == 3                       # "Too many iterations in frprmn"
     assert np.array_equal(a[1], b[1]) and a[2] == b[2] and a[3] == b[3] == 24
 
