@@ -82,8 +82,33 @@ struct Request {
     double tr_a, tr_b, tr_c;     // (meaningful only when tr_tag is set)
 };
 
-// keeps a value in a vector register, hides its origin from the optimiser
-__device__ __forceinline__ void opaque(double& v) { asm("" : "+v"(v)); }
+// keeps a value in a vector register, hides its origin from the optimiser (a no-op in a host build: the tests step the
+// machine's hot path on the CPU)
+__host__ __device__ __forceinline__ void opaque(double& v) {
+#ifdef __HIP_DEVICE_COMPILE__
+    asm("" : "+v"(v));
+#else
+    (void)v;
+#endif
+}
+
+// Brent's state between two trials of a line search (CgdMachine in S_DB_EVAL: uu is the pending trial), with the counters a
+// trial's reply moves: what the pipelined solver's stepper keeps in registers while it runs on hot steps only (solver_pipe.hpp)
+struct BrentHot {
+    double a, b, x, w, v, fx, fw, fv, dx, dw, dv, d, e, uu;
+    long long nfeval, ngeval;
+    int it;
+    bool tiny, saw_nan;
+};
+// The part of the next hot step that does not read the reply (CgdMachine::hot_pre): for either class of reply -- the trial comes
+// back no worse than x (L: x1 = uu) or worse (G: x1 = x) -- the bracket, its middle, the tolerances, the convergence test, `big`
+// and the default step; and, for G, the secant quotients on (w, dw) and (v, dv).  Formed while the reply travels.
+struct HotPre {
+    double aL, bL, xmL, tol1L, tol2L, dfltL;
+    double aG, bG, xmG, tol1G, tol2G, dfltG;
+    double qw, qv;
+    bool convL, bigL, convG, bigG, stop;
+};
 
 // Guesses at the trial steps the line search will ask for after the request the machine has just
 // issued, from the machine's state alone: the pending trial (and every guess after it) is assumed
@@ -110,6 +135,16 @@ struct Predictor {
 
     // swapped: the previous bracketing found f(1) > f(0) and went to the other side of 0
     __device__ void start(const struct CgdMachine& M, bool swapped);
+    // start() for a machine in S_DB_EVAL: a Brent trial at s.uu is pending
+    __device__ void start_eval(const BrentHot& s) {
+        ph = P_STOP; need_first = false; known = false;
+        a = b = x = dx = 0.0; ax = bx = cx = 0.0;
+        w = v = dw = dv = d = e = uu = 0.0;
+        if (s.tiny) return;       // worse after a minimal step ends the line search
+        a = s.a; b = s.b; x = s.x; dx = s.dx; ph = P_DB;
+        if (s.uu < x) a = s.uu; else b = s.uu;
+        known = true; w = s.w; v = s.v; dw = s.dw; dv = s.dv; d = s.d; e = s.e; uu = s.uu;
+    }
     __device__ void begin_brent(double ax_, double bx_, double cx_, bool slope_known, double slope) {
         a = (ax_ < cx_ ? ax_ : cx_);
         b = (ax_ > cx_ ? ax_ : cx_);
@@ -281,7 +316,7 @@ struct CgdMachine {
     // Brent iteration, the closing states of a line search, the iteration limit); otherwise `un` is
     // the next trial step (request: value + slope on the line), pre_* the pending trace record to
     // emit first, and G the state the Predictor continues from.
-    __device__ __forceinline__ bool hot(double r0, double r1, double& un, int& pre_tag, double& pre_a, double& pre_b,
+    __host__ __device__ __forceinline__ bool hot(double r0, double r1, double& un, int& pre_tag, double& pre_a, double& pre_b,
                                         double& pre_c, Predictor& G) {
 #pragma clang fp contract(off)
         const double TOL = 3.0e-8, ZEPS = DBL_EPSILON * 1.0e-3;
@@ -297,7 +332,9 @@ struct CgdMachine {
         opaque(a_); opaque(b_); opaque(x_); opaque(w_); opaque(v_); opaque(fx_); opaque(fw_); opaque(fv_);
         opaque(dx_); opaque(dw_); opaque(dv_); opaque(d_); opaque(e_); opaque(uu_);
         opaque(ppa_); opaque(ppb_); opaque(ppc_);
+#ifdef __HIP_DEVICE_COMPILE__
         asm("" : "+v"(nfe_), "+v"(nge_), "+v"(ppt_));
+#endif
         if ((tiny_ && r0 > fx_) || !(it_ + 1 < DB_ITMAX)) return false;
         const double fu = r0, du = r1;
         const bool le = fu <= fx_;
@@ -349,6 +386,104 @@ struct CgdMachine {
         G.known = true; G.w = w1; G.v = v1; G.dw = dw1; G.dv = dv1; G.d = dnew; G.e = enew; G.uu = un;
         G.ph = tn ? Predictor::P_STOP : Predictor::P_DB;
         return true;
+    }
+
+    // hot() in two parts: hot_pre(s, P) before the reply, hot_post(s, P, r0, r1, n, un) after it.  Together they are hot()
+    // bit for bit: the same operations on the same operands (contraction off, IEEE divisions), the same decisions, the same new
+    // state and counters (tests/test_hot_split.py).  hot_post returns false where hot() declines -- the caller then hands the
+    // unchanged state back to the machine, whose next() takes the step -- and otherwise the new state in n (written either way,
+    // after every read of s; the caller keeps s until it knows).  The pending trace record is TR_NONE in S_DB_EVAL (S_DB_HEAD
+    // emits it with the request), so the split form has none to hand on.
+    __host__ __device__ __forceinline__ BrentHot brent() const {
+        BrentHot s;
+        s.a = a; s.b = b; s.x = x; s.w = w; s.v = v; s.fx = fx; s.fw = fw; s.fv = fv;
+        s.dx = dx; s.dw = dw; s.dv = dv; s.d = d; s.e = e; s.uu = uu;
+        s.nfeval = nfeval; s.ngeval = ngeval; s.it = it; s.tiny = tiny; s.saw_nan = saw_nan;
+        return s;
+    }
+    __host__ __device__ __forceinline__ void set_brent(const BrentHot& s) {
+        a = s.a; b = s.b; x = s.x; w = s.w; v = s.v; fx = s.fx; fw = s.fw; fv = s.fv;
+        dx = s.dx; dw = s.dw; dv = s.dv; d = s.d; e = s.e; uu = s.uu;
+        nfeval = s.nfeval; ngeval = s.ngeval; it = s.it; tiny = s.tiny; saw_nan = s.saw_nan;
+    }
+    // (both read their operands into opaque registers first: a select between two fields of a struct in memory is otherwise
+    // folded into a load from a selected address, and the struct stays in scratch memory)
+    __host__ __device__ static __forceinline__ void hot_pre(const BrentHot& s0, HotPre& P) {
+#pragma clang fp contract(off)
+        BrentHot s = s0;
+        opaque(s.a); opaque(s.b); opaque(s.x); opaque(s.w); opaque(s.v); opaque(s.dx); opaque(s.dw); opaque(s.dv); opaque(s.e); opaque(s.uu);
+        const double TOL = 3.0e-8, ZEPS = DBL_EPSILON * 1.0e-3;
+        const int DB_ITMAX = 100;
+        const bool right = s.uu >= s.x, left = s.uu < s.x;
+        P.stop = !(s.it + 1 < DB_ITMAX);
+        // L: x1 = uu
+        P.aL = right ? s.x : s.a;
+        P.bL = right ? s.b : s.x;
+        P.xmL = 0.5 * (P.aL + P.bL);
+        P.tol1L = TOL * fabs(s.uu) + ZEPS;
+        P.tol2L = 2.0 * P.tol1L;
+        P.convL = fabs(s.uu - P.xmL) <= (P.tol2L - 0.5 * (P.bL - P.aL));
+        P.bigL = fabs(s.e) > P.tol1L;
+        P.dfltL = 2.0 * (P.bL - P.aL);
+        // G: x1 = x
+        P.aG = left ? s.uu : s.a;
+        P.bG = left ? s.b : s.uu;
+        P.xmG = 0.5 * (P.aG + P.bG);
+        P.tol1G = TOL * fabs(s.x) + ZEPS;
+        P.tol2G = 2.0 * P.tol1G;
+        P.convG = fabs(s.x - P.xmG) <= (P.tol2G - 0.5 * (P.bG - P.aG));
+        P.bigG = fabs(s.e) > P.tol1G;
+        P.dfltG = 2.0 * (P.bG - P.aG);
+        P.qw = (s.w - s.x) * s.dx / (s.dx - s.dw);
+        P.qv = (s.v - s.x) * s.dx / (s.dx - s.dv);
+    }
+    __host__ __device__ static __forceinline__ bool hot_post(const BrentHot& s0, const HotPre& P0, double fu, double du, BrentHot& n,
+                                                             double& un) {
+#pragma clang fp contract(off)
+        BrentHot s = s0;
+        HotPre P = P0;
+        opaque(s.a); opaque(s.b); opaque(s.x); opaque(s.w); opaque(s.v); opaque(s.fx); opaque(s.fw); opaque(s.fv);
+        opaque(s.dx); opaque(s.dw); opaque(s.dv); opaque(s.d); opaque(s.e); opaque(s.uu);
+        opaque(P.aL); opaque(P.bL); opaque(P.xmL); opaque(P.tol1L); opaque(P.tol2L); opaque(P.dfltL);
+        opaque(P.aG); opaque(P.bG); opaque(P.xmG); opaque(P.tol1G); opaque(P.tol2G); opaque(P.dfltG); opaque(P.qw); opaque(P.qv);
+        const bool le = fu <= s.fx;
+        const bool c1 = !le && (fu <= s.fw || s.w == s.x);
+        const bool c2 = !le && !c1 && (fu < s.fv || s.v == s.x || s.v == s.w);
+        const bool vw = le || c1;
+        const double v1 = vw ? s.w : (c2 ? s.uu : s.v), fv1 = vw ? s.fw : (c2 ? fu : s.fv), dv1 = vw ? s.dw : (c2 ? du : s.dv);
+        const double w1 = le ? s.x : (c1 ? s.uu : s.w), fw1 = le ? s.fx : (c1 ? fu : s.fw), dw1 = le ? s.dx : (c1 ? du : s.dw);
+        const double x1 = le ? s.uu : s.x, fx1 = le ? fu : s.fx, dx1 = le ? du : s.dx;
+        const double a1 = le ? P.aL : P.aG, b1 = le ? P.bL : P.bG, xm = le ? P.xmL : P.xmG;
+        const double tol1 = le ? P.tol1L : P.tol1G, tol2 = le ? P.tol2L : P.tol2G, dflt = le ? P.dfltL : P.dfltG;
+        const bool conv = le ? P.convL : P.convG, big = le ? P.bigL : P.bigG;
+        // the secant quotients that read the reply: (w1 - x1) dx1 / (dx1 - dw1) with (w1, dw1) = (x, dx) [L] or (uu, du) [G, c1],
+        // and [L] (v1 - x1) dx1 / (dx1 - dv1) with (v1, dv1) = (w, dw); the others are hot_pre's
+        const double qa = (le ? s.x - s.uu : s.uu - s.x) * (le ? du : s.dx) / (le ? du - s.dx : s.dx - du);
+        const double qb = (s.w - s.uu) * du / (du - s.dw);
+        const double q1 = vw ? qa : P.qw;
+        const double q2 = le ? qb : (c1 ? P.qw : (c2 ? qa : P.qv));
+        const double d1 = (dw1 != dx1) ? q1 : dflt;
+        const double d2 = (dv1 != dx1) ? q2 : dflt;
+        const double u1 = x1 + d1, u2 = x1 + d2;
+        const bool ok1 = (a1 - u1) * (u1 - b1) > 0.0 && dx1 * d1 <= 0.0;
+        const bool ok2 = (a1 - u2) * (u2 - b1) > 0.0 && dx1 * d2 <= 0.0;
+        const double dsel = (ok1 && ok2) ? (fabs(d1) < fabs(d2) ? d1 : d2) : (ok1 ? d1 : d2);
+        const bool accept = big && (ok1 || ok2) && (fabs(dsel) <= fabs(0.5 * s.e));
+        const double ut = x1 + dsel;
+        const double dacc = (ut - a1 < tol2 || b1 - ut < tol2) ? copysign(tol1, xm - x1) : dsel;
+        const double ebis = (dx1 >= 0.0 ? a1 - x1 : b1 - x1);
+        const double enew = accept ? s.d : ebis;
+        const double dnew = accept ? dacc : 0.5 * ebis;
+        const bool tn = !(fabs(dnew) >= tol1);
+        un = tn ? x1 + copysign(tol1, dnew) : x1 + dnew;
+        const bool taken = !((s.tiny && fu > s.fx) || P.stop || conv);
+        const bool nan = s.saw_nan || fu != fu;
+        const long long nfe = s.nfeval + 1, nge = s.ngeval + 1;
+        const int it1 = s.it + 1;
+        n.a = a1; n.b = b1; n.v = v1; n.fv = fv1; n.dv = dv1; n.w = w1; n.fw = fw1; n.dw = dw1; n.x = x1; n.fx = fx1; n.dx = dx1;
+        n.e = enew; n.d = dnew; n.tiny = tn; n.uu = un;
+        n.it = it1; n.ngeval = nge; n.nfeval = nfe; n.saw_nan = nan;
+        return taken;
     }
 
     // r0, r1, r2: reply to the previous request
@@ -583,10 +718,7 @@ __device__ inline void Predictor::start(const CgdMachine& M, bool swapped) {
         w = v = x; dw = dv = dx; uu = x;
         break;
     case CgdMachine::S_DB_EVAL:   // pending: a Brent trial at uu
-        if (M.tiny) break;        // worse after a minimal step ends the line search
-        a = M.a; b = M.b; x = M.x; dx = M.dx; ph = P_DB;
-        if (M.uu < x) a = M.uu; else b = M.uu;
-        known = true; w = M.w; v = M.v; dw = M.dw; dv = M.dv; d = M.d; e = M.e; uu = M.uu;
+        start_eval(M.brent());
         break;
     default: break;
     }

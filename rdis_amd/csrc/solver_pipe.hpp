@@ -7,9 +7,9 @@
 // that sweeps and steps is also a wave that evaluates, so nothing overlaps.  Here a workgroup of
 // four waves is
 //
-//   wave 0   STEPPER: keeps the state machine of minimizer.hpp in registers (nothing of the factor
-//            arithmetic competes for them), steps it on the sums it is handed and posts requests in
-//            an LDS mailbox.  It touches no global memory.
+//   wave 0   STEPPER: steps the state machine of minimizer.hpp on the sums it is handed -- Brent's trials
+//            in registers (nothing of the factor arithmetic competes for them), the rest of the machine
+//            in LDS (pipe_stepper) -- and posts requests in an LDS mailbox.  It touches no global memory.
 //   wave 1   COLLECTOR: sweeps the exchange slot the stepper names (all entries of the group, summed
 //            in index order), re-arms dead slots, hands the sums back through LDS.
 //   waves 2, 3   LANES: a factor per lane, variables per lane / wave exactly as in solver_coop.hpp;
@@ -109,8 +109,10 @@ struct PipeShared {
     int dead;                    // an exchange gave up
     // the result, for the lanes' write-back
     int status, rolled_back, iter;
+    int fin;                     // the result fields are written (stepper -> lanes)
     long long nfeval, ngeval;
     double fret, finit;
+    CgdMachine mach;             // the stepper's machine between hot runs (its generic step runs in lane 0 on it)
 };
 // words of PipeShared that one wave writes and another polls.  The casts name the LDS address
 // space: a volatile access through a generic pointer is compiled as a FLAT access at system scope
@@ -553,25 +555,33 @@ __device__ __forceinline__ void pipe_ctrl_barrier(PipeSync& X, PipeShared& S, bo
 }
 
 // ---- wave 0: the control logic -----------------------------------------------------------
+// Two loops.  The inner one runs Brent's trials (CgdMachine::hot, ~85 % of all steps) on a copy of Brent's state in registers:
+// straight-line code, split into the part that does not read the reply (hot_pre, formed while the sums travel) and the rest
+// (hot_post); it requests only value+slope trials on the line and makes no Request.  Whatever hot() would decline -- bracketing,
+// a line's start and end, the gradient, the exits -- leaves it: the state goes back to the machine in LDS, whose generic step
+// (next()) runs in lane 0 there, some 120 times a solve, and whose request reaches the wave through readfirstlane.  So the generic
+// step's code and registers stay out of the hot loop (inlined into one region with it, the machine's whole state was shuffled
+// through exec-masked branches and parked in AGPRs on every step).
 __device__ __forceinline__ void pipe_stepper(PipeEnv& E, PipeShared& S, int maxiters, double ftol) {
-    CgdMachine M;
-    M.init(maxiters, ftol);
+    CgdMachine& M = S.mach;
+    const bool writer = E.tid == 0;
+    if (writer) M.init(maxiters, ftol);
     int e_last = 0;             // slot of the last value+slope evaluation
     bool chain_live = false;    // ... and the lanes may be evaluating guesses behind it
     int next_free = 0;          // first exchange number not handed out
-    bool swapped = true;        // did the last bracketing go to the other side of the origin?
+    bool swapped = true;        // did the last bracketing go to the other side of the origin? (lane 0)
     double r0 = 0.0, r1 = 0.0, r2 = 0.0;
     int seq = 0;
-    const bool writer = E.tid == 0;
-    for (;;) {
-        const long long ts0 = coop_clock();
-        // What do the lanes guess for the slot after the last evaluation?  (They wrote it down before
-        // they evaluated that one.)  It is probably what the machine will ask for next: the collector
-        // has gone on to that slot by itself and gathers its sums while the machine is stepped.
-        bool guessed = false;
-        double gval = 0.0;
-        int ahead_slot = -1;          // the collector's result words for that slot, read ahead: they travel
-        double ahead0 = 0.0, ahead1 = 0.0;   // from LDS while the machine is stepped (slot word first: sums valid if it matches)
+    // What do the lanes guess for the slot after the last evaluation?  (They wrote it down before they evaluated that one.)
+    // It is probably what the machine will ask for next: the collector has gone on to that slot by itself and gathers its
+    // sums while the machine is stepped.  The collector's result words for that slot are read ahead: they travel from LDS
+    // while the machine is stepped (slot word first: the sums are valid if it matches).
+    bool guessed = false;
+    double gval = 0.0;
+    int ahead_slot = -1;
+    double ahead0 = 0.0, ahead1 = 0.0;
+    auto read_chain = [&]() {
+        guessed = false; gval = 0.0; ahead_slot = -1; ahead0 = ahead1 = 0.0;
         if (chain_live) {
             const int z = e_last + 1;
             int rec = lds_int(S.rec_slot[z & (PIPE_RECS - 1)]);
@@ -582,77 +592,128 @@ __device__ __forceinline__ void pipe_stepper(PipeEnv& E, PipeShared& S, int maxi
             guessed = (rec & 1) != 0;
             gval = uniform(lds_f64_get(S.rec_val[z & (PIPE_RECS - 1)]));
         }
-        asm volatile("; PIPE_STEP_BEGIN");
+    };
+    // a value+slope evaluation at slot e has been asked for (posted, or the chain's guess): wait for its sums
+    auto await_fd = [&](int e, bool hit) {
+        double v[2];
+        const long long tw0 = coop_clock();
+        if (hit && __builtin_amdgcn_readfirstlane(ahead_slot) == e) {
+            v[0] = uniform(ahead0); v[1] = uniform(ahead1);
+            if (lds_int(S.dead) != 0) E.X.dead = true;
+        } else {
+            pipe_result(S, e, v, E.X.dead);
+        }
+        if (hit) { E.X.tick(20, coop_clock() - tw0); E.X.tick(16, 1); }
+        else { E.X.tick(21, coop_clock() - tw0); E.X.tick(17, 1); }
+        r0 = v[0]; r1 = v[1];
+        e_last = e;
+        chain_live = true;
+        next_free = e_last + PIPE_DEPTH + 1;
+    };
+    for (;;) {
+        long long ts0 = coop_clock();
+        read_chain();
+        // ---- Brent's trials ----
+        bool stepped = false;   // the hot loop took the step on the last reply (an exchange gave up behind it)
+        if (__builtin_amdgcn_readfirstlane(lds_int(M.st)) == CgdMachine::S_DB_EVAL) {
+            BrentHot s = M.brent();
+            opaque(s.a); opaque(s.b); opaque(s.x); opaque(s.w); opaque(s.v); opaque(s.fx); opaque(s.fw); opaque(s.fv);
+            opaque(s.dx); opaque(s.dw); opaque(s.dv); opaque(s.d); opaque(s.e); opaque(s.uu);
+            HotPre P;
+            CgdMachine::hot_pre(s, P);
+            for (;;) {
+                asm volatile("; PIPE_STEP_BEGIN");
+                BrentHot n;
+                double un;
+                const bool take = CgdMachine::hot_post(s, P, r0, r1, n, un);
+                if (__builtin_amdgcn_readfirstlane(take ? 1 : 0) == 0) break;   // s unchanged: the generic step takes it
+                s = n;
+                if (E.X.dead) { stepped = true; break; }   // an exchange gave up: this step is the machine's last (below)
+                const bool hit = __builtin_amdgcn_readfirstlane((guessed && same_bits(un, gval)) ? 1 : 0) != 0;
+                int e;
+                if (hit) {
+                    // the step asked for is the chain's guess: its slot is the next one, and the lanes, who are at work on
+                    // the chain already, only need to hear how far the machine has come
+                    e = e_last + 1;
+                    if (writer) lds_set(S.verified, e);
+                } else {
+                    e = next_free;
+                    pipe_post(S, ++seq, REQ_EVAL, RF_SLOPE | RF_LINE, e, un, 0.0, writer);
+                    Predictor G;   // (the lanes are at work on the request; what they continue with follows)
+                    G.ph = Predictor::P_STOP; G.need_first = false; G.known = false; G.a = G.b = G.x = G.dx = 0.0; G.ax = G.bx = G.cx = 0.0;
+                    G.w = G.v = G.dw = G.dv = G.d = G.e = G.uu = 0.0;
+                    if (E.A.speculate) G.start_eval(s);
+                    pipe_post_predictor(S, seq, G, writer);
+                }
+                asm volatile("; PIPE_STEP_END");
+                const long long ts1 = coop_clock();
+                E.X.tick(8, ts1 - ts0);
+                E.X.e = e;
+                // a fresh step takes the lanes an evaluation: the collector goes there now
+                if (!hit) pipe_command(S, e, 2, E.X.poll_delay, writer);
+                // what the next step needs of this state alone, while the sums travel
+                CgdMachine::hot_pre(s, P);
+                await_fd(e, hit);
+                E.trace(TR_FD, un, r0, r1);
+                E.X.tick(13, coop_clock() - ts1); E.X.tick(23, 1);
+                ts0 = coop_clock();
+                read_chain();
+            }
+            if (writer) M.set_brent(s);
+        }
+        // ---- the generic step (lane 0, on the machine in LDS) ----
+        asm volatile("; PIPE_GENERIC_BEGIN");
         Request nq;
-        Predictor G;
-        G.ph = Predictor::P_STOP; G.need_first = false; G.known = false; G.a = G.b = G.x = G.dx = 0.0; G.ax = G.bx = G.cx = 0.0;
-        G.w = G.v = G.dw = G.dv = G.d = G.e = G.uu = 0.0;
-        bool was_hot;
-        {
-            double un, pa, pb, pc;
-            int ptag;
-            Predictor unused;   // (what hot() would hand on is formed from the machine below, and only for a fresh request)
-            was_hot = M.hot(r0, r1, un, ptag, pa, pb, pc, unused);
-            if (was_hot) {
-                nq = CgdMachine::req(REQ_EVAL, un, RF_SLOPE | RF_LINE);
-                nq.pre_tag = ptag; nq.pre_a = pa; nq.pre_b = pb; nq.pre_c = pc;
-            } else {
+        if (writer) {
+            if (!stepped) {
                 nq = M.next(r0, r1, r2);
                 if (M.st == CgdMachine::S_BR_FC) swapped = M.ax == 1.0;
+            } else {
+                nq = CgdMachine::req(REQ_DONE);
+            }
+            if (E.X.dead) {   // an exchange gave up: the restored start is what is returned (CGD .cpp:66-80)
+                nq = CgdMachine::req(REQ_DONE);
+                M.reason = EXIT_SYNC_TIMEOUT; M.rolled_back = true; M.fret = M.finit;
             }
         }
-        if (E.X.dead) {   // an exchange gave up: the restored start is what is returned (CGD .cpp:66-80)
-            nq = CgdMachine::req(REQ_DONE);
-            M.reason = EXIT_SYNC_TIMEOUT; M.rolled_back = true; M.fret = M.finit;
-        }
-        const bool slope = nq.kind == REQ_EVAL && (nq.flags & RF_SLOPE) != 0;
-        const bool hit = slope && nq.flags == (RF_SLOPE | RF_LINE) && guessed && same_bits(nq.a, gval);
+        const int kind = __builtin_amdgcn_readfirstlane(nq.kind);
+        const int flags = __builtin_amdgcn_readfirstlane(nq.flags);
+        const bool slope = kind == REQ_EVAL && (flags & RF_SLOPE) != 0;
+        const bool hit = __builtin_amdgcn_readfirstlane((slope && flags == (RF_SLOPE | RF_LINE) && guessed && same_bits(nq.a, gval)) ? 1 : 0) != 0;
         int e;
         if (hit) {
-            // the step asked for is the chain's guess: its slot is the next one, and the lanes, who are at
-            // work on the chain already, only need to hear how far the machine has come
             e = e_last + 1;
             if (writer) lds_set(S.verified, e);
         } else {
             e = next_free;
-            pipe_post(S, ++seq, nq.kind, nq.flags, e, nq.a, nq.b, writer);
-            if (slope) {   // (the lanes are at work on the request; what they continue with follows)
+            pipe_post(S, ++seq, kind, flags, e, nq.a, nq.b, writer);
+            if (slope && writer) {   // (the lanes are at work on the request; what they continue with follows)
+                Predictor G;
+                G.ph = Predictor::P_STOP; G.need_first = false; G.known = false; G.a = G.b = G.x = G.dx = 0.0; G.ax = G.bx = G.cx = 0.0;
+                G.w = G.v = G.dw = G.dv = G.d = G.e = G.uu = 0.0;
                 if (E.A.speculate) G.start(M, swapped);
                 pipe_post_predictor(S, seq, G, writer);
             }
         }
-        if (E.tr != nullptr) {
-            if ((nq.flags & RF_TR_FIRST) && nq.tr_tag != TR_NONE) E.trace(nq.tr_tag, nq.tr_a, nq.tr_b, nq.tr_c);
+        if (E.tr != nullptr) {   // (E.trace writes from lane 0: the record's values need be valid there only)
+            if ((flags & RF_TR_FIRST) && nq.tr_tag != TR_NONE) E.trace(nq.tr_tag, nq.tr_a, nq.tr_b, nq.tr_c);
             if (nq.pre_tag != TR_NONE) E.trace(nq.pre_tag, nq.pre_a, nq.pre_b, nq.pre_c);
-            if (!(nq.flags & RF_TR_FIRST) && nq.tr_tag != TR_NONE) E.trace(nq.tr_tag, nq.tr_a, nq.tr_b, nq.tr_c);
+            if (!(flags & RF_TR_FIRST) && nq.tr_tag != TR_NONE) E.trace(nq.tr_tag, nq.tr_a, nq.tr_b, nq.tr_c);
         }
-        asm volatile("; PIPE_STEP_END");
+        asm volatile("; PIPE_GENERIC_END");
         const long long ts1 = coop_clock();
         E.X.tick(8, ts1 - ts0);
-        if (nq.kind == REQ_DONE) break;
+        if (kind == REQ_DONE) break;
         E.X.e = e;
         chain_live = false;
-        [[maybe_unused]] const int tkind = nq.kind == REQ_GRAD ? 2 : !slope ? 0 : (nq.flags & (RF_PRE_START | RF_PRE_UPDATE)) ? 3 : 1;
-        switch (nq.kind) {
+        [[maybe_unused]] const int tkind = kind == REQ_GRAD ? 2 : !slope ? 0 : (flags & (RF_PRE_START | RF_PRE_UPDATE)) ? 3 : 1;
+        switch (kind) {
         case REQ_EVAL:
-            if (nq.flags & RF_PRE_START) pipe_ctrl_barrier(E.X, S, writer);   // the lanes' publish_xi (a direction update needs none)
+            if (flags & RF_PRE_START) pipe_ctrl_barrier(E.X, S, writer);   // the lanes' publish_xi (a direction update needs none)
             if (slope) {
                 // a fresh step takes the lanes an evaluation: the collector goes there now
                 if (!hit) pipe_command(S, E.X.e, 2, E.X.poll_delay, writer);
-                double v[2];
-                const long long tw0 = coop_clock();
-                if (hit && __builtin_amdgcn_readfirstlane(ahead_slot) == E.X.e) {
-                    v[0] = uniform(ahead0); v[1] = uniform(ahead1);
-                    if (lds_int(S.dead) != 0) E.X.dead = true;
-                } else {
-                    pipe_result(S, E.X.e, v, E.X.dead);
-                }
-                if (hit) { E.X.tick(20, coop_clock() - tw0); E.X.tick(16, 1); }
-                else { E.X.tick(21, coop_clock() - tw0); E.X.tick(17, 1); }
-                r0 = v[0]; r1 = v[1];
-                e_last = E.X.e;
-                chain_live = true;
-                next_free = e_last + PIPE_DEPTH + 1;
+                await_fd(E.X.e, hit);
                 E.trace(TR_FD, nq.a, r0, r1);
             } else {
                 double v[1];
@@ -660,12 +721,12 @@ __device__ __forceinline__ void pipe_stepper(PipeEnv& E, PipeShared& S, int maxi
                 pipe_result(S, E.X.e, v, E.X.dead);
                 r0 = v[0];
                 next_free = E.X.e + 1;
-                if (nq.flags & RF_LINE) E.trace(TR_F, nq.a, r0, 0.0);
+                if (flags & RF_LINE) E.trace(TR_F, nq.a, r0, 0.0);
             }
             break;
         case REQ_GRAD:
             pipe_ctrl_barrier(E.X, S, writer);   // gradient_to_xi: partials -> per-variable sums
-            if (nq.flags & RF_POST_REDUCE) {
+            if (flags & RF_POST_REDUCE) {
                 double v[3];
                 pipe_command(S, E.X.e, 3, E.X.poll_delay, writer);
                 pipe_result(S, E.X.e, v, E.X.dead);
@@ -688,6 +749,8 @@ __device__ __forceinline__ void pipe_stepper(PipeEnv& E, PipeShared& S, int maxi
         // the result, for everybody
         S.status = M.status(); S.rolled_back = M.rolled_back ? 1 : 0; S.iter = M.iter;
         S.nfeval = M.nfeval; S.ngeval = M.ngeval; S.fret = M.fret; S.finit = M.finit;
+        asm volatile("" ::: "memory");
+        lds_set(S.fin, 1);
     }
 }
 
@@ -861,27 +924,35 @@ __device__ __forceinline__ void pipe_solve(const ProblemView& P, const PlanView&
               },
               L.trace ? L.trace + 4ll * L.trace_cap * comp : nullptr, 0, 0,
               gt >= 0 && gt < m, 0, {}, {}, {}, {}, {}, 0.0, 0.0, {}, {}};
-    if (E.has_fac) {
-        E.fid = L.fac_id[c0 + gt];
-        const double2 o = P.obs[E.fid];
-        E.ox = o.x; E.oy = o.y;
-        const int* sp = L.slot_pos + L.slot_base[c0 + gt];
-#pragma unroll
-        for (int k = 0; k < 12; ++k) E.gpos[k] = sp[k];
-    }
-    if (tid == 0) { S.seq = 0; S.pred_seq = 0; S.cmd = -1; S.cmd_delay = 0; S.bar_done = -1; S.dead = 0; S.verified = -1; }
+    if (tid == 0) { S.seq = 0; S.pred_seq = 0; S.cmd = -1; S.cmd_delay = 0; S.bar_done = -1; S.dead = 0; S.verified = -1; S.fin = 0; }
     if (tid < PIPE_RECS) S.rec_slot[tid] = -1;
     if (tid < PIPE_RES) S.res_slot[tid] = -1;
     if (tid < PIPE_LANES / 64) S.pub[tid] = -1;
-    E.init_vectors();
     __syncthreads();
-    if (tid < 64) pipe_stepper(E, S, maxiters, ftol);
-    else if (tid < 128) pipe_collector(E.X, S);
-    else pipe_lanes(E, S);
+    // The role is wave-uniform, and the lanes' state (factor, variables) is loaded and written back
+    // inside their own branch: nothing of it is live across the stepper's code, whose state then has
+    // the register file to itself (with the loads before the branch, some 230 registers of it were
+    // live through the stepper's loop, and its state was parked in AGPRs and spilled SGPRs).
+    const int role = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (role == 0) pipe_stepper(E, S, maxiters, ftol);
+    else if (role == 1) pipe_collector(E.X, S);
+    else {
+        if (E.has_fac) {
+            E.fid = L.fac_id[c0 + gt];
+            const double2 o = P.obs[E.fid];
+            E.ox = o.x; E.oy = o.y;
+            const int* sp = L.slot_pos + L.slot_base[c0 + gt];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) E.gpos[k] = sp[k];
+        }
+        E.init_vectors();
+        pipe_lanes(E, S);
+        while (lds_int(S.fin) == 0) __builtin_amdgcn_s_sleep(1);   // the stepper's result is complete
+        const bool restore = S.rolled_back != 0;
+        E.write_back(E.lv, restore, true);
+        E.write_back(E.wv, restore, (tid & 63) == 0);
+    }
     __syncthreads();
-    const bool restore = S.rolled_back != 0;
-    E.write_back(E.lv, restore, true);
-    E.write_back(E.wv, restore, (tid & 63) == 0);
     if (wg == 0 && tid == 0) {
         L.fret[comp] = S.fret; L.delta[comp] = S.fret - S.finit; L.iters[comp] = S.iter;
         L.status[comp] = S.status; L.nfeval[comp] = S.nfeval; L.ngeval[comp] = S.ngeval;
