@@ -20,11 +20,15 @@
 //                 dir[N] (search direction scattered by variable id; zero at
 //                 non-free variables), gfac[12F | nnz] (per-factor partials of the
 //                 last full-gradient evaluation), xstart[nfree], outputs.
+//
+// These types and the constants that size them live in namespace rdis_views, which namespace rdis_hip imports.
+// refround_kernels.hip compiles the solver headers a second time with rdis_hip renamed: the import below is renamed
+// with them, the types are not, so the host and both instantiations hand each other the very same structs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-namespace rdis_hip {
+namespace rdis_views {
 
 constexpr int KIND_BA = 0;
 constexpr int KIND_NLP = 1;
@@ -130,4 +134,62 @@ struct PlanView {
     int dump_iters;
 };
 
-}  // namespace rdis_hip
+// ---- exchange state of the cooperative solvers (grid_sync.hpp has the protocol) ----
+constexpr int COOP_MAX_WG = 512;
+constexpr int COOP_SPEC = 1;  // line-search trial points evaluated per exchange (minimizer.hpp: speculation)
+constexpr int COOP_K = (2 * COOP_SPEC > 3 ? 2 * COOP_SPEC : 3);  // values per exchange
+constexpr int COOP_NBUF = 4;
+constexpr int COOP_MAX_WAVES = 8;  // waves per workgroup of the grid solvers (512 lanes)
+constexpr int COOP_KP = (COOP_K + 1) / 2 * 2;   // granules per entry, padded to 16-byte pairs
+struct CoopState {
+    // [COOP_NBUF buffers][entries: workgroup * waves + wave][COOP_KP] granules -- the values an entry
+    // publishes in one exchange are neighbours, written and read two at a time (16 bytes: half the
+    // memory operations of a sweep; each half is still checked on its own, nothing relies on the
+    // pair arriving together) -- then an abort word
+    alignas(32) unsigned long long granule[COOP_NBUF][COOP_MAX_WG * COOP_MAX_WAVES][COOP_KP];
+    unsigned int abort_flag;
+    unsigned int pad[15];
+};
+
+// the same for a small group: a component shared by a few workgroups of the point-major streaming solver
+// (solver_ptm.hpp), one state per group that runs concurrently -- up to a hundred or so per launch
+constexpr int SMALL_COOP_ENTRIES = 256;   // workgroups x waves of a group
+struct SmallCoopState {
+    alignas(32) unsigned long long granule[COOP_NBUF][SMALL_COOP_ENTRIES][COOP_KP];
+    unsigned int abort_flag;
+    unsigned int pad[15];
+};
+
+// ... and for a WIDE group of that solver (a large share of the device on one component): a CoopState whose entries are one per
+// WORKGROUP -- its first wave publishes values the caller has already summed over the workgroup (every lane holds them) --
+// 256 entries to sweep instead of 2048
+struct WideCoopState : CoopState {};
+
+// ---- arguments of the cooperative solvers (solver_coop.hpp, solver_pipe.hpp) ----
+struct CoopArgs {
+    long long* timing;     // [8] cycle accumulators written by lane 0 (profiling aid)
+    CoopState* st;
+    const int* slot_li;    // [12 * m]: local free index of each factor slot or -1 (constant)
+    const int* lane_var;   // [nwg * threads]: free variable owned by this lane or -1
+    const int* wave_var;   // [nwg * threads / 64]: free variable owned by this wave or -1
+    double* xi_glob;       // [n] published search direction
+    int comp;
+    int poll_delay;        // x64 cycles between publishing and the first sweep (a store needs about that long to land)
+    int speculate;         // evaluate guesses at the following trial steps with every line-search trial (minimizer.hpp)
+    int reference_slope;   // plan option factor_rounding = 1, the PARITY option: every sum a trial or a CG iteration forms is added in the
+                           // reference's order -- the objective over the factors in list order, every variable's partials in factor-list
+                           // order, gradient times direction and the Polak-Ribiere sums over the variables in list order (solver_coop.hpp:
+                           // ordered_sums; looked at by the reference-rounding instantiation only, refround_kernels.hip)
+    int stale;             // ... with it, plan option emulate_stale_cache: the reference's factor cache (Variable.cpp:66-76, Factor.h:228-234)
+};
+
+// One launch solves several components side by side: workgroups [wg0, wg0 + nwg) of the grid form
+// the group of component a.comp, with its own exchange state; groups never talk to each other.
+struct CoopGroup {
+    CoopArgs a;
+    int wg0, nwg;
+};
+
+}  // namespace rdis_views
+
+namespace rdis_hip { using namespace rdis_views; }

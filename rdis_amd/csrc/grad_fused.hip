@@ -1,5 +1,6 @@
 // grad_fused.hip -- kernels of the fused value + gradient pass (grad_fused.hpp) and their launches.
 #include "grad_fused.hpp"
+#include "launch_dispatch.hpp"
 #include "solver_wg.hpp"
 
 namespace rdis_hip {
@@ -281,12 +282,7 @@ hipError_t grad_camera_records_launch(hipStream_t s, int grid, const double* x, 
 }
 hipError_t grad_fused_launch(hipStream_t s, int grid, size_t dyn, const GradTables& T, const double* x, const double2* obs,
                              const double* camrec, double* cstage, double* pstage, double* partial, double* g) {
-    if (dyn > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)grad_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-        if (e != hipSuccess) return e;
-    }
-    grad_fused_kernel<<<grid, GRAD_LANES, dyn, s>>>(T, x, obs, camrec, cstage, pstage, partial, g);
-    return hipGetLastError();
+    return launch_dyn(grad_fused_kernel, grid, GRAD_LANES, dyn, s, T, x, obs, camrec, cstage, pstage, partial, g);
 }
 hipError_t grad_combine_launch(hipStream_t s, int grid, const GradTables& T, const double* cstage, const double* pstage, double* g) {
     grad_combine_kernel<<<grid, 256, 0, s>>>(T, cstage, pstage, g);

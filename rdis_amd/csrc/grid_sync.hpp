@@ -34,11 +34,7 @@
 
 namespace rdis_hip {
 
-constexpr int COOP_MAX_WG = 512;
-constexpr int COOP_SPEC = 1;  // line-search trial points evaluated per exchange (minimizer.hpp: speculation)
-constexpr int COOP_K = (2 * COOP_SPEC > 3 ? 2 * COOP_SPEC : 3);  // values per exchange
-constexpr int COOP_NBUF = 4;
-constexpr int COOP_MAX_WAVES = 8;  // waves per workgroup of the grid solvers (512 lanes)
+// (COOP_MAX_WG, COOP_SPEC, COOP_K, COOP_KP, COOP_NBUF, COOP_MAX_WAVES and the exchange states themselves: device_views.hpp)
 enum : int { SYNC_NONE = 0, SYNC_DRAIN = 1, SYNC_FENCE = 2 };
 constexpr int COOP_TM = 32;  // debug counters (rdis_hip_plan_debug_counters)
 constexpr int COOP_LONG_LIST = 48;  // variables fed by more partials than this are wave-owned
@@ -62,31 +58,7 @@ typedef __attribute__((address_space(1))) unsigned int gu32;
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) u64x2 gu64x2;
 
-constexpr int COOP_KP = (COOP_K + 1) / 2 * 2;   // granules per entry, padded to 16-byte pairs
-struct CoopState {
-    // [COOP_NBUF buffers][entries: workgroup * waves + wave][COOP_KP] granules -- the values an entry
-    // publishes in one exchange are neighbours, written and read two at a time (16 bytes: half the
-    // memory operations of a sweep; each half is still checked on its own, nothing relies on the
-    // pair arriving together) -- then an abort word
-    alignas(32) unsigned long long granule[COOP_NBUF][COOP_MAX_WG * COOP_MAX_WAVES][COOP_KP];
-    unsigned int abort_flag;
-    unsigned int pad[15];
-};
 inline size_t coop_state_bytes() { return sizeof(CoopState); }
-
-// the same for a small group: a component shared by a few workgroups of the point-major streaming solver
-// (solver_ptm.hpp), one state per group that runs concurrently -- up to a hundred or so per launch
-constexpr int SMALL_COOP_ENTRIES = 256;   // workgroups x waves of a group
-struct SmallCoopState {
-    alignas(32) unsigned long long granule[COOP_NBUF][SMALL_COOP_ENTRIES][COOP_KP];
-    unsigned int abort_flag;
-    unsigned int pad[15];
-};
-
-// ... and for a WIDE group of that solver (a large share of the device on one component): a CoopState whose entries are one per
-// WORKGROUP -- its first wave publishes values the caller has already summed over the workgroup (every lane holds them) --
-// 256 entries to sweep instead of 2048
-struct WideCoopState : CoopState {};
 
 template <class ST>
 struct GridSyncT {

@@ -9,8 +9,6 @@
 
 namespace rdis_hip {
 
-struct SmallCoopState;
-
 constexpr int PT_REC = 6;    // doubles per point record: p, xi of the block's three variables
 constexpr int PT_BND = 6;    // ... its bounds: lo[3], hi[3] -- floats rounded inward (PB), exact doubles (PE)
 #ifndef RDIS_PTM_BLK

@@ -1,27 +1,17 @@
 // ptm_kernels.hip -- the point-major streaming solver's kernels (solver_ptm.hpp) and their launches, a translation
-// unit of their own (they are the library's largest kernels; rdis_hip.hip sees them through ptm_api.hpp).
+// unit of their own (they are the library's largest kernels; rdis_hip.hip sees them through ptm_api.hpp).  A workgroup size
+// becomes a template argument through launch_dispatch.hpp: 256, 512, and 768 for everything else.
 #include "solver_ptm.hpp"
+#include "launch_dispatch.hpp"
 
 namespace rdis_hip {
 
 template <int ROT>
 static hipError_t ptm_launch_rot(int threads, int grid, size_t dyn, hipStream_t stream, const ProblemView& P, const PlanView& V,
                                  int maxiters, double ftol, int ncb_cap) {
-#define RDIS_PTM_LAUNCH(T)                                                                                                      \
-    do {                                                                                                                        \
-        if (dyn > 48 * 1024) {                                                                                                  \
-            hipError_t e = hipFuncSetAttribute((const void*)cgd_ptm_kernel<T, ROT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn); \
-            if (e != hipSuccess) return e;                                                                                      \
-        }                                                                                                                       \
-        cgd_ptm_kernel<T, ROT><<<grid, T, dyn, stream>>>(P, V, maxiters, ftol, ncb_cap);                                         \
-    } while (0)
-    switch (threads) {
-        case 256: RDIS_PTM_LAUNCH(256); break;
-        case 512: RDIS_PTM_LAUNCH(512); break;
-        default: RDIS_PTM_LAUNCH(768); break;
-    }
-#undef RDIS_PTM_LAUNCH
-    return hipGetLastError();
+    return with_threads<256, 512, 768>(threads, [&](auto T) {
+        return launch_dyn(cgd_ptm_kernel<T.value, ROT>, grid, T.value, dyn, stream, P, V, maxiters, ftol, ncb_cap);
+    });
 }
 
 hipError_t ptm_launch(int rot, int threads, int grid, size_t dyn, hipStream_t stream, const ProblemView& P, const PlanView& V,
@@ -36,11 +26,7 @@ template <int ROT>
 static const void* ptmg_kernel_ptr(int threads, bool wide, bool local) {
     if (wide && local) return (const void*)cgd_ptmg_kernel<PTM_WIDE_THREADS, ROT, true, true>;
     if (wide) return (const void*)cgd_ptmg_kernel<PTM_WIDE_THREADS, ROT, true>;
-    switch (threads) {
-        case 256: return (const void*)cgd_ptmg_kernel<256, ROT>;
-        case 512: return (const void*)cgd_ptmg_kernel<512, ROT>;
-        default: return (const void*)cgd_ptmg_kernel<768, ROT>;
-    }
+    return with_threads<256, 512, 768>(threads, [](auto T) { return (const void*)cgd_ptmg_kernel<T.value, ROT>; });
 }
 const void* ptmg_kernel_fn(int rot, int threads, bool wide, bool local) {
     switch (rot) {

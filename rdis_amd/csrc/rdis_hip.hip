@@ -32,6 +32,13 @@
 
 using namespace rdis_hip;
 
+// The one place that knows there are two roundings: a solver's launches in the default rounding (fused multiply-adds), and
+// the set to use (refround_api.hpp).  A plan asks with coop_reference_rounding() or batch_reference_rounding().
+static const SolverSet& solver_set(bool reference_rounding) {
+    static const SolverSet fused = {launch_pipe, launch_coop, pipe_max_workgroups, coop_max_workgroups, launch_lds};
+    return reference_rounding ? refround_solvers() : fused;
+}
+
 struct rdis_hip_ctx {
     int device = 0;                   // the device as the caller names it
     int phys = 0;                     // ... and the GPU behind it (the same, except under RDIS_HIP_VIRTUAL_DEVICES: tests)
@@ -1145,7 +1152,7 @@ extern "C" int rdis_hip_eval_each(rdis_hip_problem* p, int64_t nf, const int64_t
     if ((rc = ensure(c, p->tmp_out, (size_t)nf * sizeof(double)))) return rc;
     ProblemView V = p->view();
     const int blocks = grid_for(c, nf, 256);
-    if (p->kind == KIND_BA && p->each_rounding == 1) HIPCHK(c, refround_eval_each(blocks, c->stream, &V, (int)nf, dfac, p->tmp_out.as<double>()));
+    if (p->kind == KIND_BA && p->each_rounding == 1) HIPCHK(c, refround_eval_each(blocks, c->stream, V, (int)nf, dfac, p->tmp_out.as<double>()));
     else if (p->kind == KIND_BA) eval_each_kernel<KIND_BA><<<blocks, 256, 0, c->stream>>>(V, (int)nf, dfac, p->tmp_out.as<double>());
     else eval_each_kernel<KIND_NLP><<<blocks, 256, 0, c->stream>>>(V, (int)nf, dfac, p->tmp_out.as<double>());
     HIPCHK(c, hipGetLastError());
@@ -1168,7 +1175,7 @@ extern "C" int rdis_hip_grad_each_ba(rdis_hip_problem* p, int64_t nf, const int6
     if ((rc = ensure(c, p->tmp_out, (size_t)nf * 12 * sizeof(double)))) return rc;
     ProblemView V = p->view();
     if (p->each_rounding == 1) {
-        HIPCHK(c, refround_grad_each(grid_for(c, nf, 256), c->stream, &V, (int)nf, dfac, p->tmp_out.as<double>()));
+        HIPCHK(c, refround_grad_each(grid_for(c, nf, 256), c->stream, V, (int)nf, dfac, p->tmp_out.as<double>()));
     } else {
         partials_kernel<KIND_BA><<<grid_for(c, nf, 256), 256, 0, c->stream>>>(V, (int)nf, dfac, p->gfac.as<double>());
         HIPCHK(c, hipGetLastError());
@@ -1653,8 +1660,8 @@ int prepare_partition(rdis_hip_plan* L) {
         const bool rr = L->coop_reference_rounding();
         int& kc = rr ? c->cap_coop_rr[ti] : c->cap_coop[ti];
         int& kp = rr ? c->cap_pipe_rr : c->cap_pipe;
-        if (L->pipelined() && kp < 0) kp = rr ? refround_pipe_max_workgroups(c->num_cus) : pipe_max_workgroups(c->num_cus);
-        if (!L->pipelined() && kc < 0) kc = rr ? refround_coop_max_workgroups(L->coop_threads, c->num_cus) : coop_max_workgroups(L->coop_threads, c->num_cus);
+        if (L->pipelined() && kp < 0) kp = solver_set(rr).pipe_max_workgroups(c->num_cus);
+        if (!L->pipelined() && kc < 0) kc = solver_set(rr).coop_max_workgroups(L->coop_threads, c->num_cus);
         int k = L->pipelined() ? kp : kc;
         if (L->coop_workgroups > 0) k = std::min(k, L->coop_workgroups);
         return k;
@@ -2311,41 +2318,9 @@ int launch_wg(rdis_hip_plan* L, hipStream_t stream, int threads, int first, int 
     P.xrot = L->prob->xrot.as<double>(); P.rot_mode = L->rest_rot_mode;
     PlanView V = L->view();
     V.order += first;   // components [first, first + grid) of the batch list
-    switch (threads) {
-        case 64: cgd_wg_kernel<KIND, 64><<<grid, 64, 0, stream>>>(P, V, maxiters, ftol); break;
-        case 128: cgd_wg_kernel<KIND, 128><<<grid, 128, 0, stream>>>(P, V, maxiters, ftol); break;
-        case 256: cgd_wg_kernel<KIND, 256><<<grid, 256, 0, stream>>>(P, V, maxiters, ftol); break;
-        case 512: cgd_wg_kernel<KIND, 512><<<grid, 512, 0, stream>>>(P, V, maxiters, ftol); break;
-        case 768: cgd_wg_kernel<KIND, 768><<<grid, 768, 0, stream>>>(P, V, maxiters, ftol); break;
-        default: cgd_wg_kernel<KIND, 1024><<<grid, 1024, 0, stream>>>(P, V, maxiters, ftol); break;
-    }
-    HIPCHK(c, hipGetLastError());
-    return 0;
-}
-template <int ROT>
-int launch_lds_rot(rdis_hip_plan* L, hipStream_t stream, int threads, int first, int grid, int maxiters, double ftol) {
-    rdis_hip_ctx* c = L->prob->ctx;
-    ProblemView P = L->prob->view();
-    PlanView V = L->view();
-    V.order += first;
-    const size_t dyn = L->lds_dyn_bytes(c);
-    const int nsc = L->lds_ns_cap, ncc = L->lds_ncb_cap, chc = L->lds_chunk_cap;
-#define RDIS_LDS_LAUNCH(T)                                                                                              \
-    do {                                                                                                                \
-        if (dyn > 48 * 1024)                                                                                            \
-            HIPCHK(c, hipFuncSetAttribute((const void*)cgd_lds_kernel<T, ROT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
-        cgd_lds_kernel<T, ROT><<<grid, T, dyn, stream>>>(P, V, maxiters, ftol, nsc, ncc, chc);                                \
-    } while (0)
-    switch (threads) {
-        case 64: RDIS_LDS_LAUNCH(64); break;
-        case 128: RDIS_LDS_LAUNCH(128); break;
-        case 256: RDIS_LDS_LAUNCH(256); break;
-        case 512: RDIS_LDS_LAUNCH(512); break;
-        case 768: RDIS_LDS_LAUNCH(768); break;
-        default: RDIS_LDS_LAUNCH(1024); break;
-    }
-#undef RDIS_LDS_LAUNCH
-    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, (with_threads<64, 128, 256, 512, 768, 1024>(threads, [&](auto T) {
+        return launch_dyn(cgd_wg_kernel<KIND, T.value>, grid, T.value, 0, stream, P, V, maxiters, ftol);
+    })));
     return 0;
 }
 // The gradient's rounds of the point-major streaming solver (solver_ptm.hpp: gradient_to_xi) for workgroups of
@@ -2588,47 +2563,15 @@ int launch_ptm_groups(rdis_hip_plan* L, hipStream_t stream, int threads, int fir
     HIPCHK(c, hipLaunchCooperativeKernel(fn, dim3(grid), dim3(threads), args, dyn, stream));
     return 0;
 }
-int launch_lds_stale(rdis_hip_plan* L, hipStream_t stream, int threads, int first, int grid, int maxiters, double ftol) {
+int launch_lds(rdis_hip_plan* L, hipStream_t stream, int threads, int first, int grid, int maxiters, double ftol) {
     rdis_hip_ctx* c = L->prob->ctx;
     ProblemView P = L->prob->view();
     PlanView V = L->view();
     V.order += first;
-    const size_t dyn = lds_bytes_for(L->lds_ns_cap, L->lds_ncb_cap, L->lds_chunk_cap);
-    const int nsc = L->lds_ns_cap, ncc = L->lds_ncb_cap, chc = L->lds_chunk_cap;
-#define RDIS_LDS_LAUNCH(T)                                                                                              \
-    do {                                                                                                                \
-        if (dyn > 48 * 1024)                                                                                            \
-            HIPCHK(c, hipFuncSetAttribute((const void*)cgd_lds_kernel<T, ROT_PER_FACTOR, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
-        cgd_lds_kernel<T, ROT_PER_FACTOR, true><<<grid, T, dyn, stream>>>(P, V, maxiters, ftol, nsc, ncc, chc);                \
-    } while (0)
-    switch (threads) {
-        case 64: RDIS_LDS_LAUNCH(64); break;
-        case 128: RDIS_LDS_LAUNCH(128); break;
-        case 256: RDIS_LDS_LAUNCH(256); break;
-        case 512: RDIS_LDS_LAUNCH(512); break;
-        case 768: RDIS_LDS_LAUNCH(768); break;
-        default: RDIS_LDS_LAUNCH(1024); break;
-    }
-#undef RDIS_LDS_LAUNCH
-    HIPCHK(c, hipGetLastError());
+    // (lds_dyn_bytes is plain lds_bytes_for(...) under the stale cache and the parity option: lds_matrix_on() is false with either)
+    HIPCHK(c, solver_set(L->batch_reference_rounding()).launch_lds(L->lds_rot_mode, L->emulate_stale ? 1 : 0, threads, grid, L->lds_dyn_bytes(c), stream, P, V,
+                                                                   maxiters, ftol, L->lds_ns_cap, L->lds_ncb_cap, L->lds_chunk_cap));
     return 0;
-}
-int launch_lds(rdis_hip_plan* L, hipStream_t stream, int threads, int first, int grid, int maxiters, double ftol) {
-    if (L->emulate_stale && !L->batch_reference_rounding()) return launch_lds_stale(L, stream, threads, first, grid, maxiters, ftol);
-    if (L->batch_reference_rounding()) {
-        rdis_hip_ctx* c = L->prob->ctx;
-        ProblemView P = L->prob->view();
-        PlanView V = L->view();
-        V.order += first;
-        HIPCHK(c, refround_launch_lds(L->lds_rot_mode, L->emulate_stale ? 1 : 0, threads, grid, lds_bytes_for(L->lds_ns_cap, L->lds_ncb_cap, L->lds_chunk_cap), stream, &P, &V,
-                                      maxiters, ftol, L->lds_ns_cap, L->lds_ncb_cap, L->lds_chunk_cap));
-        return 0;
-    }
-    switch (L->lds_rot_mode) {
-        case ROT_CAMFIX: return launch_lds_rot<ROT_CAMFIX>(L, stream, threads, first, grid, maxiters, ftol);
-        case ROT_RECORDS: return launch_lds_rot<ROT_RECORDS>(L, stream, threads, first, grid, maxiters, ftol);
-        default: return launch_lds_rot<ROT_PER_FACTOR>(L, stream, threads, first, grid, maxiters, ftol);
-    }
 }
 }  // namespace
 
@@ -2705,18 +2648,12 @@ extern "C" int rdis_hip_plan_solve(rdis_hip_plan* L, int32_t maxiters, double ft
     for (size_t l = 0; l < L->coop_launches.size(); ++l) {
         const CoopLaunch& cl = L->coop_launches[l];
         const ProblemView PVc = p->view();
-        int rc;
-        if (L->coop_reference_rounding())
-            rc = L->pipelined()
-                     ? refround_launch_pipe(c->stream, p->kind, &PVc, &V, &L->h_coop_groups[l][0], cl.groups.p, cl.wg_group.as<int>(), cl.count, cl.total_wg, maxiters, ftol)
-                     : refround_launch_coop(c->stream, p->kind, &PVc, &V, &L->h_coop_groups[l][0], cl.groups.p, cl.wg_group.as<int>(), cl.count, cl.total_wg,
-                                            L->coop_threads, maxiters, ftol);
-        else
-            rc = L->pipelined()
-                     ? launch_pipe(c->stream, p->kind, PVc, V, L->h_coop_groups[l][0], cl.groups.as<CoopGroup>(), cl.wg_group.as<int>(),
-                                   cl.count, cl.total_wg, maxiters, ftol)
-                     : launch_coop(c->stream, p->kind, PVc, V, L->h_coop_groups[l][0], cl.groups.as<CoopGroup>(), cl.wg_group.as<int>(),
-                                   cl.count, cl.total_wg, L->coop_threads, maxiters, ftol);
+        const SolverSet& S = solver_set(L->coop_reference_rounding());
+        int rc = L->pipelined()
+                     ? S.launch_pipe(c->stream, p->kind, PVc, V, L->h_coop_groups[l][0], cl.groups.as<CoopGroup>(), cl.wg_group.as<int>(),
+                                     cl.count, cl.total_wg, maxiters, ftol)
+                     : S.launch_coop(c->stream, p->kind, PVc, V, L->h_coop_groups[l][0], cl.groups.as<CoopGroup>(), cl.wg_group.as<int>(),
+                                     cl.count, cl.total_wg, L->coop_threads, maxiters, ftol);
         if (rc != 0) return fail(c, RDIS_HIP_EDEVICE, std::string("cooperative solver launch: ") + hipGetErrorString((hipError_t)rc));
         ++L->last_launches;
     }

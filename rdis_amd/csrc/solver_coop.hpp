@@ -33,25 +33,9 @@
 // into launches of at most the resident capacity.  Bundle adjustment only (fixed arity 12).
 #pragma once
 #include "grid_sync.hpp"
+#include "launch_dispatch.hpp"
 
 namespace rdis_hip {
-
-struct CoopArgs {
-    long long* timing;     // [8] cycle accumulators written by lane 0 (profiling aid)
-    CoopState* st;
-    const int* slot_li;    // [12 * m]: local free index of each factor slot or -1 (constant)
-    const int* lane_var;   // [nwg * threads]: free variable owned by this lane or -1
-    const int* wave_var;   // [nwg * threads / 64]: free variable owned by this wave or -1
-    double* xi_glob;       // [n] published search direction
-    int comp;
-    int poll_delay;        // x64 cycles between publishing and the first sweep (a store needs about that long to land)
-    int speculate;         // evaluate guesses at the following trial steps with every line-search trial (minimizer.hpp)
-    int reference_slope;   // plan option factor_rounding = 1, the PARITY option: every sum a trial or a CG iteration forms is added in the
-                           // reference's order -- the objective over the factors in list order, every variable's partials in factor-list
-                           // order, gradient times direction and the Polak-Ribiere sums over the variables in list order (ordered_sums, below;
-                           // looked at by the reference-rounding instantiation only, refround_kernels.hip)
-    int stale;             // ... with it, plan option emulate_stale_cache: the reference's factor cache (Variable.cpp:66-76, Factor.h:228-234)
-};
 
 // the CG recurrence of one free variable
 struct VarState {
@@ -456,13 +440,7 @@ struct CoopEnv {
     }
 };
 
-// One launch solves several components side by side: workgroups [wg0, wg0 + nwg) of the grid form
-// the group of component a.comp, with its own exchange state; groups never talk to each other.
-constexpr int COOP_MAX_GROUPS = 256;
-struct CoopGroup {
-    CoopArgs a;
-    int wg0, nwg;
-};
+constexpr int COOP_MAX_GROUPS = 256;   // groups (CoopGroup, device_views.hpp) side by side in one launch
 
 // body shared by the two entry points below
 template <int THREADS>
@@ -529,7 +507,14 @@ __global__ void __launch_bounds__(256) coop_arm_kernel(const CoopGroup* __restri
     if (threadIdx.x == 0) st->abort_flag = 0u;
 }
 
-// host side: returns hipSuccess (0) or a hipError_t.  groups / wg_group: device arrays (ngroups
+// host side.  The kernel for a workgroup of `threads` lanes (512 or 128; 256 for everything else), one group or several
+inline const void* coop_kernel_fn(int threads, bool single) {
+    return with_threads<512, 128, 256>(threads, [single](auto T) {
+        return single ? (const void*)cgd_coop_single_kernel<T.value> : (const void*)cgd_coop_kernel<T.value>;
+    });
+}
+
+// returns hipSuccess (0) or a hipError_t.  groups / wg_group: device arrays (ngroups
 // entries / one entry per workgroup of the launch); first: host copy of groups[0]
 inline int launch_coop(hipStream_t stream, int kind, const ProblemView& P, const PlanView& V, const CoopGroup& first,
                        const CoopGroup* groups, const int* wg_group, int ngroups, int total_wg, int threads, int maxiters, double ftol) {
@@ -544,26 +529,17 @@ inline int launch_coop(hipStream_t stream, int kind, const ProblemView& P, const
     if (ngroups == 1) {
         CoopArgs a = first.a;
         void* args[] = {&p, &v, &a, &mi, &ft};
-        const void* fn = threads == 512 ? (const void*)cgd_coop_single_kernel<512>
-                       : threads == 128 ? (const void*)cgd_coop_single_kernel<128>
-                                        : (const void*)cgd_coop_single_kernel<256>;
-        return (int)hipLaunchCooperativeKernel(fn, dim3(total_wg), dim3(threads), args, 0, stream);
+        return (int)hipLaunchCooperativeKernel(coop_kernel_fn(threads, true), dim3(total_wg), dim3(threads), args, 0, stream);
     }
     const CoopGroup* gp = groups;
     const int* wp = wg_group;
     void* args[] = {&p, &v, &gp, &wp, &mi, &ft};
-    const void* fn = threads == 512 ? (const void*)cgd_coop_kernel<512>
-                   : threads == 128 ? (const void*)cgd_coop_kernel<128>
-                                    : (const void*)cgd_coop_kernel<256>;
-    return (int)hipLaunchCooperativeKernel(fn, dim3(total_wg), dim3(threads), args, 0, stream);
+    return (int)hipLaunchCooperativeKernel(coop_kernel_fn(threads, false), dim3(total_wg), dim3(threads), args, 0, stream);
 }
 
 inline int coop_max_workgroups(int threads, int num_cus) {
     int per_cu = 0;
-    const void* fn = threads == 512 ? (const void*)cgd_coop_kernel<512>
-                   : threads == 128 ? (const void*)cgd_coop_kernel<128>
-                                    : (const void*)cgd_coop_kernel<256>;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, 0) != hipSuccess) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, coop_kernel_fn(threads, false), threads, 0) != hipSuccess) return 0;
     // stay one block per CU below what the API reports when it reports more than one
     // (MI355X_MICROARCH.md: the query can be one high for SGPR-heavy kernels)
     if (per_cu > 1) per_cu -= 1;

@@ -30,6 +30,7 @@
 // recurrence stay in the plan's workspace (touched twice per iteration).
 #pragma once
 #include "solver_wg.hpp"
+#include "launch_dispatch.hpp"
 
 namespace rdis_hip {
 
@@ -771,6 +772,20 @@ cgd_lds_kernel(ProblemView P, PlanView L, int maxiters, double ftol, int ns_cap,
         }
 #endif
     }
+}
+
+// host side: one launch of `grid` components, a workgroup of `threads` lanes each (64 ... 768; 1024 for everything else), with
+// `dyn` bytes of dynamic LDS.  rot: the ROT_* mode of the launch; stale: the stale-cache emulation, which is instantiated for
+// per-factor rotations only and is launched as such whatever rot says.
+inline hipError_t launch_lds(int rot, int stale, int threads, int grid, size_t dyn, hipStream_t stream, const ProblemView& P, const PlanView& V,
+                             int maxiters, double ftol, int ns_cap, int ncb_cap, int chunk_cap) {
+    return with_threads<64, 128, 256, 512, 768, 1024>(threads, [&](auto T) {
+        auto* kernel = stale ? cgd_lds_kernel<T.value, ROT_PER_FACTOR, true>
+                     : rot == ROT_CAMFIX ? cgd_lds_kernel<T.value, ROT_CAMFIX>
+                     : rot == ROT_RECORDS ? cgd_lds_kernel<T.value, ROT_RECORDS>
+                                          : cgd_lds_kernel<T.value, ROT_PER_FACTOR>;
+        return launch_dyn(kernel, grid, T.value, dyn, stream, P, V, maxiters, ftol, ns_cap, ncb_cap, chunk_cap);
+    });
 }
 
 }  // namespace rdis_hip

@@ -58,7 +58,6 @@
 // A group's workgroups sit on one XCD (blockIdx mod 8 is the same for all of them), so what they hand to
 // each other through plain stores stays in that XCD's L2.
 #pragma once
-#include "solver_lds.hpp"
 #include "grid_sync.hpp"
 #include "ptm_api.hpp"
 
