@@ -228,6 +228,40 @@ int rdis_hip_plan_set_start(rdis_hip_plan *plan, const double *x_start);
 int rdis_hip_plan_solve(rdis_hip_plan *plan, int32_t maxiters, double ftol);
 int rdis_hip_plan_fetch(rdis_hip_plan *plan, double *x_out, double *fret, double *delta,
                         int32_t *iters, int32_t *status, int64_t *nfeval, int64_t *ngeval);
+
+/* ---- multi-start solves: one plan, many starting points, one launch -------------------
+ * RDIS solves a decomposition again and again from other starting values (optBA's sample loop,
+ * src/bundleadjust/optBA.cpp:198-224; a node's random restarts, src/RDISOptimizer.cpp:1087-1094; sampleRandomState,
+ * :1196-1216).  plan_solve_starts solves every component of the plan from each of nstarts rows of start values
+ * exactly as plan_solve would from that row -- the same bits --, one workgroup per (start, component) in one launch
+ * (rdis_amd/csrc/solver_lds_starts.hpp).  Variables that are not free in the plan are constants shared by all
+ * starts, read from the problem's currently assigned x.
+ *   x_starts[s][nfree_total]  row-major; a row is what plan_set_start takes (free-variable order, concatenated
+ *                             over components); copied before the call returns
+ *   x_out[s][nfree_total]; fret, delta, iters, status, nfeval, ngeval [s][ncomp]; best[ncomp]
+ * plan_solve_starts is asynchronous on the context's stream; plan_fetch_starts waits and copies out (any pointer
+ * may be NULL); the outputs of all starts are kept until the next plan_solve_starts.
+ * State afterwards -- what an RDIS node keeps of its restarts, the minimum: best[c] is the start with the lowest
+ * fret[s][c] (the lowest index on a tie; a NaN is never best unless every start of the component is one: then 0);
+ * the free variables of component c are left assigned to that start's result (a following
+ * plan_set_start(plan, NULL) continues from it; an empty component's variables are not touched, as in plan_solve),
+ * and the plan's ordinary outputs -- plan_fetch, plan_objective_device and so the objective's all-reduce -- hold
+ * the best start's row per component.  plan_last_kernel_ms covers the solver launches.
+ * Memory: inputs and outputs for all nstarts starts, and replicas of the per-solve workspace (5 doubles per free
+ * variable and one per partial, per start of a launch), allocated at first use, kept with the plan and reported by
+ * plan_device_bytes.  The plan option "starts_workspace_bytes" (default 1 GiB) bounds the replicas: when nstarts do
+ * not fit, the call runs in several launches of R starts each, R the largest count that fits (at least 1, at most
+ * 65535), the last one possibly with fewer; plan_get_info "starts_per_launch" and "starts_launches" tell R and the
+ * number of launches of the last call.
+ * First version: every component of the plan must go to the LDS-resident solver (plan_get_info "components_lds";
+ * components without factors count as such), with the default factor_rounding and emulate_stale_cache,
+ * trace_records and dump_iters off; nstarts >= 1; plan_fetch_starts needs a plan_solve_starts before it.  Anything
+ * else: RDIS_HIP_EINVAL and a message that names the cause; the plan stays usable. */
+int rdis_hip_plan_solve_starts(rdis_hip_plan *plan, int64_t nstarts, const double *x_starts,
+                               int32_t maxiters, double ftol);
+int rdis_hip_plan_fetch_starts(rdis_hip_plan *plan, double *x_out, double *fret, double *delta,
+                               int32_t *iters, int32_t *status, int64_t *nfeval, int64_t *ngeval,
+                               int32_t *best);
 /* sum of fret over the plan's components, left on the device (for the RCCL
  * all-reduce of the top-level objective, src/RDISOptimizer.cpp:1491-1494);
  * returns a device pointer to one double valid until the next plan_solve. */
@@ -335,6 +369,8 @@ int rdis_hip_comm_allreduce_f64(rdis_hip_comm *comm, double *inout, int32_t n, i
  * Factor.h:228-234 -- a factor keeps its value while its variables have moved by less than 1e-12 since
  * it was computed -- emulated in the LDS-resident batch solver and, with factor_rounding = 1, in the cooperative solver's plain
  * layout; refused where other solvers would run),
+ * "starts_workspace_bytes" (default 1 GiB: device memory the workspace replicas of a multi-start launch may take,
+ * rdis_hip_plan_solve_starts),
  * "trace_records" (per-component trace capacity, 0 = off), "dump_iters" (record p and
  * the search direction at the start of the first k line minimisations, 0 = off). */
 int rdis_hip_plan_set_option(rdis_hip_plan *plan, const char *name, int64_t value);
@@ -343,7 +379,8 @@ int rdis_hip_plan_set_option(rdis_hip_plan *plan, const char *name, int64_t valu
  * "components_point_major", "components_plain" (counts), "pipelined" (0/1: cooperative groups use the
  * pipelined layout), "point_major_group" (workgroups per component in the last solve's point-major launch), "point_major_threads" (their lanes), "point_major_round_slots" (slots a gradient round staged), "grid_stream_workgroups" (workgroups of the first component on the grid solver),
  * "point_major_wide" (0/1: that launch was a wide group), "point_major_local_cameras" (0, or the most cameras a workgroup of
- * a wide group with local camera numbering holds) */
+ * a wide group with local camera numbering holds), "starts_per_launch" / "starts_launches" (starts a launch of the last multi-start
+ * solve held; its number of launches) */
 int rdis_hip_plan_get_info(rdis_hip_plan *plan, const char *name, int64_t *value);
 /* device memory the plan holds beyond the problem's (index tables, workspace, per-factor
  * partials, results): what a host-side cache of plans budgets with

@@ -78,6 +78,8 @@ SYMBOLS = {
     "rdis_hip_plan_set_start": (C.c_int, [_vp, _vp]),
     "rdis_hip_plan_solve": (C.c_int, [_vp, C.c_int32, C.c_double]),
     "rdis_hip_plan_fetch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rdis_hip_plan_solve_starts": (C.c_int, [_vp, _i64, _vp, C.c_int32, C.c_double]),
+    "rdis_hip_plan_fetch_starts": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rdis_hip_plan_objective_device": (C.c_int, [_vp, C.POINTER(_vp)]),
     "rdis_hip_comm_unique_id": (C.c_int, [_vp]),
     "rdis_hip_comm_create": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, C.POINTER(_vp)]),
@@ -235,6 +237,27 @@ class BatchResult:
     status: np.ndarray
     nfeval: np.ndarray
     ngeval: np.ndarray
+
+    @property
+    def exit_reason(self):
+        return self.status & 0xFF
+
+    @property
+    def rolled_back(self):
+        return (self.status & STATUS_ROLLED_BACK) != 0
+
+
+@dataclass
+class StartsResult:
+    """a multi-start solve: x [nstarts, nfree]; the others [nstarts, ncomp]; best [ncomp], the start kept per component"""
+    x: Optional[np.ndarray]
+    fret: np.ndarray
+    delta: np.ndarray
+    iters: np.ndarray
+    status: np.ndarray
+    nfeval: np.ndarray
+    ngeval: np.ndarray
+    best: np.ndarray
 
     @property
     def exit_reason(self):
@@ -490,6 +513,25 @@ class Plan:
             raise ValueError("fetch(out=...): the arrays are another plan's")
         self.ctx.check(self.ctx.lib.rdis_hip_plan_fetch(self.h, _ptr(r.x), _ptr(r.fret), _ptr(r.delta), _ptr(r.iters),
                                                         _ptr(r.status), _ptr(r.nfeval), _ptr(r.ngeval)))
+        return r
+
+    def solve_starts(self, x_starts, maxiters=50, ftol=3e-8):
+        """every component from every row of x_starts [nstarts, nfree] in one launch (asynchronous); afterwards the plan's ordinary
+        outputs and the problem's free variables hold, per component, the start with the lowest value"""
+        xs = _f(x_starts)
+        if xs.ndim != 2 or xs.shape[1] != self.nfree:
+            raise ValueError("x_starts must be [nstarts, nfree]")
+        self.ctx.check(self.ctx.lib.rdis_hip_plan_solve_starts(self.h, xs.shape[0], _ptr(xs), maxiters, ftol))
+        self._nstarts = xs.shape[0]
+
+    def fetch_starts(self, want_x=True) -> StartsResult:
+        """the last multi-start solve's results, start by start, and the start kept per component"""
+        ns, nc = getattr(self, "_nstarts", 0), self.ncomp
+        r = StartsResult(np.empty((ns, self.nfree)) if want_x else None, np.empty((ns, nc)), np.empty((ns, nc)),
+                         np.empty((ns, nc), np.int32), np.empty((ns, nc), np.int32), np.empty((ns, nc), np.int64),
+                         np.empty((ns, nc), np.int64), np.empty(nc, np.int32))
+        self.ctx.check(self.ctx.lib.rdis_hip_plan_fetch_starts(self.h, _ptr(r.x), _ptr(r.fret), _ptr(r.delta), _ptr(r.iters),
+                                                               _ptr(r.status), _ptr(r.nfeval), _ptr(r.ngeval), _ptr(r.best)))
         return r
 
     def objective(self) -> float:

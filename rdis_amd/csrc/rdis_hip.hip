@@ -26,6 +26,7 @@
 #include "solver_coop.hpp"
 #include "solver_lds.hpp"
 #include "ptm_api.hpp"
+#include "starts_api.hpp"
 #include "solver_pipe.hpp"
 #include "solver_quad.hpp"
 #include "solver_stream.hpp"
@@ -354,6 +355,29 @@ struct rdis_hip_plan {
     int dump_iters = 0;
     int last_launches = 0;
     bool timed = false;
+    // multi-start solves (rdis_hip_plan_solve_starts; solver_lds_starts.hpp): inputs and outputs of every start of the last call, kept
+    // until fetched; the replicas of the per-solve workspace one launch needs, bounded by the option "starts_workspace_bytes"
+    int64_t starts_workspace_bytes = 1ll << 30;
+    DevBuf ms_in, ms_out, ms_work, ms_best, ms_stage;   // (ms_stage: pinned host memory the caller's starts are uploaded through)
+    hipEvent_t ms_stage_ev = nullptr;
+    bool ms_stage_busy = false;
+    int64_t ms_n = 0;                 // starts of the last multi-start solve (0: none to fetch)
+    int64_t ms_per_launch = 0, ms_launches = 0;
+    ~rdis_hip_plan() { if (ms_stage_ev) (void)hipEventDestroy(ms_stage_ev); }
+    // the outputs' block for n starts: xout[n][nfree] fret[n][nc] delta[n][nc] (f64) | nfeval[n][nc] ngeval[n][nc] (i64) | iters[n][nc] status[n][nc] (i32)
+    size_t ms_out_bytes(int64_t n) const { return (size_t)n * ((size_t)nfree * 8 + (size_t)ncomp * 40); }
+    StartsView starts_view(int64_t n) const {
+        StartsView s{};
+        const size_t sn = (size_t)n * (size_t)nfree, sc = (size_t)n * (size_t)ncomp;
+        s.xstart = ms_in.as<double>();
+        s.xout = ms_out.as<double>();
+        s.fret = s.xout + sn; s.delta = s.fret + sc;
+        s.nfeval = reinterpret_cast<long long*>(s.delta + sc); s.ngeval = s.nfeval + sc;
+        s.iters = reinterpret_cast<int*>(s.ngeval + sc); s.status = s.iters + sc;
+        s.ws = ms_work.as<double>(); s.gfac = nullptr;   // (gfac: behind the launch's replicas of ws -- the solve knows their number)
+        s.nfree = nfree; s.ngfac = ngfac; s.first = 0;
+        return s;
+    }
 
     const int* ip(size_t off) const { return ints.as<int>() + off; }
     double* out_f64(size_t idx) const { return outbuf.as<double>() + idx; }
@@ -1586,6 +1610,12 @@ extern "C" int rdis_hip_plan_set_option(rdis_hip_plan* L, const char* name, int6
     } else if (n == "coop_poll_delay") {
         if (value < 0 || value > 1024) return fail(c, RDIS_HIP_EINVAL, "coop_poll_delay out of range");
         L->coop_poll_delay = (int)value;
+    } else if (n == "starts_workspace_bytes") {
+        if (value < 0) return fail(c, RDIS_HIP_EINVAL, "starts_workspace_bytes < 0");
+        L->starts_workspace_bytes = value;
+        // (the bound holds from now on: replicas beyond it go; releasing device memory waits for the work that uses it)
+        if (L->ms_work.p && L->ms_work.bytes > (size_t)value) { L->dev_bytes -= std::min(L->dev_bytes, L->ms_work.bytes); L->ms_work.release(); }
+        return 0;   // (no table depends on it)
     } else if (n == "trace_records") {
         if (value < 0 || value > (1 << 22)) return fail(c, RDIS_HIP_EINVAL, "trace_records out of range");
         if (L->transient && value) return fail(c, RDIS_HIP_EINVAL, "tracing needs a persistent plan");
@@ -2563,6 +2593,29 @@ int launch_ptm_groups(rdis_hip_plan* L, hipStream_t stream, int threads, int fir
     HIPCHK(c, hipLaunchCooperativeKernel(fn, dim3(grid), dim3(threads), args, dyn, stream));
     return 0;
 }
+// the workgroup size of the LDS-resident launch (a sum's tree depends on it: the multi-start entry takes the same)
+int lds_launch_threads(const rdis_hip_plan* L) {
+    const rdis_hip_ctx* c = L->prob->ctx;
+    const int64_t mf = L->lds_max_factors;
+    int threads = L->lds_threads ? L->lds_threads : L->block_threads;
+    // A lane per factor up to 512, then 768 lanes (three waves per SIMD) -- unless the launch has more
+    // components than compute units: then 256 lanes, two workgroups per compute unit, so that one
+    // component's arithmetic fills the unit while the other's control step (one lane) or barrier runs
+    // (1000 x 2048 factors: 11.9 against 13.7 ms; 125 of them, a unit each: 3.5 against 4.7 ms)
+    if (threads == 0) threads = mf <= 64 ? 64 : mf <= 128 ? 128 : mf <= 256 ? 256 : L->rest_lds > c->num_cus ? 256 : mf <= 512 ? 512 : 768;
+    return threads;
+}
+// a plan made before rdis_hip_nlp_set_exponential marked one of its factors: the reference's gradient asserts the flag off,
+// src/NonlinearProductFactor.cpp:110 -- refused at a solve as at plan_create, not solved with values and slopes of two functions
+int refuse_late_exponential(rdis_hip_plan* L, const char* who) {
+    rdis_hip_problem* p = L->prob;
+    if (!p->h_useexp.empty())
+        for (int f : L->h_fac_id)
+            if (p->h_useexp[(size_t)f])
+                return fail(p->ctx, RDIS_HIP_EINVAL, std::string(who) + ": factor " + std::to_string(f) + " is exponential (set after the plan was created); "
+                                                     "the reference's gradient asserts it is not (NonlinearProductFactor.cpp:110)");
+    return 0;
+}
 int launch_lds(rdis_hip_plan* L, hipStream_t stream, int threads, int first, int grid, int maxiters, double ftol) {
     rdis_hip_ctx* c = L->prob->ctx;
     ProblemView P = L->prob->view();
@@ -2580,13 +2633,7 @@ extern "C" int rdis_hip_plan_solve(rdis_hip_plan* L, int32_t maxiters, double ft
     rdis_hip_problem* p = L->prob;
     rdis_hip_ctx* c = p->ctx;
     USE_DEVICE(c);
-    // (a plan made before rdis_hip_nlp_set_exponential marked one of its factors: the reference's gradient asserts the flag off,
-    // src/NonlinearProductFactor.cpp:110 -- refused here as at plan_create, not solved with values and slopes of two functions)
-    if (!p->h_useexp.empty())
-        for (int f : L->h_fac_id)
-            if (p->h_useexp[(size_t)f])
-                return fail(c, RDIS_HIP_EINVAL, "plan_solve: factor " + std::to_string(f) + " is exponential (set after the plan was created); "
-                                                "the reference's gradient asserts it is not (NonlinearProductFactor.cpp:110)");
+    if (int rc = refuse_late_exponential(L, "plan_solve")) return rc;
     if (!L->have_start) { int rc = rdis_hip_plan_set_start(L, nullptr); if (rc) return rc; }
     L->last_launches = 0;
     L->timed = false;
@@ -2694,14 +2741,7 @@ extern "C" int rdis_hip_plan_solve(rdis_hip_plan* L, int32_t maxiters, double ft
         ++L->last_launches;
     }
     if (L->rest_lds > 0) {
-        const int64_t mf = L->lds_max_factors;
-        int threads = L->lds_threads ? L->lds_threads : L->block_threads;
-        // A lane per factor up to 512, then 768 lanes (three waves per SIMD) -- unless the launch has more
-        // components than compute units: then 256 lanes, two workgroups per compute unit, so that one
-        // component's arithmetic fills the unit while the other's control step (one lane) or barrier runs
-        // (1000 x 2048 factors: 11.9 against 13.7 ms; 125 of them, a unit each: 3.5 against 4.7 ms)
-        if (threads == 0) threads = mf <= 64 ? 64 : mf <= 128 ? 128 : mf <= 256 ? 256 : L->rest_lds > c->num_cus ? 256 : mf <= 512 ? 512 : 768;
-        int rc = launch_lds(L, bs, threads, L->rest_tiny + rest + L->rest_ptm, L->rest_lds, maxiters, ftol);
+        int rc = launch_lds(L, bs, lds_launch_threads(L), L->rest_tiny + rest + L->rest_ptm, L->rest_lds, maxiters, ftol);
         if (rc) return rc;
         ++L->last_launches;
     }
@@ -2815,6 +2855,141 @@ extern "C" int rdis_hip_plan_fetch(rdis_hip_plan* L, double* x_out, double* fret
     const char* i32 = i64 + 2 * nc * 8;
     if (iters) std::memcpy(iters, i32, nc * 4);
     if (status) std::memcpy(status, i32 + nc * 4, nc * 4);
+    return 0;
+}
+
+// =====================================================================================
+// multi-start solves: one plan, many starting points, one launch (solver_lds_starts.hpp)
+// =====================================================================================
+namespace {
+constexpr size_t STARTS_STAGE_MAX_BYTES = 64u << 20;   // the caller's starts go through pinned memory up to this size
+constexpr int64_t STARTS_MAX_PER_LAUNCH = 65535;       // (the start is the grid's second dimension)
+
+// why a plan cannot be solved from many starts yet -- the first version runs on the LDS-resident solver alone
+int starts_refusal(rdis_hip_plan* L, const char* who) {
+    rdis_hip_problem* p = L->prob;
+    rdis_hip_ctx* c = p->ctx;
+    const std::string w(who);
+    if (L->transient) return fail(c, RDIS_HIP_EINVAL, w + ": needs a persistent plan");
+    if (L->factor_rounding == 1) return fail(c, RDIS_HIP_EINVAL, w + ": the parity option (factor_rounding = 1) has no multi-start entry");
+    if (L->emulate_stale) return fail(c, RDIS_HIP_EINVAL, w + ": emulate_stale_cache has no multi-start entry");
+    if (L->trace_records > 0) return fail(c, RDIS_HIP_EINVAL, w + ": trace_records must be 0 (a trace belongs to one solve)");
+    if (L->dump_iters > 0) return fail(c, RDIS_HIP_EINVAL, w + ": dump_iters must be 0 (a vector dump belongs to one solve)");
+    if (L->partition_dirty || (!L->coop.empty() && L->coop_state_gen != p->coop_state_gen)) { int rc = prepare_partition(L); if (rc) return rc; }
+    // every component on the LDS-resident solver; an empty one (no factor: no table, nothing to solve) counts as such
+    int64_t tiny = 0, ptm = 0, plain = 0;
+    const size_t r_lds = L->h_rest.size() - (size_t)L->rest_lds, r_ptm = r_lds - (size_t)L->rest_ptm;
+    for (size_t r = 0; r < r_lds; ++r) {
+        const int cc = L->h_rest[r];
+        if (L->h_fac_ptr[(size_t)cc + 1] == L->h_fac_ptr[(size_t)cc]) continue;
+        if (r < (size_t)L->rest_tiny) ++tiny; else if (r >= r_ptm) ++ptm; else ++plain;
+    }
+    std::string others;
+    auto note = [&](int64_t count, const char* solver) { if (count > 0) others += (others.empty() ? " " : ", ") + std::to_string(count) + " to the " + solver; };
+    note((int64_t)L->coop.size(), "cooperative solver");
+    note((int64_t)L->stream.size(), "grid solver");
+    note(tiny, "tiny-component solver");
+    note(ptm, "point-major streaming solver");
+    note(plain, "plain batch solver");
+    if (!others.empty())
+        return fail(c, RDIS_HIP_EINVAL, w + ": every component of the plan must run on the LDS-resident solver (bundle adjustment, variables fitting a "
+                                        "compute unit's LDS); this plan sends" + others);
+    return 0;
+}
+}  // namespace
+
+extern "C" int rdis_hip_plan_solve_starts(rdis_hip_plan* L, int64_t nstarts, const double* x_starts, int32_t maxiters, double ftol) {
+    if (!L) return RDIS_HIP_EINVAL;
+    rdis_hip_problem* p = L->prob;
+    rdis_hip_ctx* c = p->ctx;
+    USE_DEVICE(c);
+    if (maxiters <= 0) return fail(c, RDIS_HIP_EINVAL, "plan_solve_starts: maxiters must be positive");
+    if (nstarts < 1) return fail(c, RDIS_HIP_EINVAL, "plan_solve_starts: nstarts must be at least 1");
+    if (!x_starts) return fail(c, RDIS_HIP_EINVAL, "plan_solve_starts: x_starts is NULL (a row of start values per start)");
+    if (nstarts >= (1ll << 31) || (double)nstarts * (double)std::max<int64_t>(std::max(L->nfree, L->ncomp), 1) >= 9.0e15)
+        return fail(c, RDIS_HIP_ERANGE, "plan_solve_starts: too many starts");
+    if (int rc = refuse_late_exponential(L, "plan_solve_starts")) return rc;
+    if (int rc = starts_refusal(L, "plan_solve_starts")) return rc;
+    if (L->ncomp == 0) { L->ms_n = nstarts; L->ms_per_launch = nstarts; L->ms_launches = 0; L->last_launches = 0; L->timed = false; return 0; }
+
+    // replicas of the per-solve workspace (ws, gfac) a launch may hold within the budget: at least one
+    const size_t rep_doubles = 5 * (size_t)L->nfree + (size_t)L->ngfac, rep_bytes = rep_doubles * sizeof(double);
+    int64_t R = rep_bytes ? std::max<int64_t>(1, L->starts_workspace_bytes / (int64_t)rep_bytes) : nstarts;
+    R = std::min(std::min(R, nstarts), STARTS_MAX_PER_LAUNCH);
+    int rc = 0;
+    if (L->ms_work.bytes < (size_t)R * rep_bytes) rc = plan_alloc(L, L->ms_work, (size_t)R * rep_bytes);
+    const size_t in_bytes = (size_t)nstarts * (size_t)L->nfree * sizeof(double);
+    if (!rc && L->ms_in.bytes < in_bytes) rc = plan_alloc(L, L->ms_in, in_bytes);
+    if (!rc && L->ms_out.bytes < L->ms_out_bytes(nstarts)) rc = plan_alloc(L, L->ms_out, L->ms_out_bytes(nstarts));
+    if (!rc && !L->ms_best.p) rc = plan_alloc(L, L->ms_best, (size_t)L->ncomp * sizeof(int));
+    if (rc) return rc;
+    L->ms_n = 0;   // (what an earlier call left is overwritten from here on)
+
+    // the starts: through pinned memory, so that the caller may reuse x_starts the moment this returns and nothing waits
+    if (in_bytes > 0 && in_bytes <= STARTS_STAGE_MAX_BYTES) {
+        if (L->ms_stage_busy) { HIPCHK(c, hipEventSynchronize(L->ms_stage_ev)); L->ms_stage_busy = false; }
+        if (L->ms_stage.bytes < in_bytes) { rc = halloc(c, L->ms_stage, in_bytes); if (rc) return rc; }
+        if (!L->ms_stage_ev) HIPCHK(c, hipEventCreateWithFlags(&L->ms_stage_ev, hipEventDisableTiming));
+        std::memcpy(L->ms_stage.p, x_starts, in_bytes);
+        HIPCHK(c, hipMemcpyAsync(L->ms_in.p, L->ms_stage.p, in_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(L->ms_stage_ev, c->stream));
+        L->ms_stage_busy = true;
+    } else if (in_bytes > 0) {
+        HIPCHK(c, hipMemcpyAsync(L->ms_in.p, x_starts, in_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+
+    const ProblemView P = p->view();
+    PlanView V = L->view();   // (order: the whole batch list -- empty components, then the LDS-resident ones, heaviest first)
+    StartsView S = L->starts_view(nstarts);
+    S.gfac = S.ws + (size_t)R * 5 * (size_t)L->nfree;
+    const int threads = L->rest_lds > 0 ? lds_launch_threads(L) : 64;
+    const size_t dyn = L->lds_dyn_bytes(c);
+    L->last_launches = 0;
+    L->timed = false;
+    HIPCHK(c, hipEventRecord(p->ev0, c->stream));
+    for (int64_t first = 0; first < nstarts; first += R) {   // (launches on one stream: the next takes the replicas when this one is done)
+        S.first = first;
+        HIPCHK(c, starts_launch(L->lds_rot_mode, threads, (int)L->h_rest.size(), (int)std::min(R, nstarts - first), dyn, c->stream, P, V, S,
+                                maxiters, ftol, L->lds_ns_cap, L->lds_ncb_cap, L->lds_chunk_cap));
+        ++L->last_launches;
+    }
+    HIPCHK(c, hipEventRecord(p->ev1, c->stream));
+    L->timed = true;
+    p->last_timed_plan = L;
+    // what the node keeps: the best start per component, as the plan's ordinary outputs and the assignment of its variables
+    S.first = 0;
+    HIPCHK(c, starts_select_launch(c->stream, P, V, S, nstarts, L->ms_best.as<int>()));
+    objective_sum_kernel<<<1, 256, 0, c->stream>>>((int)L->ncomp, V.fret, L->objective.as<double>());
+    HIPCHK(c, hipGetLastError());
+    L->ms_n = nstarts;
+    L->ms_per_launch = R;
+    L->ms_launches = L->last_launches;
+    return 0;
+}
+
+extern "C" int rdis_hip_plan_fetch_starts(rdis_hip_plan* L, double* x_out, double* fret, double* delta, int32_t* iters, int32_t* status,
+                                          int64_t* nfeval, int64_t* ngeval, int32_t* best) {
+    if (!L) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = L->prob->ctx;
+    USE_DEVICE(c);
+    if (L->ms_n < 1) return fail(c, RDIS_HIP_EINVAL, "plan_fetch_starts: no multi-start solve to fetch (call rdis_hip_plan_solve_starts first)");
+    if (L->ncomp == 0) return 0;
+    // every array is one contiguous piece of the outputs' block: straight into the caller's memory
+    const StartsView S = L->starts_view(L->ms_n);
+    const size_t sn = (size_t)L->ms_n * (size_t)L->nfree, sc = (size_t)L->ms_n * (size_t)L->ncomp;
+    auto get = [&](void* dst, const void* src, size_t bytes) {
+        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    HIPCHK(c, get(x_out, S.xout, sn * 8));
+    HIPCHK(c, get(fret, S.fret, sc * 8));
+    HIPCHK(c, get(delta, S.delta, sc * 8));
+    HIPCHK(c, get(nfeval, S.nfeval, sc * 8));
+    HIPCHK(c, get(ngeval, S.ngeval, sc * 8));
+    HIPCHK(c, get(iters, S.iters, sc * 4));
+    HIPCHK(c, get(status, S.status, sc * 4));
+    HIPCHK(c, get(best, L->ms_best.p, (size_t)L->ncomp * 4));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -3023,6 +3198,8 @@ extern "C" int rdis_hip_plan_get_info(rdis_hip_plan* L, const char* name, int64_
     else if (n == "point_major_group") *value = L->ptm_last_group;
     else if (n == "point_major_threads") *value = L->ptm_last_threads;
     else if (n == "point_major_round_slots") *value = L->rounds_slots;
+    else if (n == "starts_per_launch") *value = L->ms_per_launch;
+    else if (n == "starts_launches") *value = L->ms_launches;
     else return fail(c, RDIS_HIP_EINVAL, "plan_get_info: unknown name '" + n + "'");
     return 0;
 }

@@ -774,6 +774,9 @@ cgd_lds_kernel(ProblemView P, PlanView L, int maxiters, double ftol, int ns_cap,
     }
 }
 
+// (a translation unit that wants the solver's device code for kernels of its own, not a second copy of these instantiations, defines
+// RDIS_LDS_NO_LAUNCHER: starts_kernels.hip)
+#ifndef RDIS_LDS_NO_LAUNCHER
 // host side: one launch of `grid` components, a workgroup of `threads` lanes each (64 ... 768; 1024 for everything else), with
 // `dyn` bytes of dynamic LDS.  rot: the ROT_* mode of the launch; stale: the stale-cache emulation, which is instantiated for
 // per-factor rotations only and is launched as such whatever rot says.
@@ -787,5 +790,6 @@ inline hipError_t launch_lds(int rot, int stale, int threads, int grid, size_t d
         return launch_dyn(kernel, grid, T.value, dyn, stream, P, V, maxiters, ftol, ns_cap, ncb_cap, chunk_cap);
     });
 }
+#endif
 
 }  // namespace rdis_hip

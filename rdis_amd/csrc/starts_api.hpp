@@ -1,0 +1,37 @@
+// starts_api.hpp -- what rdis_hip.hip sees of the multi-start entry of the LDS-resident solver (solver_lds_starts.hpp), whose
+// kernels are a translation unit of their own (starts_kernels.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstddef>
+#include "device_views.hpp"
+
+namespace rdis_views {
+
+// The per-solve arrays of a multi-start solve.  Inputs and outputs hold every start of the call, row-major [start][...],
+// and are kept until fetched; the workspace holds the replicas of one launch, which solves the starts first .. first + gridDim.y - 1.
+struct StartsView {
+    const double* xstart;   // [nstarts][nfree]
+    double* xout;           // [nstarts][nfree]
+    double* fret;           // [nstarts][ncomp] ...
+    double* delta;
+    int* iters;
+    int* status;
+    long long* nfeval;
+    long long* ngeval;
+    double* ws;             // [replicas][5 nfree]   PlanView::ws of a replica
+    double* gfac;           // [replicas][ngfac]     PlanView::gfac of a replica
+    long long nfree, ngfac; // row lengths
+    long long first;        // the launch's first start
+};
+
+}  // namespace rdis_views
+
+namespace rdis_hip {
+
+// cgd_lds_starts_kernel<threads, rot>: grid (ncomp_listed, nstarts_of_launch); V.order lists the components
+hipError_t starts_launch(int rot, int threads, int ncomp_listed, int nstarts_of_launch, size_t dyn, hipStream_t stream, const ProblemView& P,
+                         const PlanView& V, const StartsView& S, int maxiters, double ftol, int ns_cap, int ncb_cap, int chunk_cap);
+// select_best_start_kernel over the S.fret of all nstarts starts: best[ncomp], the plan's ordinary outputs, P.x
+hipError_t starts_select_launch(hipStream_t stream, const ProblemView& P, const PlanView& V, const StartsView& S, long long nstarts, int* best);
+
+}  // namespace rdis_hip

@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""Multi-start solves measured: rdis_hip_plan_solve_starts against the same starts solved one by one.
+
+  python tools/bench_multistart.py            # both steps, one JSON line
+  python tools/bench_multistart.py --step config3|config5s   # one step, in this process
+
+config3   BASELINE config 3 (ladybug 5 cameras / 30 points, one component): 320 one-ulp starts -- those of the end-value fixture,
+          tests/golden/end_values.json -- in one call, and the same 320 by set_start / solve / fetch on the same plan.
+config5s  BASELINE config 5-S (1000 components of 3 cameras x 40 points) x 8 starts, likewise.
+Every step runs in a child process under a time limit of its own; a step that fails ends the run.  Wall times are the median of
+`--repeats` calls after one warm-up call; kernel_ms is rdis_hip_plan_last_kernel_ms of the last call."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+STEP_LIMIT_S = {"config3": 240, "config5s": 240}
+
+
+def ulp_perturbed(x0, rng):
+    return np.nextafter(x0, np.where(rng.random(x0.shape) < 0.5, -np.inf, np.inf))
+
+
+def measure(pp, starts, repeats):
+    from rdis_amd import capi
+    ctx = capi.Context(0)
+    g = capi.Problem(ctx, pp)
+    plan = capi.Plan(g)
+    ns = starts.shape[0]
+
+    def together():
+        t = time.perf_counter()
+        plan.solve_starts(starts, 25, 3e-8)
+        r = plan.fetch_starts()
+        return time.perf_counter() - t, r
+
+    def one_by_one():
+        t = time.perf_counter()
+        fret, x = [], []
+        for row in starts:
+            plan.set_start(row)
+            plan.solve(25, 3e-8)
+            r = plan.fetch()
+            fret.append(r.fret.copy()); x.append(r.x.copy())
+        return time.perf_counter() - t, np.array(fret), np.array(x)
+
+    plan.set_start(starts[0]); plan.solve(25, 3e-8); plan.fetch()
+    single_ms = plan.last_kernel_ms()[0]
+    together()
+    tt = []
+    for _ in range(repeats):
+        dt, ms = together()
+        tt.append(dt)
+    kernel_ms, launches = plan.last_kernel_ms()
+    one_by_one()
+    ts = []
+    for _ in range(repeats):
+        dt, fret, x = one_by_one()
+        ts.append(dt)
+    same = bool(fret.tobytes() == ms.fret.tobytes() and x.tobytes() == ms.x.tobytes())
+    wall, seq = float(np.median(tt)), float(np.median(ts))
+    return {"starts": ns, "components": plan.ncomp, "components_lds": plan.info("components_lds"),
+            "starts_per_launch": plan.info("starts_per_launch"), "launches": launches,
+            "wall_ms": 1e3 * wall, "sequential_wall_ms": 1e3 * seq, "speedup": seq / wall,
+            "last_kernel_ms": kernel_ms, "one_solve_kernel_ms": single_ms, "kernel_in_single_solves": kernel_ms / single_ms,
+            "starts_per_second": ns / wall, "sequential_starts_per_second": ns / seq, "bits_equal_sequential": same,
+            "best_fret_sum": float(np.sum(np.min(ms.fret, axis=0))),
+            "device_bytes": plan.device_bytes()}
+
+
+def step(name, repeats):
+    from rdis_amd import problems as P
+    if name == "config3":
+        with open(os.path.join(ROOT, "tests", "golden", "end_values.json")) as fh:
+            seed = json.load(fh)["seed"]
+        pp = P.load_bal(ncams=5, npts=30).single_component()
+        starts = np.stack([ulp_perturbed(pp.x0, np.random.default_rng([seed, 100000 + k])) for k in range(320)])
+    else:
+        pp = P.make_synthetic_ba(1000, 3, 40)
+        rng = np.random.default_rng(17)
+        starts = np.stack([pp.x0] + [ulp_perturbed(pp.x0, rng) for _ in range(7)])
+    return measure(pp, starts, repeats)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--step", choices=sorted(STEP_LIMIT_S))
+    ap.add_argument("--repeats", type=int, default=3)
+    a = ap.parse_args()
+    if a.step:
+        print(json.dumps({a.step: step(a.step, a.repeats)}))
+        return 0
+    out = {"tool": "bench_multistart", "maxiters": 25, "ftol": 3e-8}
+    try:
+        out["commit"] = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
+    except OSError:
+        out["commit"] = None
+    for name in ("config3", "config5s"):
+        try:
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", name, "--repeats", str(a.repeats)],
+                               capture_output=True, text=True, timeout=STEP_LIMIT_S[name])
+        except subprocess.TimeoutExpired:
+            out[name] = {"error": f"time limit of {STEP_LIMIT_S[name]} s"}
+            break
+        if p.returncode != 0:
+            out[name] = {"error": f"exit status {p.returncode}", "stderr": p.stderr[-2000:]}
+            break   # (nothing more is started on a device that a step has just failed on)
+        out.update(json.loads(p.stdout.strip().splitlines()[-1]))
+    print(json.dumps(out))
+    return 0 if all("error" not in out.get(k, {"error": 1}) for k in ("config3", "config5s")) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

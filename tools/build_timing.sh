@@ -3,7 +3,7 @@
 set -e
 cd /root/repo/rdis_amd/csrc
 mkdir -p /root/repo/build_ab/obj_t
-for f in ${FILES:-rdis_hip ptm_kernels grad_fused refround_kernels components lm_solver}; do
+for f in ${FILES:-rdis_hip ptm_kernels starts_kernels grad_fused refround_kernels components lm_solver}; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -DRDIS_COOP_TIMING -c -o /root/repo/build_ab/obj_t/$f.o $f.hip &
 done
 wait
