@@ -234,7 +234,7 @@ int rdis_hip_plan_fetch(rdis_hip_plan *plan, double *x_out, double *fret, double
  * src/bundleadjust/optBA.cpp:198-224; a node's random restarts, src/RDISOptimizer.cpp:1087-1094; sampleRandomState,
  * :1196-1216).  plan_solve_starts solves every component of the plan from each of nstarts rows of start values
  * exactly as plan_solve would from that row -- the same bits --, one workgroup per (start, component) in one launch
- * (rdis_amd/csrc/solver_lds_starts.hpp).  Variables that are not free in the plan are constants shared by all
+ * (rdis_amd/csrc/solver_lds_starts.hpp; nonlinear-product plans: solver_wg_starts.hpp).  Variables that are not free in the plan are constants shared by all
  * starts, read from the problem's currently assigned x.
  *   x_starts[s][nfree_total]  row-major; a row is what plan_set_start takes (free-variable order, concatenated
  *                             over components); copied before the call returns
@@ -248,14 +248,18 @@ int rdis_hip_plan_fetch(rdis_hip_plan *plan, double *x_out, double *fret, double
  * and the plan's ordinary outputs -- plan_fetch, plan_objective_device and so the objective's all-reduce -- hold
  * the best start's row per component.  plan_last_kernel_ms covers the solver launches.
  * Memory: inputs and outputs for all nstarts starts, and replicas of the per-solve workspace (5 doubles per free
- * variable and one per partial, per start of a launch), allocated at first use, kept with the plan and reported by
+ * variable and one per partial, per start of a launch; on the plain batch solver also a copy of the problem's x and
+ * of its search direction, 2 N doubles: that solver keeps its trial point in global memory), allocated at first use, kept with the plan and reported by
  * plan_device_bytes.  The plan option "starts_workspace_bytes" (default 1 GiB) bounds the replicas: when nstarts do
  * not fit, the call runs in several launches of R starts each, R the largest count that fits (at least 1, at most
  * 65535), the last one possibly with fewer; plan_get_info "starts_per_launch" and "starts_launches" tell R and the
  * number of launches of the last call.
- * First version: every component of the plan must go to the LDS-resident solver (plan_get_info "components_lds";
- * components without factors count as such), with the default factor_rounding and emulate_stale_cache,
- * trace_records and dump_iters off; nstarts >= 1; plan_fetch_starts needs a plan_solve_starts before it.  Anything
+ * Scope: every component of the plan goes to the LDS-resident solver (bundle adjustment; plan_get_info
+ * "components_lds"), or the problem is a nonlinear-product one and every component goes to the plain batch solver
+ * ("components_plain": BASELINE configs 1 and 2, every decomposition of the sinusoid); components without factors
+ * count as either.  Not yet: the cooperative, grid, tiny-component and point-major solvers, bundle-adjustment
+ * components on the plain batch solver (their rotation records would need replicas too), transient plans.  With the
+ * default factor_rounding and emulate_stale_cache, trace_records and dump_iters off; nstarts >= 1; plan_fetch_starts needs a plan_solve_starts before it.  Anything
  * else: RDIS_HIP_EINVAL and a message that names the cause; the plan stays usable. */
 int rdis_hip_plan_solve_starts(rdis_hip_plan *plan, int64_t nstarts, const double *x_starts,
                                int32_t maxiters, double ftol);

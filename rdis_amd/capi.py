@@ -517,7 +517,9 @@ class Plan:
 
     def solve_starts(self, x_starts, maxiters=50, ftol=3e-8):
         """every component from every row of x_starts [nstarts, nfree] in one launch (asynchronous); afterwards the plan's ordinary
-        outputs and the problem's free variables hold, per component, the start with the lowest value"""
+        outputs and the problem's free variables hold, per component, the start with the lowest value.  For plans whose components
+        all run on the LDS-resident solver (bundle adjustment) or, on a nonlinear-product problem, all on the plain batch solver
+        (info("components_plain")); anything else raises RdisHipError (EINVAL) with the cause"""
         xs = _f(x_starts)
         if xs.ndim != 2 or xs.shape[1] != self.nfree:
             raise ValueError("x_starts must be [nstarts, nfree]")

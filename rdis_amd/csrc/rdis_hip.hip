@@ -355,10 +355,11 @@ struct rdis_hip_plan {
     int dump_iters = 0;
     int last_launches = 0;
     bool timed = false;
-    // multi-start solves (rdis_hip_plan_solve_starts; solver_lds_starts.hpp): inputs and outputs of every start of the last call, kept
-    // until fetched; the replicas of the per-solve workspace one launch needs, bounded by the option "starts_workspace_bytes"
+    // multi-start solves (rdis_hip_plan_solve_starts; solver_lds_starts.hpp, solver_wg_starts.hpp): inputs and outputs of every start of
+    // the last call, kept until fetched; the replicas of the per-solve workspace one launch needs, bounded by the option
+    // "starts_workspace_bytes" (ms_work: ws, gfac and, for the plain solver, x; ms_dir: that solver's dir, zero between launches)
     int64_t starts_workspace_bytes = 1ll << 30;
-    DevBuf ms_in, ms_out, ms_work, ms_best, ms_stage;   // (ms_stage: pinned host memory the caller's starts are uploaded through)
+    DevBuf ms_in, ms_out, ms_work, ms_dir, ms_best, ms_stage;   // (ms_stage: pinned host memory the caller's starts are uploaded through)
     hipEvent_t ms_stage_ev = nullptr;
     bool ms_stage_busy = false;
     int64_t ms_n = 0;                 // starts of the last multi-start solve (0: none to fetch)
@@ -374,8 +375,9 @@ struct rdis_hip_plan {
         s.fret = s.xout + sn; s.delta = s.fret + sc;
         s.nfeval = reinterpret_cast<long long*>(s.delta + sc); s.ngeval = s.nfeval + sc;
         s.iters = reinterpret_cast<int*>(s.ngeval + sc); s.status = s.iters + sc;
-        s.ws = ms_work.as<double>(); s.gfac = nullptr;   // (gfac: behind the launch's replicas of ws -- the solve knows their number)
-        s.nfree = nfree; s.ngfac = ngfac; s.first = 0;
+        s.ws = ms_work.as<double>(); s.gfac = nullptr;   // (gfac, x: behind the launch's replicas of ws -- the solve knows their number)
+        s.x = nullptr; s.dir = nullptr;
+        s.nfree = nfree; s.ngfac = ngfac; s.N = prob->N; s.first = 0;
         return s;
     }
 
@@ -2605,6 +2607,21 @@ int lds_launch_threads(const rdis_hip_plan* L) {
     if (threads == 0) threads = mf <= 64 ? 64 : mf <= 128 ? 128 : mf <= 256 ? 256 : L->rest_lds > c->num_cus ? 256 : mf <= 512 ? 512 : 768;
     return threads;
 }
+// ... and of the plain batch solver's launch (solver_wg.hpp), likewise shared with the multi-start entry
+int wg_launch_threads(const rdis_hip_plan* L) {
+    int64_t mf = 0;
+    for (size_t i = (size_t)L->rest_tiny; i < L->h_rest.size() - (size_t)L->rest_lds - (size_t)L->rest_ptm; ++i) {
+        const int cc = L->h_rest[i];
+        mf = std::max<int64_t>(mf, std::max<int64_t>(L->h_fac_ptr[(size_t)cc + 1] - L->h_fac_ptr[(size_t)cc],
+                                                     (L->h_free_ptr[(size_t)cc + 1] - L->h_free_ptr[(size_t)cc]) / 4));
+    }
+    int threads = L->block_threads;
+    // More than 512 factors: 768 lanes = three waves per SIMD at 168 registers (a few spills) beat
+    // two waves at 250 and four at 128 (heavy spills): +20 % / +40 % throughput on large components,
+    // and 5 % on the 361..906-factor camera components of ladybug.
+    if (threads == 0) threads = mf <= 64 ? 64 : mf <= 128 ? 128 : mf <= 256 ? 256 : mf <= 512 ? 512 : 768;
+    return threads;
+}
 // a plan made before rdis_hip_nlp_set_exponential marked one of its factors: the reference's gradient asserts the flag off,
 // src/NonlinearProductFactor.cpp:110 -- refused at a solve as at plan_create, not solved with values and slopes of two functions
 int refuse_late_exponential(rdis_hip_plan* L, const char* who) {
@@ -2801,17 +2818,7 @@ extern "C" int rdis_hip_plan_solve(rdis_hip_plan* L, int32_t maxiters, double ft
         ++L->last_launches;
     }
     if (rest > 0) {
-        int64_t mf = 0;
-        for (size_t i = (size_t)L->rest_tiny; i < L->h_rest.size() - (size_t)L->rest_lds - (size_t)L->rest_ptm; ++i) {
-            const int cc = L->h_rest[i];
-            mf = std::max<int64_t>(mf, std::max<int64_t>(L->h_fac_ptr[(size_t)cc + 1] - L->h_fac_ptr[(size_t)cc],
-                                                         (L->h_free_ptr[(size_t)cc + 1] - L->h_free_ptr[(size_t)cc]) / 4));
-        }
-        int threads = L->block_threads;
-        // More than 512 factors: 768 lanes = three waves per SIMD at 168 registers (a few spills) beat
-        // two waves at 250 and four at 128 (heavy spills): +20 % / +40 % throughput on large components,
-        // and 5 % on the 361..906-factor camera components of ladybug.
-        if (threads == 0) threads = mf <= 64 ? 64 : mf <= 128 ? 128 : mf <= 256 ? 256 : mf <= 512 ? 512 : 768;
+        const int threads = wg_launch_threads(L);
         int rc = p->kind == KIND_BA ? launch_wg<KIND_BA>(L, bs, threads, L->rest_tiny, rest, maxiters, ftol)
                                     : launch_wg<KIND_NLP>(L, bs, threads, L->rest_tiny, rest, maxiters, ftol);
         if (rc) return rc;
@@ -2859,14 +2866,15 @@ extern "C" int rdis_hip_plan_fetch(rdis_hip_plan* L, double* x_out, double* fret
 }
 
 // =====================================================================================
-// multi-start solves: one plan, many starting points, one launch (solver_lds_starts.hpp)
+// multi-start solves: one plan, many starting points, one launch (solver_lds_starts.hpp, solver_wg_starts.hpp)
 // =====================================================================================
 namespace {
 constexpr size_t STARTS_STAGE_MAX_BYTES = 64u << 20;   // the caller's starts go through pinned memory up to this size
 constexpr int64_t STARTS_MAX_PER_LAUNCH = 65535;       // (the start is the grid's second dimension)
 
-// why a plan cannot be solved from many starts yet -- the first version runs on the LDS-resident solver alone
-int starts_refusal(rdis_hip_plan* L, const char* who) {
+// why a plan cannot be solved from many starts yet.  Two kinds of plan can: every component on the LDS-resident solver (bundle
+// adjustment), or a nonlinear-product problem with every component on the plain batch solver -- *plain_solver says which
+int starts_refusal(rdis_hip_plan* L, const char* who, bool* plain_solver) {
     rdis_hip_problem* p = L->prob;
     rdis_hip_ctx* c = p->ctx;
     const std::string w(who);
@@ -2876,7 +2884,7 @@ int starts_refusal(rdis_hip_plan* L, const char* who) {
     if (L->trace_records > 0) return fail(c, RDIS_HIP_EINVAL, w + ": trace_records must be 0 (a trace belongs to one solve)");
     if (L->dump_iters > 0) return fail(c, RDIS_HIP_EINVAL, w + ": dump_iters must be 0 (a vector dump belongs to one solve)");
     if (L->partition_dirty || (!L->coop.empty() && L->coop_state_gen != p->coop_state_gen)) { int rc = prepare_partition(L); if (rc) return rc; }
-    // every component on the LDS-resident solver; an empty one (no factor: no table, nothing to solve) counts as such
+    // an empty component (no factor: no table, nothing to solve) runs on either solver
     int64_t tiny = 0, ptm = 0, plain = 0;
     const size_t r_lds = L->h_rest.size() - (size_t)L->rest_lds, r_ptm = r_lds - (size_t)L->rest_ptm;
     for (size_t r = 0; r < r_lds; ++r) {
@@ -2890,10 +2898,17 @@ int starts_refusal(rdis_hip_plan* L, const char* who) {
     note((int64_t)L->stream.size(), "grid solver");
     note(tiny, "tiny-component solver");
     note(ptm, "point-major streaming solver");
-    note(plain, "plain batch solver");
-    if (!others.empty())
+    const bool plain_ok = plain > 0 && p->kind == KIND_NLP && others.empty();
+    if (!plain_ok) note(plain, "plain batch solver");
+    if (!others.empty()) {
+        // (a bundle-adjustment component there reads its cameras' rotation records, ProblemView::xrot: they would need replicas too)
+        const char* ba_plain = plain > 0 && p->kind == KIND_BA ? " (bundle-adjustment components on the plain batch solver have no multi-start entry, alone or "
+                                                                 "beside LDS-resident ones: their rotation records would need replicas too)" : "";
         return fail(c, RDIS_HIP_EINVAL, w + ": every component of the plan must run on the LDS-resident solver (bundle adjustment, variables fitting a "
-                                        "compute unit's LDS); this plan sends" + others);
+                                        "compute unit's LDS) or, all of them, on the plain batch solver of a nonlinear-product problem; this plan sends" +
+                                        others + ba_plain);
+    }
+    *plain_solver = plain_ok;
     return 0;
 }
 }  // namespace
@@ -2909,15 +2924,21 @@ extern "C" int rdis_hip_plan_solve_starts(rdis_hip_plan* L, int64_t nstarts, con
     if (nstarts >= (1ll << 31) || (double)nstarts * (double)std::max<int64_t>(std::max(L->nfree, L->ncomp), 1) >= 9.0e15)
         return fail(c, RDIS_HIP_ERANGE, "plan_solve_starts: too many starts");
     if (int rc = refuse_late_exponential(L, "plan_solve_starts")) return rc;
-    if (int rc = starts_refusal(L, "plan_solve_starts")) return rc;
+    bool plain = false;
+    if (int rc = starts_refusal(L, "plan_solve_starts", &plain)) return rc;
     if (L->ncomp == 0) { L->ms_n = nstarts; L->ms_per_launch = nstarts; L->ms_launches = 0; L->last_launches = 0; L->timed = false; return 0; }
 
-    // replicas of the per-solve workspace (ws, gfac) a launch may hold within the budget: at least one
-    const size_t rep_doubles = 5 * (size_t)L->nfree + (size_t)L->ngfac, rep_bytes = rep_doubles * sizeof(double);
+    // replicas of the per-solve workspace (ws, gfac; the plain solver's x and dir too) a launch may hold within the budget: at least one
+    const size_t work_doubles = 5 * (size_t)L->nfree + (size_t)L->ngfac + (plain ? (size_t)p->N : 0), dir_doubles = plain ? (size_t)p->N : 0;
+    const size_t rep_bytes = (work_doubles + dir_doubles) * sizeof(double);
     int64_t R = rep_bytes ? std::max<int64_t>(1, L->starts_workspace_bytes / (int64_t)rep_bytes) : nstarts;
     R = std::min(std::min(R, nstarts), STARTS_MAX_PER_LAUNCH);
     int rc = 0;
-    if (L->ms_work.bytes < (size_t)R * rep_bytes) rc = plan_alloc(L, L->ms_work, (size_t)R * rep_bytes);
+    if (L->ms_work.bytes < (size_t)R * work_doubles * sizeof(double)) rc = plan_alloc(L, L->ms_work, (size_t)R * work_doubles * sizeof(double));
+    if (!rc && plain && L->ms_dir.bytes < (size_t)R * dir_doubles * sizeof(double)) {
+        rc = plan_alloc(L, L->ms_dir, (size_t)R * dir_doubles * sizeof(double));
+        if (!rc) HIPCHK(c, hipMemsetAsync(L->ms_dir.p, 0, L->ms_dir.bytes, c->stream));   // (the kernel leaves what it wrote zero again)
+    }
     const size_t in_bytes = (size_t)nstarts * (size_t)L->nfree * sizeof(double);
     if (!rc && L->ms_in.bytes < in_bytes) rc = plan_alloc(L, L->ms_in, in_bytes);
     if (!rc && L->ms_out.bytes < L->ms_out_bytes(nstarts)) rc = plan_alloc(L, L->ms_out, L->ms_out_bytes(nstarts));
@@ -2940,18 +2961,25 @@ extern "C" int rdis_hip_plan_solve_starts(rdis_hip_plan* L, int64_t nstarts, con
     }
 
     const ProblemView P = p->view();
-    PlanView V = L->view();   // (order: the whole batch list -- empty components, then the LDS-resident ones, heaviest first)
+    PlanView V = L->view();   // (order: the whole batch list -- empty components and those of the plan's one solver, heaviest first)
     StartsView S = L->starts_view(nstarts);
     S.gfac = S.ws + (size_t)R * 5 * (size_t)L->nfree;
-    const int threads = L->rest_lds > 0 ? lds_launch_threads(L) : 64;
+    const int threads = plain ? wg_launch_threads(L) : L->rest_lds > 0 ? lds_launch_threads(L) : 64;
     const size_t dyn = L->lds_dyn_bytes(c);
+    if (plain) {   // every replica's x: the problem's, for the constants (solver_wg_starts.hpp; once per call)
+        S.x = S.gfac + (size_t)R * (size_t)L->ngfac;
+        S.dir = L->ms_dir.as<double>();
+        HIPCHK(c, starts_fill_x_launch(c->stream, P, S, R));
+    }
     L->last_launches = 0;
     L->timed = false;
     HIPCHK(c, hipEventRecord(p->ev0, c->stream));
     for (int64_t first = 0; first < nstarts; first += R) {   // (launches on one stream: the next takes the replicas when this one is done)
         S.first = first;
-        HIPCHK(c, starts_launch(L->lds_rot_mode, threads, (int)L->h_rest.size(), (int)std::min(R, nstarts - first), dyn, c->stream, P, V, S,
-                                maxiters, ftol, L->lds_ns_cap, L->lds_ncb_cap, L->lds_chunk_cap));
+        const int ns = (int)std::min(R, nstarts - first);
+        if (plain) HIPCHK(c, starts_launch_wg(threads, (int)L->h_rest.size(), ns, c->stream, P, V, S, maxiters, ftol));
+        else HIPCHK(c, starts_launch(L->lds_rot_mode, threads, (int)L->h_rest.size(), ns, dyn, c->stream, P, V, S,
+                                     maxiters, ftol, L->lds_ns_cap, L->lds_ncb_cap, L->lds_chunk_cap));
         ++L->last_launches;
     }
     HIPCHK(c, hipEventRecord(p->ev1, c->stream));

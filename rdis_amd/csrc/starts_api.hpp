@@ -1,5 +1,5 @@
-// starts_api.hpp -- what rdis_hip.hip sees of the multi-start entry of the LDS-resident solver (solver_lds_starts.hpp), whose
-// kernels are a translation unit of their own (starts_kernels.hip).
+// starts_api.hpp -- what rdis_hip.hip sees of the multi-start entries of the LDS-resident solver (solver_lds_starts.hpp) and of
+// the plain one-workgroup solver (solver_wg_starts.hpp), whose kernels are a translation unit of their own (starts_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
@@ -20,7 +20,9 @@ struct StartsView {
     long long* ngeval;
     double* ws;             // [replicas][5 nfree]   PlanView::ws of a replica
     double* gfac;           // [replicas][ngfac]     PlanView::gfac of a replica
-    long long nfree, ngfac; // row lengths
+    double* x;              // [replicas][N]         plain solver only: ProblemView::x of a replica (the trial point lives there) ...
+    double* dir;            // [replicas][N]         ... and PlanView::dir of a replica; zero between launches
+    long long nfree, ngfac, N; // row lengths
     long long first;        // the launch's first start
 };
 
@@ -31,6 +33,11 @@ namespace rdis_hip {
 // cgd_lds_starts_kernel<threads, rot>: grid (ncomp_listed, nstarts_of_launch); V.order lists the components
 hipError_t starts_launch(int rot, int threads, int ncomp_listed, int nstarts_of_launch, size_t dyn, hipStream_t stream, const ProblemView& P,
                          const PlanView& V, const StartsView& S, int maxiters, double ftol, int ns_cap, int ncb_cap, int chunk_cap);
+// cgd_wg_starts_kernel<KIND_NLP, threads>: the plain solver's, same grid; S.x and S.dir hold the launch's replicas
+hipError_t starts_launch_wg(int threads, int ncomp_listed, int nstarts_of_launch, hipStream_t stream, const ProblemView& P, const PlanView& V,
+                            const StartsView& S, int maxiters, double ftol);
+// starts_fill_x_kernel: every one of the `replicas` rows of S.x = P.x
+hipError_t starts_fill_x_launch(hipStream_t stream, const ProblemView& P, const StartsView& S, long long replicas);
 // select_best_start_kernel over the S.fret of all nstarts starts: best[ncomp], the plan's ordinary outputs, P.x
 hipError_t starts_select_launch(hipStream_t stream, const ProblemView& P, const PlanView& V, const StartsView& S, long long nstarts, int* best);
 

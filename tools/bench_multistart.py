@@ -2,11 +2,13 @@
 """Multi-start solves measured: rdis_hip_plan_solve_starts against the same starts solved one by one.
 
   python tools/bench_multistart.py            # both steps, one JSON line
-  python tools/bench_multistart.py --step config3|config5s   # one step, in this process
+  python tools/bench_multistart.py --step config3|config5s|config2   # one step, in this process
 
 config3   BASELINE config 3 (ladybug 5 cameras / 30 points, one component): 320 one-ulp starts -- those of the end-value fixture,
           tests/golden/end_values.json -- in one call, and the same 320 by set_start / solve / fetch on the same plan.
 config5s  BASELINE config 5-S (1000 components of 3 cameras x 40 points) x 8 starts, likewise.
+config2   BASELINE config 2 (the 121-variable sinusoid, one component on the plain solver: one workgroup of 512 lanes a solve) from
+          1024 starts drawn uniformly in the domains (seed 2), likewise.
 Every step runs in a child process under a time limit of its own; a step that fails ends the run.  Wall times are the median of
 `--repeats` calls after one warm-up call; kernel_ms is rdis_hip_plan_last_kernel_ms of the last call."""
 import argparse
@@ -21,7 +23,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-STEP_LIMIT_S = {"config3": 240, "config5s": 240}
+STEP_LIMIT_S = {"config3": 240, "config5s": 240, "config2": 240}
+STEPS = ("config3", "config5s", "config2")
 
 
 def ulp_perturbed(x0, rng):
@@ -67,6 +70,7 @@ def measure(pp, starts, repeats):
     same = bool(fret.tobytes() == ms.fret.tobytes() and x.tobytes() == ms.x.tobytes())
     wall, seq = float(np.median(tt)), float(np.median(ts))
     return {"starts": ns, "components": plan.ncomp, "components_lds": plan.info("components_lds"),
+            "components_plain": plan.info("components_plain"),
             "starts_per_launch": plan.info("starts_per_launch"), "launches": launches,
             "wall_ms": 1e3 * wall, "sequential_wall_ms": 1e3 * seq, "speedup": seq / wall,
             "last_kernel_ms": kernel_ms, "one_solve_kernel_ms": single_ms, "kernel_in_single_solves": kernel_ms / single_ms,
@@ -82,6 +86,9 @@ def step(name, repeats):
             seed = json.load(fh)["seed"]
         pp = P.load_bal(ncams=5, npts=30).single_component()
         starts = np.stack([ulp_perturbed(pp.x0, np.random.default_rng([seed, 100000 + k])) for k in range(320)])
+    elif name == "config2":
+        pp = P.make_high_dim_sinusoid().single_component()
+        starts = np.random.default_rng(2).uniform(pp.lo, pp.hi, size=(1024, pp.nvars))
     else:
         pp = P.make_synthetic_ba(1000, 3, 40)
         rng = np.random.default_rng(17)
@@ -102,7 +109,7 @@ def main():
         out["commit"] = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
     except OSError:
         out["commit"] = None
-    for name in ("config3", "config5s"):
+    for name in STEPS:
         try:
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", name, "--repeats", str(a.repeats)],
                                capture_output=True, text=True, timeout=STEP_LIMIT_S[name])
@@ -114,7 +121,7 @@ def main():
             break   # (nothing more is started on a device that a step has just failed on)
         out.update(json.loads(p.stdout.strip().splitlines()[-1]))
     print(json.dumps(out))
-    return 0 if all("error" not in out.get(k, {"error": 1}) for k in ("config3", "config5s")) else 1
+    return 0 if all("error" not in out.get(k, {"error": 1}) for k in STEPS) else 1
 
 
 if __name__ == "__main__":
