@@ -97,7 +97,7 @@ def factors_host():
 
 
 def ptm_point_order(cam_vid0, pt_vid0, spread: int = 16, wide: bool = False, local_cus: int = 0):
-    """the point blocks of one component in the point-major streaming solver's order (rdis_hip.hip: prepare_partition), from the
+    """the point blocks of one component in the point-major streaming solver's order (plan_tables.hpp: ptm_point_order), from the
     component's listed factors' camera / point blocks: by number of listed factors descending, among equals by their cameras (the
     cameras' ranks, in listed order) lexicographically, ties by id; the whole wave-chunks of 64 blocks whose first blocks have
     equally many factors are then dealt out over `spread` equal runs of their sorted order (ptm_api.hpp: PTM_SPREAD) -- round robin,
@@ -389,7 +389,7 @@ class OracleProblem:
         return o
 
     def set_cooperative_topology(self, free_vid=None, fac=None, lanes_per_workgroup: int = 128) -> None:
-        """wave-owned variables as rdis_hip.hip's prepare_partition picks them: fed by more than 48 listed partials (bundle
+        """wave-owned variables as plan_tables.hpp's coop_owner_tables picks them: fed by more than 48 listed partials (bundle
         adjustment: one per listed factor that reads the variable), the longest runs first, ties in list order -- as many as the
         component's cooperative group has waves: workgroups = max(ceil(max(factors, variables) / lanes), and for groups of fewer
         than 16 workgroups min(ceil(long runs / waves per workgroup), 2 x that + 2)), lanes = 128 factor lanes per workgroup in

@@ -570,8 +570,8 @@ void ro_set_sum_order(ro_problem *p, int which)
  *            rounded), the terms then added like the values;
  *   gg, dgg  lane i carries the terms of free variable i unless a wave owns it; wave w's first lane adds the terms of the
  *            variable it owns; the lanes' terms then added like the values (solver_coop.hpp: cg_reduce);
- *   gradient a variable fed by more than 48 partials is owned by a wave (the longest runs first, rdis_hip.hip:
- *            prepare_partition): lane l adds the partials l, l + 64, ... of its run in order from 0.0, then a wave sum; every
+ *   gradient a variable fed by more than 48 partials is owned by a wave (the longest runs first, plan_tables.hpp:
+ *            coop_owner_tables): lane l adds the partials l, l + 64, ... of its run in order from 0.0, then a wave sum; every
  *            other variable adds its partials in factor-list order like the reference.
  * ------------------------------------------------------------------------------------------------------------------- */
 static double tree64(const double *v)
@@ -658,11 +658,11 @@ void ro_set_lds_topology(ro_problem *p, int nt, int64_t nslots, const int64_t *s
  * RO_SUM_TOPOLOGY_PTM: the sums of the device's point-major streaming solver (rdis_amd/csrc/solver_ptm.hpp, one workgroup of nt
  * lanes per component -- BASELINE config 5-L, the strong-scaling workload's one-device case), restated entry for entry.
  *   layout   the component's point blocks in the plan's order (by number of listed factors descending, then by their cameras;
- *            whole wave-chunks of 64 dealt out over sixteen runs: rdis_hip.hip prepare_partition -- the caller passes the order);
+ *            whole wave-chunks of 64 dealt out over sixteen runs: plan_tables.hpp ptm_point_order -- the caller passes the order);
  *            chunk ch holds blocks 64 ch .. 64 ch + 63, lane l its l-th; a chunk has as many SLOTS as its first block has listed
  *            factors, slot t of lane l is the t-th listed factor of the lane's block;
  *   trials   the chunks' slots in blocks of `blk`, the blocks in chunk order dealt to the waves in equal contiguous shares (rows:
- *            rdis_hip.hip ptm_build_segments); a lane adds its factors' terms row by row, slot by slot, from 0.0; a wave's 64 lanes
+ *            plan_tables.hpp ptm_segment_rows); a lane adds its factors' terms row by row, slot by slot, from 0.0; a wave's 64 lanes
  *            as a balanced tree, the waves' sums as a balanced tree over 16 entries (zero-padded; 4 up to four waves).  Values and
  *            slopes in matrix form against per-camera records (factors.hpp: ba_camera_trial, ba_trial_value, ba_trial_slope);
  *   rollback the value at clamp(x_start): wave w takes the chunks w, w + waves, ... whole (eval_start);

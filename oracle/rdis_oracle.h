@@ -111,7 +111,7 @@ void ro_set_sum_order(ro_problem *p, int which);
  * solver_pipe.hpp: waves of 64 as balanced trees, the waves' sums as entries taken l, l + 64, ... by lane l, a wave sum over the
  * lanes; the slope factor by factor; gg / dgg by owner lane; a wave-owned variable's partials strided over a wave), restated entry
  * for entry in rdis_oracle.c.  wave_vid: the variables a wave owns, in wave order -- those fed by more than 48 listed partials,
- * the longest runs first, ties in list order (rdis_hip.hip: prepare_partition).  With it, RO_ARITH_* and
+ * the longest runs first, ties in list order (plan_tables.hpp: coop_owner_tables).  With it, RO_ARITH_* and
  * RO_BA_DERIV_ADJOINT_DEVICE on, and the stale cache off, ro_cgd_optimize returns what the device's DEFAULT cooperative path
  * returns, bit for bit (tests/test_gpu_parity.py).  Bundle adjustment only. */
 #define RO_SUM_TOPOLOGY_REFERENCE 0

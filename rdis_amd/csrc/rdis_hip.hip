@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "host_blocks.hpp"
+#include "plan_tables.hpp"
 #include "components.hpp"
 #include "lm_solver.hpp"
 #include "eval_kernels.hpp"
@@ -326,9 +327,7 @@ struct rdis_hip_plan {
     int ptm_local_cameras = -1;       // option "ptm_local_cameras": -1 = where the cameras do not fit, 0 = never, 1 = for every wide component (tests)
     bool ptm_local = false, ptm_local_off = false;   // the plan has such a component; it was tried and did not fit (then never again)
     int ptm_local_K = 0, ptm_local_comp = -1;
-    ivec h_lc, h_cr_ptr, h_cr, h_wg_chunk0;          // PtmGroupArgs' tables; the workgroups' chunk ranges
-    std::vector<long long> h_lc_off;
-    std::vector<short> h_pm_lcam;                    // entry of the point-major order -> its camera's number in the owning workgroup
+    PtmLocalTables loc;                              // its host tables (plan_tables.hpp)
     DevBuf lc_dev, lc_off_dev, cr_ptr_dev, cr_dev, ptm_tot;
     DevBuf seq_val, seq_ab;           // the parity option's buffers (PlanView::seq_val, seq_ab), allocated at the first solve that needs them
     int lds_ns_cap = 0, lds_ncb_cap = 0, lds_chunk_cap = 0, lds_rot_mode = ROT_PER_FACTOR;
@@ -1643,10 +1642,49 @@ extern "C" int rdis_hip_plan_set_option(rdis_hip_plan* L, const char* name, int6
 }
 
 namespace {
-// decide which components the cooperative solver takes and build what it needs
-int prepare_partition(rdis_hip_plan* L) {
-    rdis_hip_ctx* c = L->prob->ctx;
-    rdis_hip_problem* p = L->prob;
+// ---- prepare_partition: which solver takes each component, and what that solver needs.  The decisions, the allocation and the
+// uploads are here, in steps; every index table is built by plan_tables.hpp's host functions (tested without a device).
+
+// what flows between the steps
+struct Partition {
+    bool coop_on = false, any_big = false;
+    int cap = 0, scap = 0;               // workgroups a cooperative launch / the grid solver can have resident
+    int64_t group_min = INT64_MAX;       // group mode: every component of at least this many factors gets a cooperative group
+    int64_t max_n = 0;                   // running total of the cooperative components' variables
+    std::vector<int64_t> nlong_of;       // per component: its variables on long lists (counted once: the layouts are compared)
+    cvec wide_comp;                      // per component: it joined the batch list for a wide point-major group
+    ivec cams, pts, deg, lane_var, wave_var, sl_own;   // scratch, reused from component to component
+    // the slot tables, per component
+    cvec kind_of;                        // 1 = LDS-resident, 2 = point-major streaming
+    ivec ls_ncb, ls_gcount, pm_pt0, ls_fidx;
+    ivec ls_pidx;                        // (host only) a listed factor's point block within its component: all 31 bits of it
+    std::vector<ivec> vid_of, free_of, gp_of, pptr_of;
+    std::vector<ivec> local_cams;        // per workgroup of the local group: its cameras (component numbers), ascending
+    bool local_failed = false;
+};
+
+BlockArrays block_arrays(rdis_hip_problem* p) {
+    if (p->h_blk_stamp.empty()) { p->h_blk_stamp.assign((size_t)p->N, 0); p->h_blk_idx.assign((size_t)p->N, 0); }
+    return BlockArrays{p->h_cam.data(), p->h_pt.data(), p->h_block_of.data(), p->h_ptblock_of.data(),
+                       p->h_blk_stamp.data(), p->h_blk_idx.data(), p->h_owner_stamp.data(), p->h_local.data()};
+}
+CompLists comp_lists(const rdis_hip_plan* L, int cc) {
+    const int f0 = L->h_free_ptr[(size_t)cc], c0 = L->h_fac_ptr[(size_t)cc];
+    return CompLists{L->h_fac_id.data() + c0, L->h_fac_ptr[(size_t)cc + 1] - c0, L->h_free_vid.data() + f0, L->h_free_ptr[(size_t)cc + 1] - f0,
+                     L->h_v2s_ptr.data() + f0};
+}
+// no camera variable free among the components [r0, r1) of the batch list
+bool cameras_fixed(const rdis_hip_plan* L, size_t r0, size_t r1) {
+    for (size_t r = r0; r < r1; ++r) {
+        const int cc = L->h_rest[r];
+        for (int k = L->h_free_ptr[(size_t)cc]; k < L->h_free_ptr[(size_t)cc + 1]; ++k)
+            if (L->prob->h_block_of[(size_t)L->h_free_vid[(size_t)k]] >= 0) return false;
+    }
+    return true;
+}
+
+// step 1: drop the previous partition
+void drop_partition(rdis_hip_plan* L) {
     // (the device memory of the items about to be dropped leaves the plan's account with them)
     auto drop = [&](DevBuf& b) { if (!L->transient && b.owned) L->dev_bytes -= std::min(L->dev_bytes, b.bytes); b.release(); };
     for (CoopLaunch& cl : L->coop_launches) { drop(cl.groups); drop(cl.wg_group); }
@@ -1658,130 +1696,142 @@ int prepare_partition(rdis_hip_plan* L) {
     L->h_coop_wg.clear();
     L->stream.clear();
     L->h_rest.clear();
-    int cap = 0, scap = 0;
+}
+
+// workgroups of a component's cooperative group with `lanes` factor lanes each: a lane per factor / variable, a wave per long gradient run
+int64_t groups_of(const rdis_hip_plan* L, Partition& S, int cc, int lanes) {
+    const int wpw = lanes / 64;
+    const int64_t m = L->h_fac_ptr[(size_t)cc + 1] - L->h_fac_ptr[(size_t)cc];
+    const int64_t n = L->h_free_ptr[(size_t)cc + 1] - L->h_free_ptr[(size_t)cc];
+    const int f0 = L->h_free_ptr[(size_t)cc];
+    int64_t& nlong = S.nlong_of[(size_t)cc];
+    if (nlong < 0) {
+        nlong = 0;
+        for (int64_t i = 0; i < n; ++i)
+            if (L->h_v2s_ptr[(size_t)(f0 + i) + 1] - L->h_v2s_ptr[(size_t)(f0 + i)] > COOP_LONG_LIST) ++nlong;
+    }
+    const int64_t need = (std::max(m, n) + lanes - 1) / lanes;
+    // (small groups only: a large one has its waves anyway, and more workgroups lengthen every sweep)
+    const int64_t for_long = need < 16 ? std::min<int64_t>((nlong + wpw - 1) / wpw, 2 * need + 2) : 0;
+    return std::max<int64_t>(1, std::max(need, for_long));
+}
+// workgroups a cooperative launch of the plain or the pipelined layout can have resident
+int coop_cap(rdis_hip_plan* L, bool pipe) {
+    rdis_hip_ctx* c = L->prob->ctx;
+    // (the occupancy queries behind these are not free: asked once per context -- a device -- and layout;
+    // calls on a context are serialised, include/rdis_hip.h)
+    const int ti = L->coop_threads == 128 ? 0 : L->coop_threads == 256 ? 1 : 2;
+    const bool rr = L->coop_reference_rounding();
+    int& kc = rr ? c->cap_coop_rr[ti] : c->cap_coop[ti];
+    int& kp = rr ? c->cap_pipe_rr : c->cap_pipe;
+    if (pipe && kp < 0) kp = solver_set(rr).pipe_max_workgroups(c->num_cus);
+    if (!pipe && kc < 0) kc = solver_set(rr).coop_max_workgroups(L->coop_threads, c->num_cus);
+    int k = pipe ? kp : kc;
+    if (L->coop_workgroups > 0) k = std::min(k, L->coop_workgroups);
+    return k;
+}
+
+// step 2: the cooperative layout and its cap
+void choose_coop_layout(rdis_hip_plan* L, Partition& S) {
+    rdis_hip_problem* p = L->prob;
+    S.nlong_of.assign((size_t)L->ncomp, -1);
     // The grid solvers are for a few large components that would leave the device idle as single
     // workgroups, one launch each.  When there are more large components than that, the batch
     // kernel fills the device by itself (one workgroup per component) and is the better fit.
-    std::vector<int64_t> nlong_of((size_t)L->ncomp, -1);   // (counted once per component: the layouts are compared below)
-    auto groups_of = [&](int cc) {   // workgroups of a component's cooperative group: a lane per factor / variable, a wave per long gradient run
-        const int wpw = L->coop_lanes() / 64;
-        const int64_t m = L->h_fac_ptr[(size_t)cc + 1] - L->h_fac_ptr[(size_t)cc];
-        const int64_t n = L->h_free_ptr[(size_t)cc + 1] - L->h_free_ptr[(size_t)cc];
-        const int f0 = L->h_free_ptr[(size_t)cc];
-        int64_t& nlong = nlong_of[(size_t)cc];
-        if (nlong < 0) {
-            nlong = 0;
-            for (int64_t i = 0; i < n; ++i)
-                if (L->h_v2s_ptr[(size_t)(f0 + i) + 1] - L->h_v2s_ptr[(size_t)(f0 + i)] > COOP_LONG_LIST) ++nlong;
-        }
-        const int64_t need = (std::max(m, n) + L->coop_lanes() - 1) / L->coop_lanes();
-        // (small groups only: a large one has its waves anyway, and more workgroups lengthen every sweep)
-        const int64_t for_long = need < 16 ? std::min<int64_t>((nlong + wpw - 1) / wpw, 2 * need + 2) : 0;
-        return std::max<int64_t>(1, std::max(need, for_long));
-    };
     int64_t nbig = 0;
     for (int64_t cc = 0; cc < L->ncomp; ++cc)
         if (L->h_fac_ptr[(size_t)cc + 1] - L->h_fac_ptr[(size_t)cc] >= L->coop_min_factors) ++nbig;
-    bool any_big = L->coop_min_factors > 0 && L->coop_max_components > 0 && L->nfac >= L->coop_min_factors &&
-                   nbig <= L->coop_max_components;
-    const bool coop_on = L->coop_min_factors > 0 && L->coop_max_components > 0 && p->kind == KIND_BA && !L->force_stream;
-    auto cap_of = [&]() {
-        // (the occupancy queries behind these are not free: asked once per context -- a device -- and layout;
-        // calls on a context are serialised, include/rdis_hip.h)
-        const int ti = L->coop_threads == 128 ? 0 : L->coop_threads == 256 ? 1 : 2;
-        const bool rr = L->coop_reference_rounding();
-        int& kc = rr ? c->cap_coop_rr[ti] : c->cap_coop[ti];
-        int& kp = rr ? c->cap_pipe_rr : c->cap_pipe;
-        if (L->pipelined() && kp < 0) kp = solver_set(rr).pipe_max_workgroups(c->num_cus);
-        if (!L->pipelined() && kc < 0) kc = solver_set(rr).coop_max_workgroups(L->coop_threads, c->num_cus);
-        int k = L->pipelined() ? kp : kc;
-        if (L->coop_workgroups > 0) k = std::min(k, L->coop_workgroups);
-        return k;
-    };
+    S.any_big = L->coop_min_factors > 0 && L->coop_max_components > 0 && L->nfac >= L->coop_min_factors && nbig <= L->coop_max_components;
+    S.coop_on = L->coop_min_factors > 0 && L->coop_max_components > 0 && p->kind == KIND_BA && !L->force_stream;
     // The pipelined layout (solver_pipe.hpp) has half the factor lanes per workgroup: it is used when
     // everything that gets a cooperative group with the plain layout also gets one with it.
-    L->use_pipe = false;
+    bool pipe = false;
     // (factor_rounding = 1, the parity option: the reference's slope -- a gradient pass of the whole group per trial and one
     // sequential sum -- exists in the plain cooperative layout only, solver_coop.hpp)
-    if (coop_on && L->coop_pipeline != 0 && L->factor_rounding != 1 && L->coop_threads == PIPE_THREADS) {
-        auto census = [&](int64_t& group_total, int64_t& group_count, int64_t& big_unfit) {
-            const int k = cap_of();
-            group_total = group_count = big_unfit = 0;
+    if (S.coop_on && L->coop_pipeline != 0 && L->factor_rounding != 1 && L->coop_threads == PIPE_THREADS) {
+        struct Census { int64_t group_total = 0, group_count = 0, big_unfit = 0; bool groups_fit = false; };
+        auto census = [&](bool piped) {
+            const int k = coop_cap(L, piped), lanes = piped ? PIPE_LANES : L->coop_threads;
+            Census r;
             for (int cc : L->h_order) {
                 const int64_t m = L->h_fac_ptr[(size_t)cc + 1] - L->h_fac_ptr[(size_t)cc];
-                if (L->coop_group_min_factors > 0 && m >= L->coop_group_min_factors) { group_total += groups_of(cc); ++group_count; }
-                if (m >= L->coop_min_factors && groups_of(cc) > k) ++big_unfit;
+                if (L->coop_group_min_factors > 0 && m >= L->coop_group_min_factors) { r.group_total += groups_of(L, S, cc, lanes); ++r.group_count; }
+                if (m >= L->coop_min_factors && groups_of(L, S, cc, lanes) > k) ++r.big_unfit;
             }
-            return k;
+            r.groups_fit = r.group_count > 0 && r.group_total <= k && r.group_count <= COOP_MAX_GROUPS;
+            return r;
         };
-        int64_t gt0, gc0, bu0, gt1, gc1, bu1;
-        const int k0 = census(gt0, gc0, bu0);
-        L->use_pipe = true;
-        const int k1 = census(gt1, gc1, bu1);
-        const bool group0 = gc0 > 0 && gt0 <= k0 && gc0 <= COOP_MAX_GROUPS, group1 = gc1 > 0 && gt1 <= k1 && gc1 <= COOP_MAX_GROUPS;
-        if ((group0 && !group1) || bu1 > bu0) L->use_pipe = false;
+        const Census plain = census(false), piped = census(true);
+        pipe = !((plain.groups_fit && !piped.groups_fit) || piped.big_unfit > plain.big_unfit);
     }
-    if (coop_on) cap = cap_of();
+    L->use_pipe = pipe;
+    if (S.coop_on) S.cap = coop_cap(L, pipe);
+}
+
+// step 3: group mode, and the grid solver's cap
+void choose_group_mode(rdis_hip_plan* L, Partition& S) {
+    rdis_hip_ctx* c = L->prob->ctx;
     // Group mode: every component of some size gets a cooperative group when all the groups are
     // resident at once -- a device that the batch kernel would leave mostly idle (49 camera components
     // of ladybug: 6.6 ms as one workgroup each).  Otherwise only the few very large ones do.
-    int64_t group_min = INT64_MAX;
-    if (coop_on && cap > 0 && L->coop_group_min_factors > 0) {
+    if (S.coop_on && S.cap > 0 && L->coop_group_min_factors > 0) {
         int64_t total = 0, count = 0;
         for (int cc : L->h_order) {
             if (L->h_fac_ptr[(size_t)cc + 1] - L->h_fac_ptr[(size_t)cc] < L->coop_group_min_factors) break;   // heaviest first
-            total += groups_of(cc);
+            total += groups_of(L, S, cc, L->coop_lanes());
             ++count;
         }
-        if (count > 0 && total <= cap && count <= COOP_MAX_GROUPS) { group_min = L->coop_group_min_factors; any_big = true; }
+        if (count > 0 && total <= S.cap && count <= COOP_MAX_GROUPS) { S.group_min = L->coop_group_min_factors; S.any_big = true; }
     }
-    if (any_big) scap = stream_max_workgroups(p->kind, c->num_cus);
-    if (L->coop_workgroups > 0) scap = std::min(scap, L->coop_workgroups);
-    int64_t max_n = 0;
-    ivec blk_all;
+    if (S.any_big) S.scap = stream_max_workgroups(L->prob->kind, c->num_cus);
+    if (L->coop_workgroups > 0) S.scap = std::min(S.scap, L->coop_workgroups);
+}
+
+// a component too large for a cooperative group whose camera blocks fit a compute unit's LDS (or may be numbered per workgroup)
+bool wide_ptm_ok(rdis_hip_plan* L, Partition& S, int cc) {
+    rdis_hip_problem* p = L->prob;
+    if (p->kind != KIND_BA || L->ptm_stream == 0 || p->ncam_blocks <= 0 || (L->lds_resident == 0 && L->ptm_stream != 2)) return false;
+    if (L->factor_rounding == 1 || L->emulate_stale) return false;   // (instantiated for the cooperative and LDS-resident solvers only)
+    const BlockArrays B = block_arrays(p);
+    if (!block_census(B, comp_lists(L, cc), ++p->stamp, S.cams, nullptr)) return false;
+    const int ncb = (int)S.cams.size();
+    // (more cameras than fit: a wide group whose workgroups keep their own cameras only -- decided with the tables below)
+    return ncb <= PTM_MAX_CAMERAS && (ptm_bytes_for(ncb, PTM_WIDE_THREADS) <= p->ctx->lds_limit || (L->ptm_local_cameras != 0 && !L->ptm_local_off));
+}
+
+// step 4: every component to the cooperative solver (with its owner tables), the grid solver, or the batch list
+int assign_components(rdis_hip_plan* L, Partition& S) {
+    rdis_hip_problem* p = L->prob;
+    rdis_hip_ctx* c = p->ctx;
     L->ptm_wide_wanted = false;
-    cvec wide_comp((size_t)L->ncomp, 0);
-    auto wide_ptm_ok = [&](int cc) {
-        if (p->kind != KIND_BA || L->ptm_stream == 0 || p->ncam_blocks <= 0 || (L->lds_resident == 0 && L->ptm_stream != 2)) return false;
-        if (L->factor_rounding == 1 || L->emulate_stale) return false;   // (instantiated for the cooperative and LDS-resident solvers only)
-        const int c0 = L->h_fac_ptr[(size_t)cc], c1 = L->h_fac_ptr[(size_t)cc + 1];
-        if (p->h_blk_stamp.empty()) { p->h_blk_stamp.assign((size_t)p->N, 0); p->h_blk_idx.assign((size_t)p->N, 0); }
-        const int stamp = ++p->stamp;
-        int ncb = 0;
-        for (int j = c0; j < c1; ++j) {
-            const int b = p->h_cam[(size_t)L->h_fac_id[(size_t)j]];
-            if (p->h_blk_stamp[(size_t)b] != stamp) { p->h_blk_stamp[(size_t)b] = stamp; ++ncb; }
-        }
-        for (int i = L->h_free_ptr[(size_t)cc]; i < L->h_free_ptr[(size_t)cc + 1]; ++i) {
-            const int v = L->h_free_vid[(size_t)i];
-            const int b = p->h_block_of[(size_t)v];
-            if (b >= 0) { if (p->h_blk_stamp[(size_t)b] != stamp) { p->h_blk_stamp[(size_t)b] = stamp; ++ncb; } }
-            else if (p->h_ptblock_of[(size_t)v] < 0) return false;
-        }
-        // (more cameras than fit: a wide group whose workgroups keep their own cameras only -- decided with the tables below)
-        return ncb <= PTM_MAX_CAMERAS && (ptm_bytes_for(ncb, PTM_WIDE_THREADS) <= c->lds_limit || (L->ptm_local_cameras != 0 && !L->ptm_local_off));
-    };
+    S.wide_comp.assign((size_t)L->ncomp, 0);
     // (one allocation: growing this by appending costs a transient call on ladybug 1.5 ms in page faults)
-    L->h_coop_ints.reserve((size_t)(any_big ? 12 * L->nfac + 4 * (L->nfac + L->nfree) + 4096 * (int64_t)std::min<int64_t>(L->ncomp, 64) : 0));
+    L->h_coop_ints.reserve((size_t)(S.any_big ? 12 * L->nfac + 4 * (L->nfac + L->nfree) + 4096 * (int64_t)std::min<int64_t>(L->ncomp, 64) : 0));
+    auto append = [&](const int* v, size_t count) {
+        const size_t off = L->h_coop_ints.size();
+        L->h_coop_ints.insert(L->h_coop_ints.end(), v, v + count);
+        L->h_coop_ints.resize((L->h_coop_ints.size() + 63) / 64 * 64, -1);
+        return off;
+    };
     for (int cc : L->h_order) {  // heaviest first
         const int64_t m = L->h_fac_ptr[(size_t)cc + 1] - L->h_fac_ptr[(size_t)cc];
         const int64_t n = L->h_free_ptr[(size_t)cc + 1] - L->h_free_ptr[(size_t)cc];
-        const int64_t need = groups_of(cc);
-        const bool grouped = m >= group_min;
-        const bool big = any_big && (grouped || (m >= L->coop_min_factors && (int)(L->coop.size() + L->stream.size()) < L->coop_max_components));
-        const bool take = big && cap > 0 && need <= cap && coop_on;
+        const int64_t need = groups_of(L, S, cc, L->coop_lanes());
+        const bool grouped = m >= S.group_min;
+        const bool big = S.any_big && (grouped || (m >= L->coop_min_factors && (int)(L->coop.size() + L->stream.size()) < L->coop_max_components));
+        const bool take = big && S.cap > 0 && need <= S.cap && S.coop_on;
         // A bundle-adjustment component too large for a cooperative group whose CAMERA blocks fit a compute unit's LDS goes to the
         // point-major streaming solver as a wide group -- a workgroup per compute unit on the one component (solver_ptm.hpp: a trial
         // streams 18 bytes a factor and 48 a point block, nothing is written; the grid solver below forms every trial point in x[]
-        // and gathers 24 doubles a factor through L2).  It joins the batch list; the tables below decide (cameras, LDS).
-        if (!take && big && wide_ptm_ok(cc)) { L->h_rest.push_back(cc); L->ptm_wide_wanted = true; wide_comp[(size_t)cc] = 1; continue; }
-        if (!take && big && scap > 0) {
+        // and gathers 24 doubles a factor through L2).  It joins the batch list; the slot tables decide (cameras, LDS).
+        if (!take && big && wide_ptm_ok(L, S, cc)) { L->h_rest.push_back(cc); L->ptm_wide_wanted = true; S.wide_comp[(size_t)cc] = 1; continue; }
+        if (!take && big && S.scap > 0) {
             // too large for the register-resident solver (or not bundle adjustment): the streaming
             // grid solver; about two factors per lane and trial point, at most what is resident
             L->stream.emplace_back();
             StreamItem& st = L->stream.back();
             st.comp = cc;
-            st.nwg = (int)std::max<int64_t>(1, std::min<int64_t>(scap, (std::max(m, n) + 2 * STREAM_THREADS - 1) / (2 * STREAM_THREADS)));
+            st.nwg = (int)std::max<int64_t>(1, std::min<int64_t>(S.scap, (std::max(m, n) + 2 * STREAM_THREADS - 1) / (2 * STREAM_THREADS)));
             const int f0s = L->h_free_ptr[(size_t)cc];
             ivec longv;
             for (int64_t i = 0; i < n; ++i)
@@ -1800,78 +1850,44 @@ int prepare_partition(rdis_hip_plan* L) {
         CoopItem& it = L->coop.back();
         it.comp = cc;
         it.nwg = (int)need;
-        it.xi_off = (size_t)max_n;   // (max_n: running total of the cooperative components' variables)
-        const int f0 = L->h_free_ptr[(size_t)cc], c0 = L->h_fac_ptr[(size_t)cc];
-        // local free index of each factor slot: plan_create's table, or (a plan that did not keep it) formed
-        // here from the per-problem marks, valid for one stamp
-        ivec sl_own;
+        it.xi_off = (size_t)S.max_n;
+        const CompLists C = comp_lists(L, cc);
+        // local free index of each factor slot: plan_create's table, or (a plan that did not keep it) formed here
         const int* sl = nullptr;
-        if (!L->h_slot_li.empty()) sl = L->h_slot_li.data() + 12 * (size_t)c0;
-        else {
-            for (int64_t i = 0; i < n; ++i) p->h_local[(size_t)L->h_free_vid[(size_t)(f0 + i)]] = (int)i;
-            const int stamp = ++p->stamp;
-            for (int64_t i = 0; i < n; ++i) p->h_owner_stamp[(size_t)L->h_free_vid[(size_t)(f0 + i)]] = stamp;
-            sl_own.resize((size_t)(12 * m));
-            for (int64_t j = 0; j < m; ++j) {
-                const int f = L->h_fac_id[(size_t)(c0 + j)];
-                for (int k = 0; k < 12; ++k) {
-                    const int v = p->var_of(f, k);
-                    sl_own[(size_t)(12 * j + k)] = p->h_owner_stamp[(size_t)v] == stamp ? p->h_local[(size_t)v] : -1;
-                }
-            }
-            sl = sl_own.data();
-        }
-        // owners of the CG recurrence: a lane per variable, a whole wave for variables fed by
-        // many partials (longest first), see solver_coop.hpp
-        const int lanes = it.nwg * L->coop_lanes(), waves = lanes / 64;
-        ivec lane_var((size_t)lanes, -1), wave_var((size_t)waves, -1), longv;
-        for (int64_t i = 0; i < n; ++i)
-            if (L->h_v2s_ptr[(size_t)(f0 + i) + 1] - L->h_v2s_ptr[(size_t)(f0 + i)] > COOP_LONG_LIST) longv.push_back((int)i);
-        std::stable_sort(longv.begin(), longv.end(), [&](int a, int b) {
-            return (L->h_v2s_ptr[(size_t)(f0 + a) + 1] - L->h_v2s_ptr[(size_t)(f0 + a)]) >
-                   (L->h_v2s_ptr[(size_t)(f0 + b) + 1] - L->h_v2s_ptr[(size_t)(f0 + b)]);
-        });
-        cvec wave_owned((size_t)n, 0);
-        for (size_t k = 0; k < longv.size() && (int)k < waves; ++k) { wave_var[k] = longv[k]; wave_owned[(size_t)longv[k]] = 1; }
-        for (int64_t i = 0; i < n; ++i) if (!wave_owned[(size_t)i]) lane_var[(size_t)i] = (int)i;
-        auto append = [&](const int* v, size_t count) {
-            const size_t off = L->h_coop_ints.size();
-            L->h_coop_ints.insert(L->h_coop_ints.end(), v, v + count);
-            L->h_coop_ints.resize((L->h_coop_ints.size() + 63) / 64 * 64, -1);
-            return off;
-        };
+        if (!L->h_slot_li.empty()) sl = L->h_slot_li.data() + 12 * (size_t)L->h_fac_ptr[(size_t)cc];
+        else { coop_slot_li(block_arrays(p), C, ++p->stamp, S.sl_own); sl = S.sl_own.data(); }
+        coop_owner_tables(C, it.nwg * L->coop_lanes(), COOP_LONG_LIST, S.lane_var, S.wave_var);
         it.slot_li = append(sl, (size_t)(12 * m));
-        it.lane_var = append(lane_var.data(), lane_var.size());
-        it.wave_var = append(wave_var.data(), wave_var.size());
-        max_n += n;
+        it.lane_var = append(S.lane_var.data(), S.lane_var.size());
+        it.wave_var = append(S.wave_var.data(), S.wave_var.size());
+        S.max_n += n;
     }
+    return 0;
+}
+
+// step 5: tiny components to the front of the batch list; how the list's factors get their rotations
+void order_rest(rdis_hip_plan* L) {
+    rdis_hip_problem* p = L->prob;
     // tiny bundle-adjustment components (at most QUAD_MAX_VARS free variables: a point against fixed
     // cameras) go first in the batch list: four lanes each (solver_quad.hpp) instead of a workgroup
-    {
-        auto tiny = [&](int cc) {
-            return p->kind == KIND_BA && L->quad_max_vars > 0 &&
-                   L->h_free_ptr[(size_t)cc + 1] - L->h_free_ptr[(size_t)cc] <= std::min(L->quad_max_vars, QUAD_MAX_VARS);
-        };
-        // ... when there are enough of them to fill the device: below that a wave's sixteen components
-        // finish at different times and the wave runs as long as its slowest (measured: ladybug's 7776
-        // points 2.8 ms with a workgroup each, 4.2 ms as quads; 31104 synthetic points 4.5 vs 2.3 ms)
-        int64_t ntiny = 0;
-        for (int cc : L->h_rest) ntiny += tiny(cc) ? 1 : 0;
-        L->rest_tiny = 0;
-        L->tiny_group = ntiny >= L->quad_min_components ? 4 : ntiny >= L->row_min_components ? 16 : 0;
-        if (L->tiny_group != 0) {
-            auto mid = std::stable_partition(L->h_rest.begin(), L->h_rest.end(), tiny);
-            L->rest_tiny = (int)(mid - L->h_rest.begin());
-        }
+    auto tiny = [&](int cc) {
+        return p->kind == KIND_BA && L->quad_max_vars > 0 &&
+               L->h_free_ptr[(size_t)cc + 1] - L->h_free_ptr[(size_t)cc] <= std::min(L->quad_max_vars, QUAD_MAX_VARS);
+    };
+    // ... when there are enough of them to fill the device: below that a wave's sixteen components
+    // finish at different times and the wave runs as long as its slowest (measured: ladybug's 7776
+    // points 2.8 ms with a workgroup each, 4.2 ms as quads; 31104 synthetic points 4.5 vs 2.3 ms)
+    int64_t ntiny = 0;
+    for (int cc : L->h_rest) ntiny += tiny(cc) ? 1 : 0;
+    L->rest_tiny = 0;
+    L->tiny_group = ntiny >= L->quad_min_components ? 4 : ntiny >= L->row_min_components ? 16 : 0;
+    if (L->tiny_group != 0) {
+        auto mid = std::stable_partition(L->h_rest.begin(), L->h_rest.end(), tiny);
+        L->rest_tiny = (int)(mid - L->h_rest.begin());
     }
     L->rest_rot_mode = ROT_PER_FACTOR;
     if (p->kind == KIND_BA && L->camera_records != 0 && p->ncam_blocks > 0 && !L->h_rest.empty()) {
-        bool camfix = true;
-        for (size_t i = 0; i < L->h_rest.size() && camfix; ++i) {
-            const int cc = L->h_rest[i];
-            for (int k = L->h_free_ptr[(size_t)cc]; k < L->h_free_ptr[(size_t)cc + 1] && camfix; ++k)
-                camfix = p->h_block_of[(size_t)L->h_free_vid[(size_t)k]] < 0;
-        }
+        const bool camfix = cameras_fixed(L, 0, L->h_rest.size());
         // Free cameras: rewriting their records at every trial point puts one lane's rotation latency in
         // front of the evaluation and takes the rotation out of every factor -- a gain only where a lane
         // has many factors per camera (64 components of 31843 factors: 74 against 79 ms; no difference
@@ -1880,12 +1896,76 @@ int prepare_partition(rdis_hip_plan* L) {
         for (int cc : L->h_rest) mf = std::max<int64_t>(mf, L->h_fac_ptr[(size_t)cc + 1] - L->h_fac_ptr[(size_t)cc]);
         L->rest_rot_mode = camfix ? ROT_CAMFIX : (L->camera_records == 2 || mf > 2048) ? ROT_RECORDS : ROT_PER_FACTOR;
     }
-    // Slot tables.  The LDS-resident solver (solver_lds.hpp) takes the bundle-adjustment components of the
-    // batch list whose variables -- free ones and the constants their factors read -- fit a compute unit's
-    // LDS as slots: camera blocks (9 slots each, ascending by id), then point blocks (3 each, ascending).
-    // Of the others, those whose CAMERA blocks fit go to the point-major streaming solver (solver_ptm.hpp:
-    // point blocks as records in HBM, ordered by their number of factors, descending).  Both move to the
-    // end of the list (streaming ones first); what fits neither stays with solver_wg.hpp.
+}
+
+// step 6, one component of the batch list: which of the two solvers below takes it, if any, and its tables
+void component_slot_tables(rdis_hip_plan* L, Partition& S, const BlockArrays& B, int cc, int ptm_max_threads) {
+    rdis_hip_problem* p = L->prob;
+    rdis_hip_ctx* c = p->ctx;
+    const CompLists C = comp_lists(L, cc);
+    if (C.m == 0) return;   // (an empty factor list needs no table: solver_wg.hpp returns 0 for it)
+    const int stamp = ++p->stamp;
+    bool free_cam = false;
+    if (!block_census(B, C, stamp, S.cams, &S.pts, &free_cam) || S.cams.size() > (size_t)PTM_MAX_CAMERAS) return;
+    const bool many_points = S.pts.size() >= (1u << 20);   // (beyond the LDS-resident solver's slot word; the streaming tables use ls_pidx)
+    const int ncb = (int)S.cams.size(), npb = (int)S.pts.size(), ns = 9 * ncb + 3 * npb, m = C.m, c0 = L->h_fac_ptr[(size_t)cc];
+    std::sort(S.cams.begin(), S.cams.end());
+    number_blocks(B, S.cams);
+    ivec& gp = S.gp_of[(size_t)cc];
+    gradient_pass_order(B, C, ncb, free_cam, gp);
+    const int nchunk = (int)gp.size() / 64;
+    // (the streaming solver is for what is too LARGE for the LDS: with lds_resident = 0 such components stay with
+    // solver_wg.hpp -- the comparison the bit-identity tests make; ptm_stream = 2 sends everything its tables fit)
+    const bool lds_size_ok = !many_points && lds_bytes_for(ns, ncb, nchunk) <= c->lds_limit;
+    const bool fits_lds = L->lds_resident != 0 && lds_size_ok && L->ptm_stream != 2;
+    const bool wide = S.wide_comp[(size_t)cc] != 0;
+    const bool want_local = wide && !L->ptm_local_off && L->ptm_local_cameras != 0 && !S.local_failed &&
+                            (L->ptm_local_cameras == 1 || ptm_bytes_for(ncb, PTM_WIDE_THREADS) > c->lds_limit);
+    const bool fits_ptm = !fits_lds && (L->ptm_stream == 2 || (L->ptm_stream == 1 && !lds_size_ok)) &&
+                          (want_local || ptm_bytes_for(ncb, ptm_max_threads) <= c->lds_limit);
+    if (want_local && L->ptm_local) { S.local_failed = true; gp.clear(); return; }   // (one such component a plan)
+    if (!fits_lds && !fits_ptm) { gp.clear(); return; }
+    if (fits_lds) std::sort(S.pts.begin(), S.pts.end());
+    else {
+        PtmLocalReport rep;
+        const bool fits = ptm_point_order(B, C, ncb, want_local ? PtmDeal::LOCAL : wide ? PtmDeal::WIDE : PtmDeal::SPREAD, c->num_cus, c->lds_limit,
+                                          S.pts, S.deg, L->loc.wg_chunk0, S.local_cams, rep);
+        if (rep.dealt && std::getenv("RDIS_HIP_LOCAL_STATS"))
+            std::fprintf(stderr, "local cameras: %d workgroups over %d chunks, %d cameras in the component, at most %zu in a workgroup (the LDS holds %zu)\n",
+                         rep.K, rep.chunks, ncb, rep.worst, rep.cam_cap);
+        if (!fits) { S.local_failed = true; gp.clear(); return; }
+        if (want_local) { L->ptm_local = true; L->ptm_local_K = rep.K; L->ptm_local_comp = cc; }
+    }
+    slot_table(B, C, stamp, S.cams, S.pts, !fits_lds, S.vid_of[(size_t)cc], S.free_of[(size_t)cc], S.ls_fidx.data() + c0, S.ls_pidx.data() + c0, S.pptr_of[(size_t)cc]);
+    S.ls_ncb[(size_t)cc] = ncb;
+    S.ls_gcount[(size_t)cc] = nchunk;
+    if (fits_lds) {
+        S.kind_of[(size_t)cc] = 1;
+        L->lds_ns_cap = std::max(L->lds_ns_cap, ns);
+        L->lds_ncb_cap = std::max(L->lds_ncb_cap, ncb);
+        L->lds_chunk_cap = std::max(L->lds_chunk_cap, nchunk);
+        L->lds_max_factors = std::max<int64_t>(L->lds_max_factors, m);
+    } else {
+        S.kind_of[(size_t)cc] = 2;
+        if (L->ptm_local && L->ptm_local_comp == cc) {   // (a workgroup's LDS holds its own cameras only)
+            for (const ivec& lc : S.local_cams) L->ptm_ncb_cap = std::max(L->ptm_ncb_cap, (int)lc.size());
+        } else {
+            L->ptm_ncb_cap = std::max(L->ptm_ncb_cap, ncb);
+        }
+    }
+}
+
+// step 6: Slot tables.  The LDS-resident solver (solver_lds.hpp) takes the bundle-adjustment components of the
+// batch list whose variables -- free ones and the constants their factors read -- fit a compute unit's
+// LDS as slots: camera blocks (9 slots each, ascending by id), then point blocks (3 each, ascending).
+// Of the others, those whose CAMERA blocks fit go to the point-major streaming solver (solver_ptm.hpp:
+// point blocks as records in HBM, ordered by their number of factors, descending).  Both move to the
+// end of the list (streaming ones first); what fits neither stays with solver_wg.hpp.
+// false: local camera numbering did not work out (a workgroup's cameras beyond the LDS, too few chunks, a second streaming
+// component in the plan).
+bool build_slot_tables(rdis_hip_plan* L, Partition& S) {
+    rdis_hip_problem* p = L->prob;
+    rdis_hip_ctx* c = p->ctx;
     L->rest_lds = L->rest_ptm = 0;
     L->h_lds_ints.clear();
     L->h_pm_jg.clear();
@@ -1893,351 +1973,78 @@ int prepare_partition(rdis_hip_plan* L) {
     L->rounds_threads = L->rounds_K = 0;
     L->lds_max_factors = 0;
     L->pm_blocks = L->pm_entries = 0;
-    if (p->kind == KIND_BA && (L->lds_resident != 0 || L->ptm_stream != 0) && p->ncam_blocks > 0 && (int)L->h_rest.size() > L->rest_tiny) {
-        if (p->h_blk_stamp.empty()) { p->h_blk_stamp.assign((size_t)p->N, 0); p->h_blk_idx.assign((size_t)p->N, 0); }
-        const size_t nc = (size_t)L->ncomp;
-        cvec kind_of(nc, 0);   // 1 = LDS-resident, 2 = point-major streaming
-        // (the staging area of its gradient grows with the workgroup; a plan with a component meant for a wide group keeps to that group's 512 lanes)
-        const int ptm_max_threads = L->ptm_threads ? L->ptm_threads : L->ptm_wide_wanted ? PTM_WIDE_THREADS : 768;
-        ivec ls_ncb(nc, 0), ls_gcount(nc, 0), pm_pt0(nc, 0), ls_fidx((size_t)L->nfac, 0);
-        ivec ls_pidx((size_t)L->nfac, 0);   // (host only) a listed factor's point block within its component: all 31 bits of it
-        std::vector<ivec> vid_of(nc), free_of(nc), gp_of(nc), pptr_of(nc);
-        ivec cams, pts, deg;
-        bool local_failed = false;
-        L->ptm_local = false; L->ptm_local_K = 0; L->ptm_local_comp = -1;
-        L->h_lc.clear(); L->h_lc_off.clear(); L->h_cr_ptr.clear(); L->h_cr.clear(); L->h_wg_chunk0.clear(); L->h_pm_lcam.clear();
-        std::vector<ivec> local_cams;   // per workgroup of the local group: its cameras (component numbers), ascending
-        for (size_t r = (size_t)L->rest_tiny; r < L->h_rest.size(); ++r) {
-            const int cc = L->h_rest[r];
-            const int f0 = L->h_free_ptr[(size_t)cc], f1 = L->h_free_ptr[(size_t)cc + 1];
-            const int c0 = L->h_fac_ptr[(size_t)cc], c1 = L->h_fac_ptr[(size_t)cc + 1];
-            if (c1 == c0) continue;   // (an empty factor list needs no table: solver_wg.hpp returns 0 for it)
-            const int stamp = ++p->stamp;
-            cams.clear(); pts.clear();
-            auto note = [&](int b, ivec& list) {
-                if (p->h_blk_stamp[(size_t)b] != stamp) { p->h_blk_stamp[(size_t)b] = stamp; list.push_back(b); }
-            };
-            bool ok = true, free_cam = false;
-            for (int j = c0; j < c1; ++j) { const int f = L->h_fac_id[(size_t)j]; note(p->h_cam[(size_t)f], cams); note(p->h_pt[(size_t)f], pts); }
-            for (int i = f0; i < f1 && ok; ++i) {
-                const int v = L->h_free_vid[(size_t)i];
-                if (p->h_block_of[(size_t)v] >= 0) { note(p->h_block_of[(size_t)v], cams); free_cam = true; }
-                else if (p->h_ptblock_of[(size_t)v] >= 0) note(p->h_ptblock_of[(size_t)v], pts);
-                else ok = false;   // a variable no factor of the problem reads: no block to put it in
-            }
-            if (!ok || cams.size() > (size_t)PTM_MAX_CAMERAS) continue;
-            const bool many_points = pts.size() >= (1u << 20);   // (beyond the LDS-resident solver's slot word; the streaming tables use ls_pidx)
-            const int ncb = (int)cams.size(), npb = (int)pts.size(), ns = 9 * ncb + 3 * npb, m = c1 - c0;
-            std::sort(cams.begin(), cams.end());
-            for (int k = 0; k < ncb; ++k) p->h_blk_idx[(size_t)cams[(size_t)k]] = k;
-            // the order of the gradient pass: camera by camera (listed order within a camera), whole waves per camera --
-            // where a camera variable is free; otherwise nothing is summed per camera and the listed order serves
-            ivec& gp = gp_of[(size_t)cc];
-            if (free_cam) {
-                ivec start((size_t)ncb + 1, 0);
-                for (int j = c0; j < c1; ++j) ++start[(size_t)p->h_blk_idx[(size_t)p->h_cam[(size_t)L->h_fac_id[(size_t)j]]] + 1];
-                for (int k = 0; k < ncb; ++k) start[(size_t)k + 1] = start[(size_t)k] + (start[(size_t)k + 1] + 63) / 64 * 64;
-                gp.assign((size_t)start[(size_t)ncb], -1);
-                for (int j = c0; j < c1; ++j) gp[(size_t)start[(size_t)p->h_blk_idx[(size_t)p->h_cam[(size_t)L->h_fac_id[(size_t)j]]]]++] = j - c0;
-            } else {
-                gp.assign((size_t)((m + 63) / 64 * 64), -1);
-                std::iota(gp.begin(), gp.begin() + m, 0);
-            }
-            const int nchunk = (int)gp.size() / 64;
-            // (the streaming solver is for what is too LARGE for the LDS: with lds_resident = 0 such components stay with
-            // solver_wg.hpp -- the comparison the bit-identity tests make; ptm_stream = 2 sends everything its tables fit)
-            const bool lds_size_ok = !many_points && lds_bytes_for(ns, ncb, nchunk) <= c->lds_limit;
-            const bool fits_lds = L->lds_resident != 0 && lds_size_ok && L->ptm_stream != 2;
-            const bool want_local = wide_comp[(size_t)cc] && !L->ptm_local_off && L->ptm_local_cameras != 0 && !local_failed &&
-                                    (L->ptm_local_cameras == 1 || ptm_bytes_for(ncb, PTM_WIDE_THREADS) > c->lds_limit);
-            const bool fits_ptm = !fits_lds && (L->ptm_stream == 2 || (L->ptm_stream == 1 && !lds_size_ok)) &&
-                                  (want_local || ptm_bytes_for(ncb, ptm_max_threads) <= c->lds_limit);
-            if (want_local && L->ptm_local) { local_failed = true; gp.clear(); continue; }   // (one such component a plan)
-            if (!fits_lds && !fits_ptm) { gp.clear(); continue; }
-            if (fits_lds) std::sort(pts.begin(), pts.end());
-            else {
-                // By number of factors, descending: the lanes of a wave run loops of equal length.  Among blocks of equal
-                // count by their cameras, in listed order, lexicographically: neighbours in a wave-chunk then read the SAME
-                // camera slots at the same time -- one LDS access serves them all, and the few distinct cameras of a chunk
-                // are neighbours too, which keeps them on different banks (random cameras: 54 % of the LDS cycles were bank
-                // conflicts, profiles/r03_a_pmc_lds_synthL.txt).  Ties: ascending id.
-                std::sort(pts.begin(), pts.end());
-                for (int k = 0; k < npb; ++k) p->h_blk_idx[(size_t)pts[(size_t)k]] = k;
-                deg.assign((size_t)npb + 1, 0);
-                for (int j = c0; j < c1; ++j) ++deg[(size_t)p->h_blk_idx[(size_t)p->h_pt[(size_t)L->h_fac_id[(size_t)j]]] + 1];
-                for (int k = 0; k < npb; ++k) deg[(size_t)k + 1] += deg[(size_t)k];   // (now a CSR over the blocks in id order)
-                ivec pcam((size_t)m), fill(deg.begin(), deg.end() - 1);
-                for (int j = c0; j < c1; ++j) {
-                    const int f = L->h_fac_id[(size_t)j];
-                    // (camera numbers within the component: h_blk_idx of the camera blocks was set above and is still valid for them)
-                    pcam[(size_t)fill[(size_t)p->h_blk_idx[(size_t)p->h_pt[(size_t)f]]]++] = p->h_blk_idx[(size_t)p->h_cam[(size_t)f]];
-                }
-                ivec ord((size_t)npb);
-                std::iota(ord.begin(), ord.end(), 0);
-                std::sort(ord.begin(), ord.end(), [&](int a, int b) {
-                    const int da = deg[(size_t)a + 1] - deg[(size_t)a], db = deg[(size_t)b + 1] - deg[(size_t)b];
-                    if (da != db) return da > db;
-                    const int* pa = pcam.data() + deg[(size_t)a];
-                    const int* pb = pcam.data() + deg[(size_t)b];
-                    for (int t = 0; t < da; ++t) if (pa[t] != pb[t]) return pa[t] < pb[t];
-                    return a < b;
-                });
-                // Whole wave-chunks of equal slot count are then dealt out over PTM_SPREAD runs of the sorted order: the chunks
-                // that the waves of a workgroup evaluate at the same time come from different runs and meet different cameras
-                // (the gradient's round sums, solver_ptm.hpp, are as long as a round's longest camera segment).
-                if (want_local) {
-                    // LOCAL: workgroup r owns a CONTIGUOUS slice of every run of chunks of equal slot count (the runs stand in
-                    // camera order: a slice meets few cameras; a slice of every run: equal work), its positions in the chunk order
-                    // are consecutive ([h_wg_chunk0[r], h_wg_chunk0[r + 1])), and inside them wave w (position - first mod 8) takes a
-                    // contiguous eighth of the workgroup's chunks: the waves of a workgroup meet different cameras at a time
-                    const int nfull = npb / 64, npc_all = (npb + 63) / 64;
-                    const int Kl = (int)std::min<int64_t>(std::min<int64_t>(c->num_cus, PTM_WIDE_MAX_GROUP), std::max<int64_t>(1, npc_all / 24));
-                    if (Kl <= PTM_MAX_GROUP) local_failed = true;
-                    else {
-                        std::vector<ivec> wl((size_t)Kl);
-                        for (int a0 = 0; a0 < nfull;) {
-                            const int T = deg[(size_t)ord[(size_t)(64 * a0)] + 1] - deg[(size_t)ord[(size_t)(64 * a0)]];
-                            int a1 = a0;
-                            while (a1 < nfull && deg[(size_t)ord[(size_t)(64 * a1)] + 1] - deg[(size_t)ord[(size_t)(64 * a1)]] == T) ++a1;
-                            const long long mm = a1 - a0;
-                            for (int rk = 0; rk < Kl; ++rk)
-                                for (long long a = a0 + rk * mm / Kl; a < a0 + (rk + 1) * mm / Kl; ++a) wl[(size_t)rk].push_back((int)a);
-                            a0 = a1;
-                        }
-                        ivec chunk_of((size_t)nfull);
-                        L->h_wg_chunk0.assign((size_t)Kl + 1, 0);
-                        int pos = 0;
-                        for (int rk = 0; rk < Kl; ++rk) {
-                            const ivec& li = wl[(size_t)rk];
-                            const int nr = (int)li.size(), nwv = PTM_WIDE_THREADS / 64;
-                            L->h_wg_chunk0[(size_t)rk] = pos;
-                            int taken = 0;
-                            for (int w = 0; w < nwv; ++w) {   // wave w's positions: first + w, first + w + 8, ... -- the next (nr - w + 7) / 8 chunks of the list
-                                const int cnt = nr > w ? (nr - w + nwv - 1) / nwv : 0;
-                                for (int j = 0; j < cnt; ++j) chunk_of[(size_t)(pos + w + nwv * j)] = li[(size_t)(taken + j)];
-                                taken += cnt;
-                            }
-                            pos += nr;
-                        }
-                        L->h_wg_chunk0[(size_t)Kl] = npc_all;   // (the last workgroup also takes the chunk of the npb % 64 blocks left over)
-                        ivec ord2(ord);
-                        for (int a = 0; a < nfull; ++a)
-                            for (int l = 0; l < 64; ++l) ord2[(size_t)(64 * a + l)] = ord[(size_t)(64 * chunk_of[(size_t)a] + l)];
-                        ord.swap(ord2);
-                        // every workgroup's cameras
-                        local_cams.assign((size_t)Kl, ivec());
-                        const size_t cam_cap = [&] { size_t k = 1; while (k < 255 && ptm_bytes_for((int)k + 1, PTM_WIDE_THREADS) <= c->lds_limit) ++k; return k; }();
-                        ivec mark((size_t)ncb, -1);
-                        size_t worst = 0;
-                        for (int rk = 0; rk < Kl && !local_failed; ++rk) {
-                            ivec& lc = local_cams[(size_t)rk];
-                            for (int k = 64 * L->h_wg_chunk0[(size_t)rk]; k < std::min(npb, 64 * L->h_wg_chunk0[(size_t)rk + 1]); ++k) {
-                                const int a = ord[(size_t)k];
-                                for (int t = deg[(size_t)a]; t < deg[(size_t)a + 1]; ++t)
-                                    if (mark[(size_t)pcam[(size_t)t]] != rk) { mark[(size_t)pcam[(size_t)t]] = rk; lc.push_back(pcam[(size_t)t]); }
-                            }
-                            std::sort(lc.begin(), lc.end());
-                            if (lc.empty()) lc.push_back(0);   // (a workgroup without chunks still has its LDS laid out for one camera)
-                            worst = std::max(worst, lc.size());
-                            if (lc.size() > cam_cap) local_failed = true;
-                        }
-                        if (std::getenv("RDIS_HIP_LOCAL_STATS"))
-                            std::fprintf(stderr, "local cameras: %d workgroups over %d chunks, %d cameras in the component, at most %zu in a workgroup (the LDS holds %zu)\n",
-                                         Kl, npc_all, ncb, worst, cam_cap);
-                        if (!local_failed) { L->ptm_local = true; L->ptm_local_K = Kl; L->ptm_local_comp = cc; }
-                    }
-                    if (local_failed) { gp.clear(); continue; }
-                } else {
-                    const int nfull = npb / 64;
-                    ivec chunk_of((size_t)nfull);
-                    int pos = 0;
-                    for (int a0 = 0; a0 < nfull;) {
-                        const int T = deg[(size_t)ord[(size_t)(64 * a0)] + 1] - deg[(size_t)ord[(size_t)(64 * a0)]];
-                        int a1 = a0;
-                        while (a1 < nfull && deg[(size_t)ord[(size_t)(64 * a1)] + 1] - deg[(size_t)ord[(size_t)(64 * a1)]] == T) ++a1;
-                        const int mm = a1 - a0, q = (mm + PTM_SPREAD - 1) / PTM_SPREAD;
-                        if (!wide_comp[(size_t)cc]) {
-                            for (int rr = 0; rr < q; ++rr)
-                                for (int gg = 0; gg < PTM_SPREAD; ++gg) { const int idx = gg * q + rr; if (idx < mm) chunk_of[(size_t)pos++] = a0 + idx; }
-                        } else {
-                            // A wide group deals chunk c to workgroup c mod K, wave (c / K) mod waves -- with K a multiple of
-                            // PTM_SPREAD the round robin above would hand all the waves of a workgroup neighbours of ONE run, i.e.
-                            // one camera: a gradient round's sums (one lane per camera entry, solver_ptm.hpp) 512 rows long, 22 000
-                            // of a round's 26 000 cycles at 8e6 factors.  Here position c takes the next chunk of run h(c), h a
-                            // weighted sum of c's hexadecimal digits mod 16: the positions c, c + K, c + 2 K, ... of a workgroup's
-                            // waves meet different runs for every K that occurs (searched over K = 1 .. 16, 32 .. 512).
-                            int used[PTM_SPREAD] = {};
-                            for (int t = 0; t < mm; ++t) {
-                                int gg = ((pos & 15) + 15 * ((pos >> 4) & 15) + ((pos >> 8) & 15) + 15 * ((pos >> 12) & 15) + ((pos >> 16) & 15) + ((pos >> 20) & 15)) % PTM_SPREAD;
-                                for (int tries = 0; tries < PTM_SPREAD && gg * q + used[gg] >= std::min(mm, (gg + 1) * q); ++tries) gg = (gg + 1) % PTM_SPREAD;
-                                chunk_of[(size_t)pos++] = a0 + gg * q + used[gg]++;
-                            }
-                        }
-                        a0 = a1;
-                    }
-                    ivec ord2(ord);
-                    for (int a = 0; a < nfull; ++a)
-                        for (int l = 0; l < 64; ++l) ord2[(size_t)(64 * a + l)] = ord[(size_t)(64 * chunk_of[(size_t)a] + l)];
-                    ord.swap(ord2);
-                }
-                ivec pts2((size_t)npb);
-                for (int k = 0; k < npb; ++k) pts2[(size_t)k] = pts[(size_t)ord[(size_t)k]];
-                pts.swap(pts2);
-            }
-            for (int k = 0; k < npb; ++k) p->h_blk_idx[(size_t)pts[(size_t)k]] = k;
-            // local free index of the component's variables (the per-problem arrays are valid for one stamp)
-            for (int i = f0; i < f1; ++i) { const int v = L->h_free_vid[(size_t)i]; p->h_owner_stamp[(size_t)v] = stamp; p->h_local[(size_t)v] = i - f0; }
-            ivec& sv = vid_of[(size_t)cc];
-            ivec& sf = free_of[(size_t)cc];
-            sv.reserve((size_t)ns); sf.reserve((size_t)ns);
-            auto slot = [&](int v) { sv.push_back(v); sf.push_back(p->h_owner_stamp[(size_t)v] == stamp ? p->h_local[(size_t)v] : -1); };
-            if (fits_lds) { for (int b : cams) for (int k = 0; k < 9; ++k) slot(b + k); }
-            else {   // the streaming solver's camera slots: ten per block, [t f k1 k2 | r | pad] (ptm_api.hpp)
-                for (int b : cams)
-                    for (int q = 0; q < PTM_CS; ++q) {
-                        const int k = ptm_var_of(q);
-                        if (k >= 0) slot(b + k); else { sv.push_back(b); sf.push_back(-1); }
-                    }
-            }
-            for (int b : pts) for (int k = 0; k < 3; ++k) slot(b + k);
-            for (int j = c0; j < c1; ++j) {
-                const int f = L->h_fac_id[(size_t)j];
-                ls_fidx[(size_t)j] = (int)((unsigned)p->h_blk_idx[(size_t)p->h_cam[(size_t)f]] | ((unsigned)p->h_blk_idx[(size_t)p->h_pt[(size_t)f]] << 12));
-                ls_pidx[(size_t)j] = p->h_blk_idx[(size_t)p->h_pt[(size_t)f]];
-            }
-            ls_ncb[(size_t)cc] = ncb;
-            ls_gcount[(size_t)cc] = nchunk;
-            if (fits_lds) {
-                kind_of[(size_t)cc] = 1;
-                L->lds_ns_cap = std::max(L->lds_ns_cap, ns);
-                L->lds_ncb_cap = std::max(L->lds_ncb_cap, ncb);
-                L->lds_chunk_cap = std::max(L->lds_chunk_cap, nchunk);
-                L->lds_max_factors = std::max<int64_t>(L->lds_max_factors, m);
-            } else {
-                kind_of[(size_t)cc] = 2;
-                if (L->ptm_local && L->ptm_local_comp == cc) {   // (a workgroup's LDS holds its own cameras only)
-                    for (const ivec& lc : local_cams) L->ptm_ncb_cap = std::max(L->ptm_ncb_cap, (int)lc.size());
-                } else {
-                    L->ptm_ncb_cap = std::max(L->ptm_ncb_cap, ncb);
-                }
-                // the point's factors, in listed order (a CSR over the point blocks in their slot order)
-                ivec& pp = pptr_of[(size_t)cc];
-                pp.assign((size_t)npb + 1, 0);
-                for (int j = c0; j < c1; ++j) ++pp[(size_t)ls_pidx[(size_t)j] + 1];
-                for (int k = 0; k < npb; ++k) pp[(size_t)k + 1] += pp[(size_t)k];
-            }
-        }
-        // (the maxima of a launch may come from different components: its LDS must hold them together)
-        if (L->lds_ns_cap > 0 && lds_bytes_for(L->lds_ns_cap, L->lds_ncb_cap, L->lds_chunk_cap) > c->lds_limit)
-            for (size_t cc = 0; cc < nc; ++cc) if (kind_of[cc] == 1) kind_of[cc] = 0;
-        auto first_other = std::stable_partition(L->h_rest.begin() + L->rest_tiny, L->h_rest.end(), [&](int cc) { return kind_of[(size_t)cc] == 0; });
-        auto first_lds = std::stable_partition(first_other, L->h_rest.end(), [&](int cc) { return kind_of[(size_t)cc] == 2; });
-        L->rest_ptm = (int)(first_lds - first_other);
-        L->rest_lds = (int)(L->h_rest.end() - first_lds);
-        // local camera numbering did not work out (a workgroup's cameras beyond the LDS, too few chunks, a second streaming
-        // component in the plan): once more without it -- the component then takes the grid solver
-        if (local_failed || (L->ptm_local && L->rest_ptm != 1)) {
-            L->ptm_local = false;
-            L->ptm_local_off = true;
-            return prepare_partition(L);
-        }
-        if (L->rest_ptm + L->rest_lds > 0) {
-            // one int32 block, tables in component order (a component without one has empty ranges)
-            ivec sptr(nc + 1, 0), gptr(nc + 1, 0), svid, sfree, gperm;
-            for (size_t cc = 0; cc < nc; ++cc) {
-                const bool has = kind_of[cc] != 0;
-                sptr[cc + 1] = sptr[cc] + (has ? (int)vid_of[cc].size() : 0);
-                gptr[cc + 1] = gptr[cc] + (has ? ls_gcount[cc] : 0);
-                if (!has) continue;
-                svid.insert(svid.end(), vid_of[cc].begin(), vid_of[cc].end());
-                sfree.insert(sfree.end(), free_of[cc].begin(), free_of[cc].end());
-                gperm.insert(gperm.end(), gp_of[cc].begin(), gp_of[cc].end());
-            }
-            // Point-major factor order of the streaming components.  A component's point blocks stand in slot order
-            // (by number of factors, descending) and are taken 64 at a time -- a wave-chunk, a lane per block.  The
-            // factors of a chunk's blocks are laid out slot-major: entry cptr[chunk] + 64 t + lane is the t-th listed
-            // factor of the lane's block (or no factor: -1), so a wave's loads of a slot are 64 neighbours and their
-            // addresses depend on nothing the wave has loaded before.  entry -> listed factor (plan-wide index).
-            ivec pm_ch0v(nc, 0), cptr;
-            L->h_pm_jg.clear();
-            for (size_t cc = 0; cc < nc; ++cc) {
-                if (kind_of[cc] != 2) continue;
-                const int c0 = L->h_fac_ptr[cc], c1 = L->h_fac_ptr[cc + 1], npb = (int)pptr_of[cc].size() - 1, npc = (npb + 63) / 64;
-                pm_pt0[cc] = (int)L->pm_blocks;
-                pm_ch0v[cc] = (int)cptr.size();
+    if (!(p->kind == KIND_BA && (L->lds_resident != 0 || L->ptm_stream != 0) && p->ncam_blocks > 0 && (int)L->h_rest.size() > L->rest_tiny)) return true;
+    const BlockArrays B = block_arrays(p);
+    const size_t nc = (size_t)L->ncomp;
+    S.kind_of.assign(nc, 0);
+    // (the staging area of its gradient grows with the workgroup; a plan with a component meant for a wide group keeps to that group's 512 lanes)
+    const int ptm_max_threads = L->ptm_threads ? L->ptm_threads : L->ptm_wide_wanted ? PTM_WIDE_THREADS : 768;
+    S.ls_ncb.assign(nc, 0); S.ls_gcount.assign(nc, 0); S.pm_pt0.assign(nc, 0);
+    S.ls_fidx.assign((size_t)L->nfac, 0); S.ls_pidx.assign((size_t)L->nfac, 0);
+    S.vid_of.assign(nc, ivec()); S.free_of.assign(nc, ivec()); S.gp_of.assign(nc, ivec()); S.pptr_of.assign(nc, ivec());
+    L->ptm_local = false; L->ptm_local_K = 0; L->ptm_local_comp = -1;
+    L->loc.clear();
+    for (size_t r = (size_t)L->rest_tiny; r < L->h_rest.size(); ++r) component_slot_tables(L, S, B, L->h_rest[r], ptm_max_threads);
+    // (the maxima of a launch may come from different components: its LDS must hold them together)
+    if (L->lds_ns_cap > 0 && lds_bytes_for(L->lds_ns_cap, L->lds_ncb_cap, L->lds_chunk_cap) > c->lds_limit)
+        for (size_t cc = 0; cc < nc; ++cc) if (S.kind_of[cc] == 1) S.kind_of[cc] = 0;
+    auto first_other = std::stable_partition(L->h_rest.begin() + L->rest_tiny, L->h_rest.end(), [&](int cc) { return S.kind_of[(size_t)cc] == 0; });
+    auto first_lds = std::stable_partition(first_other, L->h_rest.end(), [&](int cc) { return S.kind_of[(size_t)cc] == 2; });
+    L->rest_ptm = (int)(first_lds - first_other);
+    L->rest_lds = (int)(L->h_rest.end() - first_lds);
+    return !(S.local_failed || (L->ptm_local && L->rest_ptm != 1));
+}
 
-                const int e0 = (int)L->h_pm_jg.size();
-                ivec cbase((size_t)npc + 1, 0);
-                for (int ch = 0; ch < npc; ++ch)   // (descending: a chunk's first block has the most factors)
-                    cbase[(size_t)ch + 1] = cbase[(size_t)ch] + 64 * (pptr_of[cc][(size_t)(64 * ch) + 1] - pptr_of[cc][(size_t)(64 * ch)]);
-                L->h_pm_jg.resize((size_t)e0 + (size_t)cbase[(size_t)npc], -1);
-                ivec fill((size_t)npb, 0);
-                for (int j = c0; j < c1; ++j) {
-                    const int pi = ls_pidx[(size_t)j];
-                    const int e = e0 + cbase[(size_t)(pi / 64)] + 64 * fill[(size_t)pi]++ + (pi % 64);
-                    L->h_pm_jg[(size_t)e] = j;
-                }
-                for (int k = 0; k <= npc; ++k) cptr.push_back(e0 + cbase[(size_t)k]);
-                L->pm_blocks += npb;
-                if (L->ptm_local && L->ptm_local_comp == (int)cc) {
-                    // the tables of the local group (ptm_api.hpp: PtmGroupArgs): per workgroup its cameras and chunk range, per entry
-                    // of the factor stream the camera's number in the workgroup that owns the chunk, per component camera who holds it
-                    const int Kl = L->ptm_local_K, ncbg = ls_ncb[cc];
-                    L->h_pm_lcam.assign((size_t)cbase[(size_t)npc] + 64 * PTM_BLK, (short)-1);
-                    L->h_lc_off.assign((size_t)Kl, 0);
-                    std::vector<ivec> holders((size_t)ncbg);
-                    ivec g2l((size_t)ncbg, -1);
-                    for (int rk = 0; rk < Kl; ++rk) {
-                        const ivec& lc = local_cams[(size_t)rk];
-                        for (size_t k = 0; k < lc.size(); ++k) g2l[(size_t)lc[k]] = (int)k;
-                        L->h_lc_off[(size_t)rk] = (long long)L->h_lc.size();
-                        L->h_lc.push_back((int)lc.size()); L->h_lc.push_back(L->h_wg_chunk0[(size_t)rk]); L->h_lc.push_back(L->h_wg_chunk0[(size_t)rk + 1]); L->h_lc.push_back(0);
-                        L->h_lc.insert(L->h_lc.end(), lc.begin(), lc.end());
-                        for (size_t k = 0; k < lc.size(); ++k) {   // (the first workgroup that holds a camera speaks for it)
-                            L->h_lc.push_back(holders[(size_t)lc[k]].empty() ? 1 : 0);
-                            holders[(size_t)lc[k]].push_back((rk << 8) | (int)k);
-                        }
-                        for (int e = cbase[(size_t)L->h_wg_chunk0[(size_t)rk]]; e < cbase[(size_t)L->h_wg_chunk0[(size_t)rk + 1]]; ++e) {
-                            const int j = L->h_pm_jg[(size_t)(e0 + e)];
-                            if (j >= 0) L->h_pm_lcam[(size_t)e] = (short)g2l[(size_t)(((unsigned)ls_fidx[(size_t)j]) & 0xFFFu)];
-                        }
-                    }
-                    L->h_cr_ptr.assign(1, 0);
-                    for (int g = 0; g < ncbg; ++g) {
-                        L->h_cr.insert(L->h_cr.end(), holders[(size_t)g].begin(), holders[(size_t)g].end());
-                        L->h_cr_ptr.push_back((int)L->h_cr.size());
-                    }
-                }
-            }
-            L->pm_entries = (int64_t)L->h_pm_jg.size();
-            L->pm_cptr_len = (int64_t)cptr.size();
-            L->ls_total_chunks = gptr[nc];
-            L->ptm_min_points = INT64_MAX;
-            for (size_t cc = 0; cc < nc; ++cc)
-                if (kind_of[cc] == 2) L->ptm_min_points = std::min<int64_t>(L->ptm_min_points, (int64_t)pptr_of[cc].size() - 1);
-            ivec& blk = L->h_lds_ints;
-            auto put = [&](const ivec& v) { const size_t off = blk.size(); blk.insert(blk.end(), v.begin(), v.end()); return off; };
-            L->off_ls_ptr = put(sptr); L->off_ls_vid = put(svid); L->off_ls_free = put(sfree);
-            L->off_ls_ncb = put(ls_ncb); L->off_ls_fidx = put(ls_fidx); L->off_ls_gptr = put(gptr); L->off_ls_gperm = put(gperm);
-            L->off_pm_pt0 = put(pm_pt0); L->off_pm_ch0 = put(pm_ch0v); L->off_pm_cptr = put(cptr); L->off_pm_jg = put(L->h_pm_jg);
-            // rotations: no camera variable free among a launch's components -> records, read only; otherwise records
-            // that follow the trial point when a lane has several factors per camera and trial (else each factor forms its own)
-            auto camfix_of = [&](size_t r0, size_t r1) {
-                for (size_t r = r0; r < r1; ++r) {
-                    const int cc = L->h_rest[r];
-                    for (int k = L->h_free_ptr[(size_t)cc]; k < L->h_free_ptr[(size_t)cc + 1]; ++k)
-                        if (p->h_block_of[(size_t)L->h_free_vid[(size_t)k]] >= 0) return false;
-                }
-                return true;
-            };
-            const size_t r_lds = L->h_rest.size() - (size_t)L->rest_lds, r_ptm = r_lds - (size_t)L->rest_ptm;
-            const bool records = L->lds_rot >= 0 ? L->lds_rot == 1 : L->lds_max_factors > 512;
-            // (the stale-cache emulation is instantiated for per-factor rotations only: the same bits per factor, fewer kernels)
-            L->lds_rot_mode = (L->camera_records == 0 || L->emulate_stale) ? ROT_PER_FACTOR : camfix_of(r_lds, L->h_rest.size()) ? ROT_CAMFIX : records ? ROT_RECORDS : ROT_PER_FACTOR;
-            // (the streaming solver always works from per-camera records: rewritten at every trial point, or never)
-            L->ptm_rot_mode = camfix_of(r_ptm, r_lds) ? ROT_CAMFIX : ROT_RECORDS;
-        }
+// step 6, the end: the components' tables as one int32 block, the streaming components' factor stream, the rotation modes
+void assemble_slot_block(rdis_hip_plan* L, Partition& S) {
+    if (L->rest_ptm + L->rest_lds == 0) return;
+    const size_t nc = (size_t)L->ncomp;
+    // one int32 block, tables in component order (a component without one has empty ranges)
+    ivec sptr(nc + 1, 0), gptr(nc + 1, 0), svid, sfree, gperm;
+    for (size_t cc = 0; cc < nc; ++cc) {
+        const bool has = S.kind_of[cc] != 0;
+        sptr[cc + 1] = sptr[cc] + (has ? (int)S.vid_of[cc].size() : 0);
+        gptr[cc + 1] = gptr[cc] + (has ? S.ls_gcount[cc] : 0);
+        if (!has) continue;
+        svid.insert(svid.end(), S.vid_of[cc].begin(), S.vid_of[cc].end());
+        sfree.insert(sfree.end(), S.free_of[cc].begin(), S.free_of[cc].end());
+        gperm.insert(gperm.end(), S.gp_of[cc].begin(), S.gp_of[cc].end());
     }
+    ivec pm_ch0v(nc, 0), cptr, cbase;
+    L->h_pm_jg.clear();
+    L->ptm_min_points = INT64_MAX;
+    for (size_t cc = 0; cc < nc; ++cc) {
+        if (S.kind_of[cc] != 2) continue;
+        const int c0 = L->h_fac_ptr[cc], npb = (int)S.pptr_of[cc].size() - 1, e0 = (int)L->h_pm_jg.size();
+        S.pm_pt0[cc] = (int)L->pm_blocks;
+        pm_ch0v[cc] = (int)cptr.size();
+        ptm_factor_stream(c0, L->h_fac_ptr[cc + 1] - c0, S.ls_pidx.data() + c0, S.pptr_of[cc], L->h_pm_jg, cptr, cbase);
+        L->pm_blocks += npb;
+        L->ptm_min_points = std::min<int64_t>(L->ptm_min_points, npb);
+        if (L->ptm_local && L->ptm_local_comp == (int)cc) ptm_local_tables(S.ls_ncb[cc], S.local_cams, cbase, e0, L->h_pm_jg, S.ls_fidx.data(), L->loc);
+    }
+    L->pm_entries = (int64_t)L->h_pm_jg.size();
+    L->pm_cptr_len = (int64_t)cptr.size();
+    L->ls_total_chunks = gptr[nc];
+    ivec& blk = L->h_lds_ints;
+    auto put = [&](const ivec& v) { const size_t off = blk.size(); blk.insert(blk.end(), v.begin(), v.end()); return off; };
+    L->off_ls_ptr = put(sptr); L->off_ls_vid = put(svid); L->off_ls_free = put(sfree);
+    L->off_ls_ncb = put(S.ls_ncb); L->off_ls_fidx = put(S.ls_fidx); L->off_ls_gptr = put(gptr); L->off_ls_gperm = put(gperm);
+    L->off_pm_pt0 = put(S.pm_pt0); L->off_pm_ch0 = put(pm_ch0v); L->off_pm_cptr = put(cptr); L->off_pm_jg = put(L->h_pm_jg);
+    // rotations: no camera variable free among a launch's components -> records, read only; otherwise records
+    // that follow the trial point when a lane has several factors per camera and trial (else each factor forms its own)
+    const size_t r_lds = L->h_rest.size() - (size_t)L->rest_lds, r_ptm = r_lds - (size_t)L->rest_ptm;
+    const bool records = L->lds_rot >= 0 ? L->lds_rot == 1 : L->lds_max_factors > 512;
+    // (the stale-cache emulation is instantiated for per-factor rotations only: the same bits per factor, fewer kernels)
+    L->lds_rot_mode = (L->camera_records == 0 || L->emulate_stale) ? ROT_PER_FACTOR : cameras_fixed(L, r_lds, L->h_rest.size()) ? ROT_CAMFIX : records ? ROT_RECORDS : ROT_PER_FACTOR;
+    // (the streaming solver always works from per-camera records: rewritten at every trial point, or never)
+    L->ptm_rot_mode = cameras_fixed(L, r_ptm, r_lds) ? ROT_CAMFIX : ROT_RECORDS;
+}
+
+// step 7: device memory and uploads
+int upload_partition(rdis_hip_plan* L, Partition& S) {
+    rdis_hip_problem* p = L->prob;
+    rdis_hip_ctx* c = p->ctx;
     if (L->rest_tiny > 0 && L->group_blocks4 == 0) {
         int b4 = 0, b16 = 0;
         HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b4, cgd_group_kernel<4, QUAD_THREADS>, QUAD_THREADS, 0));
@@ -2247,7 +2054,7 @@ int prepare_partition(rdis_hip_plan* L) {
     }
     int rc = plan_alloc(L, L->rest_order, std::max<size_t>(L->h_rest.size(), 1) * sizeof(int));
     if (!rc) rc = plan_alloc(L, L->queue, 256);
-    if (!rc && max_n > 0) rc = plan_alloc(L, L->xi_glob, (size_t)max_n * sizeof(double));
+    if (!rc && S.max_n > 0) rc = plan_alloc(L, L->xi_glob, (size_t)S.max_n * sizeof(double));
     if (rc) return rc;
     if (L->rest_lds + L->rest_ptm > 0) {
         rc = plan_alloc(L, L->lds_ints, L->h_lds_ints.size() * sizeof(int));
@@ -2271,18 +2078,19 @@ int prepare_partition(rdis_hip_plan* L) {
         HIPCHK(c, ptm_gather_launch(grid_for(c, L->pm_entries, 256), c->stream, (int)L->pm_entries, L->lds_ints.as<int>() + L->off_pm_jg, V.ls_fidx, V.ls_obs,
                                     L->pm_cam.as<short>(), L->pm_obs.as<double2>()));
         if (L->ptm_local) {   // the stream names a factor's camera by its number in the workgroup that owns the chunk; the group's tables
-            HIPCHK(c, hipMemcpyAsync(L->pm_cam.p, L->h_pm_lcam.data(), std::min(L->h_pm_lcam.size(), (size_t)L->pm_entries + 64 * PTM_BLK) * sizeof(short),
+            const PtmLocalTables& T = L->loc;
+            HIPCHK(c, hipMemcpyAsync(L->pm_cam.p, T.pm_lcam.data(), std::min(T.pm_lcam.size(), (size_t)L->pm_entries + 64 * PTM_BLK) * sizeof(short),
                                      hipMemcpyHostToDevice, c->stream));
-            rc = plan_alloc(L, L->lc_dev, L->h_lc.size() * sizeof(int));
-            if (!rc) rc = plan_alloc(L, L->lc_off_dev, L->h_lc_off.size() * sizeof(long long));
-            if (!rc) rc = plan_alloc(L, L->cr_ptr_dev, L->h_cr_ptr.size() * sizeof(int));
-            if (!rc) rc = plan_alloc(L, L->cr_dev, std::max<size_t>(L->h_cr.size(), 1) * sizeof(int));
-            if (!rc) rc = plan_alloc(L, L->ptm_tot, 2 * (size_t)PTM_CS * (L->h_cr_ptr.size() - 1) * sizeof(double));
+            rc = plan_alloc(L, L->lc_dev, T.lc.size() * sizeof(int));
+            if (!rc) rc = plan_alloc(L, L->lc_off_dev, T.lc_off.size() * sizeof(long long));
+            if (!rc) rc = plan_alloc(L, L->cr_ptr_dev, T.cr_ptr.size() * sizeof(int));
+            if (!rc) rc = plan_alloc(L, L->cr_dev, std::max<size_t>(T.cr.size(), 1) * sizeof(int));
+            if (!rc) rc = plan_alloc(L, L->ptm_tot, 2 * (size_t)PTM_CS * (T.cr_ptr.size() - 1) * sizeof(double));
             if (rc) return rc;
-            HIPCHK(c, hipMemcpyAsync(L->lc_dev.p, L->h_lc.data(), L->h_lc.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(L->lc_off_dev.p, L->h_lc_off.data(), L->h_lc_off.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(L->cr_ptr_dev.p, L->h_cr_ptr.data(), L->h_cr_ptr.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(L->cr_dev.p, L->h_cr.data(), L->h_cr.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(L->lc_dev.p, T.lc.data(), T.lc.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(L->lc_off_dev.p, T.lc_off.data(), T.lc_off.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(L->cr_ptr_dev.p, T.cr_ptr.data(), T.cr_ptr.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(L->cr_dev.p, T.cr.data(), T.cr.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
         }
     }
     if (!L->coop.empty()) {
@@ -2290,7 +2098,14 @@ int prepare_partition(rdis_hip_plan* L) {
         if (rc) return rc;
         HIPCHK(c, hipMemcpyAsync(L->coop_ints.p, L->h_coop_ints.data(), L->h_coop_ints.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     }
-    // cooperative groups, packed into launches of at most `cap` workgroups
+    return 0;
+}
+
+// step 8: cooperative groups, packed into launches of at most `cap` workgroups
+int pack_coop_launches(rdis_hip_plan* L, int cap) {
+    rdis_hip_problem* p = L->prob;
+    rdis_hip_ctx* c = p->ctx;
+    int rc = 0;
     size_t max_groups = 1;
     for (size_t i = 0; i < L->coop.size();) {
         CoopLaunch cl;
@@ -2335,11 +2150,36 @@ int prepare_partition(rdis_hip_plan* L) {
         for (size_t g = 0; g < hg.size(); ++g) hg[g].a.st = p->coop_state.as<CoopState>() + g;
         HIPCHK(c, hipMemcpyAsync(L->coop_launches[l].groups.p, hg.data(), hg.size() * sizeof(CoopGroup), hipMemcpyHostToDevice, c->stream));
     }
+    return 0;
+}
+
+// decide which solver takes each component and build what it needs
+int prepare_partition(rdis_hip_plan* L) {
+    rdis_hip_ctx* c = L->prob->ctx;
+    Partition S;
+    for (;;) {
+        S = Partition();
+        drop_partition(L);
+        choose_coop_layout(L, S);
+        choose_group_mode(L, S);
+        int rc = assign_components(L, S);
+        if (rc) return rc;
+        order_rest(L);
+        if (build_slot_tables(L, S)) break;
+        // local camera numbering did not work out: once more without it -- the component then takes the grid solver
+        // (once: the flag stays set, and without local numbering nothing above fails)
+        L->ptm_local = false;
+        L->ptm_local_off = true;
+    }
+    assemble_slot_block(L, S);
+    int rc = upload_partition(L, S);
+    if (!rc) rc = pack_coop_launches(L, S.cap);
+    if (rc) return rc;
     // (a transient plan lives until its results are fetched, which waits for the stream)
     if (!L->transient) HIPCHK(c, hipStreamSynchronize(c->stream));
     if (!L->h_rest.empty()) HIPCHK(c, hipMemcpyAsync(L->rest_order.p, L->h_rest.data(), L->h_rest.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     L->partition_dirty = false;
-    L->coop_state_gen = p->coop_state_gen;
+    L->coop_state_gen = L->prob->coop_state_gen;
     return 0;
 }
 
@@ -2355,67 +2195,27 @@ int launch_wg(rdis_hip_plan* L, hipStream_t stream, int threads, int first, int 
     })));
     return 0;
 }
-// The gradient's rounds of the point-major streaming solver (solver_ptm.hpp: gradient_to_xi) for workgroups of
-// `threads` lanes, K to a component.  Workgroup (component, rank r) takes the point chunks c = r (mod K), its wave w
-// those with (c / K) mod waves = w, slot by slot: that is the wave's sequence of steps, and round rr of the workgroup
-// is every wave's rr-th step.  Within a round the factors are ranked by camera block (within a camera by wave and
-// lane): a factor's rank is the staging row of its camera partials (pm_grow, two bytes per factor), and a round's
-// table names per camera the first row of its segment [ncb + 1] -- the order of the sums.  Built on the host from the
-// plan's point-major tables, once per (threads, K); nothing to build when no camera variable is free.
-// A trial's work by wave (solver_ptm.hpp: eval_line), for the same workgroups: the workgroup's wave-chunks cut into blocks of
-// PTM_BLK slots, the blocks in chunk order dealt out in equal CONTIGUOUS shares -- a wave's share is a run of whole chunks
-// with at most a partial one at either end (a chunk's 64 point blocks times some of their slots).  By whole chunks 41 of them
-// over 12 waves are four for some and three for the rest, and a trial waits for the slowest.
+// The streaming solver's work tables for workgroups of `threads` lanes, K to a component: a trial's segment rows and the gradient's
+// rounds (plan_tables.hpp: ptm_segment_rows, ptm_round_tables).  Built on the host from the plan's point-major tables, once per
+// (threads, K); no rounds to build when no camera variable is free.
+static PtmStreamTables ptm_stream_tables(const rdis_hip_plan* L) {
+    const int* li = L->h_lds_ints.data();
+    const size_t r_lds = L->h_rest.size() - (size_t)L->rest_lds, r_ptm = r_lds - (size_t)L->rest_ptm;
+    PtmStreamTables T;
+    T.ncomp = L->ncomp; T.pm_entries = L->pm_entries;
+    T.comps = L->h_rest.data() + r_ptm; T.ncomps = r_lds - r_ptm;
+    T.ls_ptr = li + L->off_ls_ptr; T.ls_ncb = li + L->off_ls_ncb; T.ls_fidx = li + L->off_ls_fidx;
+    T.pm_ch0 = li + L->off_pm_ch0; T.cptr = li + L->off_pm_cptr; T.jg = li + L->off_pm_jg;
+    T.local_comp = L->ptm_local ? L->ptm_local_comp : -1;
+    T.local = &L->loc;
+    return T;
+}
 static int ptm_build_segments(rdis_hip_plan* L, int threads, int K) {
     rdis_hip_ctx* c = L->prob->ctx;
-    const int nw = threads / 64;
-    const int* li = L->h_lds_ints.data();
-    const int* ls_ptr = li + L->off_ls_ptr;
-    const int* ls_ncb = li + L->off_ls_ncb;
-    const int* pm_ch0 = li + L->off_pm_ch0;
-    const int* cptr = li + L->off_pm_cptr;
     const size_t nwg = (size_t)L->ncomp * (size_t)K;
-    std::vector<long long> off(nwg, 0);
-    ivec rows;   // per workgroup: its number of rows R, 0, 0, 0, then three planes of R ints
-    std::vector<ivec> share((size_t)nw);
-    const size_t r_lds = L->h_rest.size() - (size_t)L->rest_lds, r_ptm = r_lds - (size_t)L->rest_ptm;
-    for (size_t ri = r_ptm; ri < r_lds; ++ri) {
-        const int cc = L->h_rest[ri];
-        const int ncb = ls_ncb[cc], ns = ls_ptr[cc + 1] - ls_ptr[cc], npb = (ns - PTM_CS * ncb) / 3, npc = (npb + 63) / 64;
-        const int* cp = cptr + pm_ch0[cc];
-        const bool local = L->ptm_local && L->ptm_local_comp == cc;   // (a workgroup's chunks: consecutive ones instead of every K-th)
-        for (int rk = 0; rk < K; ++rk) {
-            const int ch0 = local ? L->h_wg_chunk0[(size_t)rk] : rk, chend = local ? L->h_wg_chunk0[(size_t)rk + 1] : npc, chstep = local ? 1 : K;
-            long long units = 0;
-            for (int ch = ch0; ch < chend; ch += chstep) units += ((cp[ch + 1] - cp[ch]) / 64 + PTM_BLK - 1) / PTM_BLK;
-            size_t depth = 0;
-            long long u = 0;   // blocks dealt out so far
-            int ch = ch0, done = 0;   // the chunk at hand and its blocks already dealt out
-            for (int w = 0; w < nw; ++w) {
-                ivec& sh = share[(size_t)w];
-                sh.clear();
-                const long long end = units * (w + 1) / nw;
-                while (u < end) {
-                    const int nb = ((cp[ch + 1] - cp[ch]) / 64 + PTM_BLK - 1) / PTM_BLK;
-                    if (done >= nb) { ch += chstep; done = 0; continue; }
-                    const int take = (int)std::min<long long>(nb - done, end - u);
-                    const int e0 = cp[ch] + 64 * PTM_BLK * done, e1 = std::min(cp[ch + 1], e0 + 64 * PTM_BLK * take);
-                    sh.push_back(ch); sh.push_back(e0); sh.push_back(e1); sh.push_back(0);
-                    done += take; u += take;
-                }
-                depth = std::max(depth, sh.size() / 4);
-            }
-            // (two rows of nothing behind every wave's last: the loop asks for its rows two ahead)
-            // (and at least one row of work: a rank with no chunks still has the three rows a wave reads up front)
-            const size_t base = rows.size(), R = (std::max<size_t>(depth, 1) + 2) * (size_t)nw;
-            off[(size_t)cc * K + rk] = (long long)base;
-            rows.resize(base + 4 + 3 * R, 0);
-            rows[base] = (int)R;
-            for (int w = 0; w < nw; ++w)
-                for (size_t k = 0; k < share[(size_t)w].size() / 4; ++k)
-                    for (size_t q = 0; q < 3; ++q) rows[base + 4 + q * R + k * (size_t)nw + (size_t)w] = share[(size_t)w][4 * k + q];
-        }
-    }
+    std::vector<long long> off;
+    ivec rows;
+    ptm_segment_rows(ptm_stream_tables(L), threads, K, rows, off);
     int rc = plan_alloc(L, L->pm_segs, std::max<size_t>(rows.size(), 4) * sizeof(int));
     if (!rc) rc = plan_alloc(L, L->pm_sg_off, nwg * sizeof(long long));
     if (rc) return rc;
@@ -2440,74 +2240,15 @@ int ptm_build_rounds(rdis_hip_plan* L, int threads, int K) {
     L->rounds_threads = L->rounds_K = 0;
     { const int rc = ptm_build_segments(L, threads, K); if (rc) return rc; }
     if (L->ptm_rot_mode == ROT_CAMFIX) { L->rounds_threads = threads; L->rounds_K = K; L->rounds_slots = rs; return 0; }
-    const int nw = threads / 64;
-    const int* li = L->h_lds_ints.data();
-    const int* ls_ptr = li + L->off_ls_ptr;
-    const int* ls_ncb = li + L->off_ls_ncb;
-    const unsigned* fidx = reinterpret_cast<const unsigned*>(li + L->off_ls_fidx);
-    const int* pm_ch0 = li + L->off_pm_ch0;
-    const int* cptr = li + L->off_pm_cptr;
-    const int* jg = li + L->off_pm_jg;
+    const PtmStreamTables T = ptm_stream_tables(L);
     const size_t nwg = (size_t)L->ncomp * (size_t)K;
-    std::vector<long long> off(nwg, 0);
-    ivec nr(nwg, 0);
-    std::vector<unsigned short> tab, grow((size_t)L->pm_entries + 64 * PTM_BLK, 0);
-    std::vector<ivec> steps((size_t)nw), step_slots((size_t)nw);
-    ivec seg, pos;
-    const size_t r_lds = L->h_rest.size() - (size_t)L->rest_lds, r_ptm = r_lds - (size_t)L->rest_ptm;
-    for (size_t ri = r_ptm; ri < r_lds; ++ri) {
-        const int cc = L->h_rest[ri];
-        const int ncb_all = ls_ncb[cc], ns = ls_ptr[cc + 1] - ls_ptr[cc], npb = (ns - PTM_CS * ncb_all) / 3, npc = (npb + 63) / 64;
-        const int* cp = cptr + pm_ch0[cc];
-        const bool local = L->ptm_local && L->ptm_local_comp == cc;
-        for (int rk = 0; rk < K; ++rk) {
-            // (a local group: the workgroup's own cameras, under its own numbers; its chunks consecutive, wave w every eighth from the w-th on)
-            const int ncb = local ? L->h_lc[(size_t)L->h_lc_off[(size_t)rk]] : ncb_all;
-            const size_t stride = (size_t)ptm_round_stride(ncb);
-            auto cam_of = [&](int e, int j) { return local ? (int)L->h_pm_lcam[(size_t)e] : (int)(fidx[j] & 0xFFFu); };   // (an entry's camera as the stream names it)
-            size_t nrounds = 0;
-            for (int w = 0; w < nw; ++w) {
-                ivec& st = steps[(size_t)w];
-                ivec& sn = step_slots[(size_t)w];
-                st.clear(); sn.clear();
-                const int ch0 = local ? L->h_wg_chunk0[(size_t)rk] + w : rk + K * w, chend = local ? L->h_wg_chunk0[(size_t)rk + 1] : npc, chstep = local ? nw : K * nw;
-                // (a step: one slot of a chunk, or -- two slots a round -- a block of up to two of ONE chunk)
-                for (int ch = ch0; ch < chend; ch += chstep)
-                    for (int e = cp[ch]; e < cp[ch + 1]; e += 64 * rs) { st.push_back(e); sn.push_back(std::min(rs, (cp[ch + 1] - e) / 64)); }
-                nrounds = std::max(nrounds, st.size());
-            }
-            const size_t base = tab.size();
-            off[(size_t)cc * K + rk] = (long long)base;
-            nr[(size_t)cc * K + rk] = (int)nrounds;
-            tab.resize(base + nrounds * stride, 0);
-            for (size_t rr = 0; rr < nrounds; ++rr) {
-                unsigned short* rec = tab.data() + base + rr * stride;
-                seg.assign((size_t)ncb + 1, 0);
-                for (int w = 0; w < nw; ++w) {
-                    if (rr >= steps[(size_t)w].size()) continue;
-                    const int e = steps[(size_t)w][rr];
-                    for (int l = 0; l < 64 * step_slots[(size_t)w][rr]; ++l) { const int j = jg[e + l]; if (j >= 0) ++seg[(size_t)cam_of(e + l, j) + 1]; }
-                }
-                for (int k = 0; k < ncb; ++k) seg[(size_t)k + 1] += seg[(size_t)k];
-                for (int k = 0; k <= ncb; ++k) rec[k] = (unsigned short)seg[(size_t)k];
-                pos.assign(seg.begin(), seg.end() - 1);
-                // (within a camera: the round's first slots by wave and lane, then its second slots -- with every chunk an even number of
-                // slots long that is the order of one slot a round)
-                for (int sl = 0; sl < rs; ++sl)
-                    for (int w = 0; w < nw; ++w) {
-                        if (rr >= steps[(size_t)w].size() || sl >= step_slots[(size_t)w][rr]) continue;
-                        const int e = steps[(size_t)w][rr] + 64 * sl;
-                        for (int l = 0; l < 64; ++l) {
-                            const int j = jg[e + l];
-                            if (j >= 0) grow[(size_t)(e + l)] = (unsigned short)pos[(size_t)cam_of(e + l, j)]++;
-                        }
-                    }
-            }
-        }
-    }
+    std::vector<long long> off;
+    ivec nr;
+    std::vector<unsigned short> tab, grow;
+    ptm_round_tables(T, threads, K, rs, tab, grow, off, nr);
     if (std::getenv("RDIS_HIP_ROUND_STATS") && nwg > 0) {   // (tuning: how uneven are a round's camera segments?)
-        const int cc = L->h_rest[r_ptm];
-        const int ncb = ls_ncb[cc];
+        const int cc = T.comps[0];
+        const int ncb = T.ls_ncb[cc];
         const size_t stride = (size_t)ptm_round_stride(ncb);
         const unsigned short* t0 = tab.data() + off[(size_t)cc * K];
         long long sum_max = 0, worst = 0, rows = 0, active = 0;

@@ -394,7 +394,7 @@ struct PtmEnv {
     // PTM_BLK slots at a time.  Everything is asked for a block of slots before it is used: while one block of slots is
     // evaluated the next one's cameras and observations are in flight (the next chunk's first block during a chunk's last),
     // from a chunk's first block on the next chunk's point records, and the entry range of the chunk after that.
-    // The waves' shares are equal runs of blocks of slots in chunk order (the plan's rows, rdis_hip.hip: ptm_build_segments): a
+    // The waves' shares are equal runs of blocks of slots in chunk order (the plan's rows, plan_tables.hpp: ptm_segment_rows): a
     // wave evaluates some whole chunks and at most part of the slots of one more at either end.
     // The workgroup's barrier behind assign_cameras<.., false> stands in here, behind the first loads: the wave that forms
     // the cameras' records is the last to arrive, and what the others asked for is on its way meanwhile.
