@@ -240,7 +240,7 @@ int rdis_hip_plan_fetch(rdis_hip_plan *plan, double *x_out, double *fret, double
  *                             over components); copied before the call returns
  *   x_out[s][nfree_total]; fret, delta, iters, status, nfeval, ngeval [s][ncomp]; best[ncomp]
  * plan_solve_starts is asynchronous on the context's stream; plan_fetch_starts waits and copies out (any pointer
- * may be NULL); the outputs of all starts are kept until the next plan_solve_starts.
+ * may be NULL); the outputs of all starts are kept until the next plan_solve_starts or plan_solve_population.
  * State afterwards -- what an RDIS node keeps of its restarts, the minimum: best[c] is the start with the lowest
  * fret[s][c] (the lowest index on a tie; a NaN is never best unless every start of the component is one: then 0);
  * the free variables of component c are left assigned to that start's result (a following
@@ -266,6 +266,59 @@ int rdis_hip_plan_solve_starts(rdis_hip_plan *plan, int64_t nstarts, const doubl
 int rdis_hip_plan_fetch_starts(rdis_hip_plan *plan, double *x_out, double *fret, double *delta,
                                int32_t *iters, int32_t *status, int64_t *nfeval, int64_t *ngeval,
                                int32_t *best);
+/* ---- populations: S complete states on the device, a plan solved on all of them at once ----
+ * RDIS's restarts draw a whole state and then run the decomposition on it: fix a separator, solve the children, swap,
+ * repeat (optBA's sample loop, src/bundleadjust/optBA.cpp:198-224; sampleRandomState, src/RDISOptimizer.cpp:1196-1216).
+ * From the second half-round on the constants of sample s are sample s's own results, which plan_solve_starts -- constants
+ * shared by all starts -- cannot express.  A population holds X[nmembers][N] on the device, every member a complete
+ * assignment of the problem's variables; plan_solve_population runs a plan on all members in one launch, member s taking
+ * both its start and its constants from X[s] and leaving its result there, so that the next plan (the other variables
+ * free) follows with no host traffic (rdis_amd/csrc/solver_lds_population.hpp).
+ *   population_create   allocates X; x[nmembers][N] row-major, or NULL: every member a copy of the problem's currently
+ *                       assigned x.  nmembers >= 1 (RDIS_HIP_EINVAL), below 2^31 and nmembers * N below 9e15
+ *                       (RDIS_HIP_ERANGE).  Both problem kinds.  A population belongs to one problem and is destroyed
+ *                       before it.  Its device memory is its own (not in any plan_device_bytes).
+ *   population_set_x / _get_x   members first .. first + count - 1, n values each: val / out [count][n] row-major;
+ *                       vid == NULL: variables 0..n-1 (n <= N); ids and ranges checked like rdis_hip_set_x.
+ *   population_assign   the problem's assigned x := that member's x (asynchronous on the context's stream).
+ *   population_eval     f[s], s < nmembers: bit for bit what rdis_hip_eval(p, nf, fac, .) returns when member s's x is the
+ *                       assigned x -- the same kernels with x replaced, the rotation records of a long bundle-adjustment
+ *                       list rebuilt from the member's x --, all members enqueued without a wait, one copy back.  The
+ *                       problem's assigned x and what eval_grad_device handed out are left as they were.
+ *   plan_solve_population   asynchronous on the context's stream.  For every member s and component c exactly what
+ *                       plan_set_start(plan, NULL) + plan_solve would do on a problem whose assigned x is X[s] -- the same
+ *                       bits in fret, delta, x, iters, status, nfeval, ngeval: the start is X[s][free_vid], clamped at
+ *                       entry; the constants are X[s][v] for the other variables the component's factors read; the result
+ *                       (clamped; after a rollback clamp(x_init)) is assigned into X[s][free_vid]; an empty component's
+ *                       variables are untouched, its status RDIS_HIP_EXIT_EMPTY.  Writing into X[s] needs no replica of
+ *                       it: the components of a plan are independent (plan_create: RDIS_HIP_EOVERLAP), so a variable one
+ *                       workgroup of member s writes is read by no other workgroup of member s.  The problem's own x, the
+ *                       plan's ordinary outputs (plan_fetch, plan_objective_device) and start are not touched.
+ *   plan_fetch_population   waits and copies out (any pointer may be NULL): x_out[s][nfree_total]; fret, delta, iters,
+ *                       status, nfeval, ngeval [s][ncomp].  The outputs are kept until the next plan_solve_population or
+ *                       plan_solve_starts on the plan, whose buffers they share: plan_fetch_starts after a population
+ *                       solve, and plan_fetch_population after a multi-start solve or before any, return RDIS_HIP_EINVAL.
+ * Workspace: the replicas of the multi-start entry on the LDS-resident solver (5 doubles per free variable and one per
+ * partial, per member of a launch), bounded by the plan option "starts_workspace_bytes" with the same splitting into
+ * launches of R members (plan_get_info "starts_per_launch" / "starts_launches"), counted by plan_device_bytes;
+ * plan_last_kernel_ms covers the solver launches.
+ * Scope: a bundle-adjustment problem, every non-empty component of the plan on the LDS-resident solver (plan_get_info
+ * "components_lds"); a persistent plan; default factor_rounding; emulate_stale_cache, trace_records and dump_iters off; the
+ * population must be the plan's problem's.  Not yet: the other solvers, nonlinear-product plans (create, set_x, get_x,
+ * assign and eval do work for that kind).  Anything else: RDIS_HIP_EINVAL and a message that names the cause; the plan and
+ * the population stay usable. */
+typedef struct rdis_hip_population rdis_hip_population;
+int rdis_hip_population_create(rdis_hip_problem *p, int64_t nmembers, const double *x, rdis_hip_population **out);
+void rdis_hip_population_destroy(rdis_hip_population *pop);
+int rdis_hip_population_set_x(rdis_hip_population *pop, int64_t first, int64_t count, int64_t n, const int64_t *vid,
+                              const double *val);
+int rdis_hip_population_get_x(rdis_hip_population *pop, int64_t first, int64_t count, int64_t n, const int64_t *vid,
+                              double *out);
+int rdis_hip_population_assign(rdis_hip_population *pop, int64_t member);
+int rdis_hip_population_eval(rdis_hip_population *pop, int64_t nf, const int64_t *fac, double *f);
+int rdis_hip_plan_solve_population(rdis_hip_plan *plan, rdis_hip_population *pop, int32_t maxiters, double ftol);
+int rdis_hip_plan_fetch_population(rdis_hip_plan *plan, double *x_out, double *fret, double *delta, int32_t *iters,
+                                   int32_t *status, int64_t *nfeval, int64_t *ngeval);
 /* sum of fret over the plan's components, left on the device (for the RCCL
  * all-reduce of the top-level objective, src/RDISOptimizer.cpp:1491-1494);
  * returns a device pointer to one double valid until the next plan_solve. */

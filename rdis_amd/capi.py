@@ -80,6 +80,14 @@ SYMBOLS = {
     "rdis_hip_plan_fetch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rdis_hip_plan_solve_starts": (C.c_int, [_vp, _i64, _vp, C.c_int32, C.c_double]),
     "rdis_hip_plan_fetch_starts": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rdis_hip_population_create": (C.c_int, [_vp, _i64, _vp, C.POINTER(_vp)]),
+    "rdis_hip_population_destroy": (None, [_vp]),
+    "rdis_hip_population_set_x": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
+    "rdis_hip_population_get_x": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
+    "rdis_hip_population_assign": (C.c_int, [_vp, _i64]),
+    "rdis_hip_population_eval": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "rdis_hip_plan_solve_population": (C.c_int, [_vp, _vp, C.c_int32, C.c_double]),
+    "rdis_hip_plan_fetch_population": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rdis_hip_plan_objective_device": (C.c_int, [_vp, C.POINTER(_vp)]),
     "rdis_hip_comm_unique_id": (C.c_int, [_vp]),
     "rdis_hip_comm_create": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, C.POINTER(_vp)]),
@@ -102,7 +110,7 @@ SYMBOLS = {
 }
 
 _lib: Optional[C.CDLL] = None
-_live = []  # weak references to open handles, closed in order (plans, problems, contexts) at exit
+_live = []  # weak references to open handles, closed in order (plans, populations, problems, contexts) at exit
 
 
 def _register(obj):
@@ -134,7 +142,7 @@ class _Cell:
 def _close_all():
     # the HIP runtime must still be loaded when device memory and streams are released
     objs = [r() for r in _live]
-    for cls in ("Comm", "Plan", "Problem", "Context"):
+    for cls in ("Comm", "Plan", "Population", "Problem", "Context"):
         for o in objs:
             if o is not None and type(o).__name__ == cls:
                 try:
@@ -249,7 +257,8 @@ class BatchResult:
 
 @dataclass
 class StartsResult:
-    """a multi-start solve: x [nstarts, nfree]; the others [nstarts, ncomp]; best [ncomp], the start kept per component"""
+    """a multi-start solve: x [nstarts, nfree]; the others [nstarts, ncomp]; best [ncomp], the start kept per component
+    (None for a population solve, which selects nothing: the rows are the members)"""
     x: Optional[np.ndarray]
     fret: np.ndarray
     delta: np.ndarray
@@ -257,7 +266,7 @@ class StartsResult:
     status: np.ndarray
     nfeval: np.ndarray
     ngeval: np.ndarray
-    best: np.ndarray
+    best: Optional[np.ndarray] = None
 
     @property
     def exit_reason(self):
@@ -412,6 +421,75 @@ class Problem:
         return r
 
 
+class Population:
+    """rdis_hip_population: nmembers complete states X[nmembers, nvars] of one problem, resident on the device.  x: the members'
+    rows, or None: every member a copy of the problem's currently assigned x.  Plan.solve_population runs a plan on all of them."""
+
+    def __init__(self, prob: Problem, nmembers: Optional[int] = None, x=None):
+        self.prob, self.ctx = prob, prob.ctx
+        xs = None if x is None else _f(x)
+        if xs is not None:
+            if xs.ndim != 2 or xs.shape[1] != prob.nvars or (nmembers is not None and nmembers != xs.shape[0]):
+                raise ValueError("x must be [nmembers, nvars]")
+            nmembers = xs.shape[0]
+        if nmembers is None:
+            raise ValueError("nmembers or x is needed")
+        h = _vp()
+        self.ctx.check(self.ctx.lib.rdis_hip_population_create(prob.h, int(nmembers), _ptr(xs), C.byref(h)))
+        self._cell = _Cell(h, self.ctx.lib.rdis_hip_population_destroy, prob._cell)   # (closed before its problem)
+        self.nmembers, self.nvars = int(nmembers), prob.nvars
+        _register(self)
+
+    @property
+    def h(self):
+        return self._cell.h
+
+    def close(self):
+        if getattr(self, "_cell", None):
+            self._cell.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _range(self, first, count):
+        return int(first), int(self.nmembers - first if count is None else count)
+
+    def set_x(self, val, vid=None, first=0, count=None):
+        """members first .. first + count - 1 (default: to the last): val [count, n] at the variables vid (None: 0..n-1)"""
+        first, count = self._range(first, count)
+        vid = _i(vid)
+        val = _f(val)
+        val = val.reshape(count, -1) if val.ndim == 1 else val
+        if val.ndim != 2 or val.shape[0] != count or (vid is not None and vid.shape[0] != val.shape[1]):
+            raise ValueError("val must be [count, n]")
+        self.ctx.check(self.ctx.lib.rdis_hip_population_set_x(self.h, first, count, val.shape[1], _ptr(vid), _ptr(val)))
+
+    def get_x(self, member=None, vid=None, first=0, count=None) -> np.ndarray:
+        """member given: that member's values [n]; otherwise members first .. first + count - 1: [count, n]"""
+        if member is not None:
+            first, count = int(member), 1
+        first, count = self._range(first, count)
+        vid = _i(vid)
+        n = self.nvars if vid is None else vid.shape[0]
+        out = np.empty((max(count, 0), n))
+        self.ctx.check(self.ctx.lib.rdis_hip_population_get_x(self.h, first, count, n, _ptr(vid), _ptr(out)))
+        return out[0] if member is not None else out
+
+    def assign(self, member: int):
+        """the problem's assigned x := that member's x"""
+        self.ctx.check(self.ctx.lib.rdis_hip_population_assign(self.h, int(member)))
+
+    def eval(self, fac=None) -> np.ndarray:
+        """[nmembers]: per member what Problem.eval(fac) returns with that member's x assigned, bit for bit"""
+        fac, nf = self.prob._nf(fac)
+        f = np.empty(self.nmembers)
+        self.ctx.check(self.ctx.lib.rdis_hip_population_eval(self.h, nf, _ptr(fac), _ptr(f)))
+        return f
+
+
 class Comm:
     """rdis_hip_comm: the communicator of the path's one collective (the objective's all-reduce over RCCL / xGMI).
     One rank per process and GPU; `unique_id()` on rank 0, its 128 bytes to every rank, `Comm(ctx, world, rank, id)` on all."""
@@ -534,6 +612,24 @@ class Plan:
                          np.empty((ns, nc), np.int64), np.empty(nc, np.int32))
         self.ctx.check(self.ctx.lib.rdis_hip_plan_fetch_starts(self.h, _ptr(r.x), _ptr(r.fret), _ptr(r.delta), _ptr(r.iters),
                                                                _ptr(r.status), _ptr(r.nfeval), _ptr(r.ngeval), _ptr(r.best)))
+        return r
+
+    def solve_population(self, pop: "Population", maxiters=50, ftol=3e-8):
+        """every component on every member of pop in one launch (asynchronous): member s starts from its own x at the plan's free
+        variables, reads its constants from its own x and is left assigned to its result -- what set_start(None) + solve does on a
+        problem whose x is that member's.  The problem's x and the plan's ordinary outputs are not touched.  Bundle adjustment,
+        every component on the LDS-resident solver; anything else raises RdisHipError (EINVAL) with the cause"""
+        self.ctx.check(self.ctx.lib.rdis_hip_plan_solve_population(self.h, pop.h, maxiters, ftol))
+        self._nmembers = pop.nmembers
+
+    def fetch_population(self, want_x=True) -> StartsResult:
+        """the last population solve's results, member by member (best is None: nothing is selected)"""
+        ns, nc = getattr(self, "_nmembers", 0), self.ncomp
+        r = StartsResult(np.empty((ns, self.nfree)) if want_x else None, np.empty((ns, nc)), np.empty((ns, nc)),
+                         np.empty((ns, nc), np.int32), np.empty((ns, nc), np.int32), np.empty((ns, nc), np.int64),
+                         np.empty((ns, nc), np.int64), None)
+        self.ctx.check(self.ctx.lib.rdis_hip_plan_fetch_population(self.h, _ptr(r.x), _ptr(r.fret), _ptr(r.delta), _ptr(r.iters),
+                                                                   _ptr(r.status), _ptr(r.nfeval), _ptr(r.ngeval)))
         return r
 
     def objective(self) -> float:

@@ -1,0 +1,21 @@
+// population_api.hpp -- what rdis_hip.hip sees of the population entry of the LDS-resident solver (solver_lds_population.hpp),
+// whose kernels are a translation unit of their own (population_kernels.hip).  The per-solve arrays are the multi-start
+// entry's (starts_api.hpp: StartsView); the population itself is X[members][N], row-major.
+#pragma once
+#include "starts_api.hpp"
+
+namespace rdis_hip {
+
+// cgd_lds_population_kernel<threads, rot>: grid (ncomp_listed, members_of_launch); V.order lists the components; member
+// S.first + blockIdx.y reads its constants from X[S.first + blockIdx.y] and is assigned there
+hipError_t population_launch(int rot, int threads, int ncomp_listed, int members_of_launch, size_t dyn, hipStream_t stream, const ProblemView& P,
+                             const PlanView& V, const StartsView& S, double* X, int maxiters, double ftol, int ns_cap, int ncb_cap, int chunk_cap);
+// population_gather_kernel: xstart[s][nfree] = X[s][free_vid] for s < members
+hipError_t population_gather_launch(hipStream_t stream, const double* X, long long N, const int* free_vid, long long nfree, long long members, double* xstart);
+// population_scatter_kernel / population_pick_kernel: members first .. first + count - 1, n values each (vid null: variables 0 .. n-1)
+hipError_t population_scatter_launch(hipStream_t stream, double* X, long long N, long long first, long long count, const int* vid, long long n, const double* val);
+hipError_t population_pick_launch(hipStream_t stream, const double* X, long long N, long long first, long long count, const int* vid, long long n, double* out);
+// population_copy_rows_kernel: `rows` rows of dst, each a copy of src[N]
+hipError_t population_copy_rows_launch(hipStream_t stream, const double* src, double* dst, long long N, long long rows);
+
+}  // namespace rdis_hip

@@ -1,0 +1,58 @@
+// population_kernels.hip -- the population kernels of the LDS-resident solver (solver_lds_population.hpp) and their launches, a
+// translation unit of their own (rdis_hip.hip sees them through population_api.hpp).  A workgroup size becomes a template
+// argument through launch_dispatch.hpp, with the list of starts_kernels.hip: 64 ... 768, 1024 for everything else.
+#define RDIS_LDS_NO_LAUNCHER   // (cgd_lds_kernel is instantiated where it is launched: rdis_hip.hip, refround_kernels.hip)
+#include <algorithm>
+#include "solver_lds_population.hpp"
+#include "population_api.hpp"
+
+namespace rdis_hip {
+
+hipError_t population_launch(int rot, int threads, int ncomp_listed, int members_of_launch, size_t dyn, hipStream_t stream, const ProblemView& P,
+                             const PlanView& V, const StartsView& S, double* X, int maxiters, double ftol, int ns_cap, int ncb_cap, int chunk_cap) {
+    return with_threads<64, 128, 256, 512, 768, 1024>(threads, [&](auto T) {
+        auto* kernel = rot == ROT_CAMFIX ? cgd_lds_population_kernel<T.value, ROT_CAMFIX>
+                     : rot == ROT_RECORDS ? cgd_lds_population_kernel<T.value, ROT_RECORDS>
+                                          : cgd_lds_population_kernel<T.value, ROT_PER_FACTOR>;
+        if (dyn > 48 * 1024) {
+            hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+            if (e != hipSuccess) return e;
+        }
+        kernel<<<dim3((unsigned)ncomp_listed, (unsigned)members_of_launch), T.value, dyn, stream>>>(P, V, S, X, maxiters, ftol, ns_cap, ncb_cap, chunk_cap);
+        return hipGetLastError();
+    });
+}
+
+namespace {
+int helper_grid(long long total) { return (int)std::min<long long>((total + 255) / 256, 4096); }
+}  // namespace
+
+hipError_t population_gather_launch(hipStream_t stream, const double* X, long long N, const int* free_vid, long long nfree, long long members, double* xstart) {
+    const long long total = members * nfree;
+    if (total <= 0) return hipSuccess;
+    population_gather_kernel<<<helper_grid(total), 256, 0, stream>>>(X, N, free_vid, nfree, total, xstart);
+    return hipGetLastError();
+}
+
+hipError_t population_scatter_launch(hipStream_t stream, double* X, long long N, long long first, long long count, const int* vid, long long n, const double* val) {
+    const long long total = count * n;
+    if (total <= 0) return hipSuccess;
+    population_scatter_kernel<<<helper_grid(total), 256, 0, stream>>>(X, N, first, vid, n, total, val);
+    return hipGetLastError();
+}
+
+hipError_t population_pick_launch(hipStream_t stream, const double* X, long long N, long long first, long long count, const int* vid, long long n, double* out) {
+    const long long total = count * n;
+    if (total <= 0) return hipSuccess;
+    population_pick_kernel<<<helper_grid(total), 256, 0, stream>>>(X, N, first, vid, n, total, out);
+    return hipGetLastError();
+}
+
+hipError_t population_copy_rows_launch(hipStream_t stream, const double* src, double* dst, long long N, long long rows) {
+    const long long total = rows * N;
+    if (total <= 0) return hipSuccess;
+    population_copy_rows_kernel<<<helper_grid(total), 256, 0, stream>>>(src, dst, N, total);
+    return hipGetLastError();
+}
+
+}  // namespace rdis_hip

@@ -28,6 +28,7 @@
 #include "solver_lds.hpp"
 #include "ptm_api.hpp"
 #include "starts_api.hpp"
+#include "population_api.hpp"
 #include "solver_pipe.hpp"
 #include "solver_quad.hpp"
 #include "solver_stream.hpp"
@@ -362,6 +363,7 @@ struct rdis_hip_plan {
     hipEvent_t ms_stage_ev = nullptr;
     bool ms_stage_busy = false;
     int64_t ms_n = 0;                 // starts of the last multi-start solve (0: none to fetch)
+    bool ms_population = false;       // ... which was a population solve (rdis_hip_plan_solve_population: the members are the starts; no ms_best)
     int64_t ms_per_launch = 0, ms_launches = 0;
     ~rdis_hip_plan() { if (ms_stage_ev) (void)hipEventDestroy(ms_stage_ev); }
     // the outputs' block for n starts: xout[n][nfree] fret[n][nc] delta[n][nc] (f64) | nfeval[n][nc] ngeval[n][nc] (i64) | iters[n][nc] status[n][nc] (i32)
@@ -739,15 +741,14 @@ int refuse_exponential(rdis_hip_problem* p, int64_t nf, const int64_t* fac, cons
 }
 
 template <bool GRAD>
-int launch_eval_sum(rdis_hip_problem* p, int nf, const int* dfac, int blocks) {
+int launch_eval_sum(rdis_hip_problem* p, const ProblemView& V, int nf, const int* dfac, int blocks, double* out_dev) {
     rdis_hip_ctx* c = p->ctx;
-    ProblemView V = p->view();
     if (p->kind == KIND_BA)
         eval_sum_kernel<KIND_BA, GRAD><<<blocks, 256, 0, c->stream>>>(V, nf, dfac, p->gfac.as<double>(), p->partial.as<double>());
     else
         eval_sum_kernel<KIND_NLP, GRAD><<<blocks, 256, 0, c->stream>>>(V, nf, dfac, p->gfac.as<double>(), p->partial.as<double>());
     HIPCHK(c, hipGetLastError());
-    final_sum_kernel<<<1, 256, 0, c->stream>>>(blocks, p->partial.as<double>(), p->scalar.as<double>());
+    final_sum_kernel<<<1, 256, 0, c->stream>>>(blocks, p->partial.as<double>(), out_dev);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
@@ -1045,7 +1046,7 @@ int eval_grad_two_pass(rdis_hip_problem* p, int64_t nf, const int64_t* fac) {
     if ((rc = ensure(c, p->partial, (size_t)blocks * sizeof(double)))) return rc;
     if ((rc = ensure(c, p->gfac, (size_t)p->nslots() * sizeof(double)))) return rc;
     if ((rc = ensure(c, p->g_all, (size_t)p->N * sizeof(double)))) return rc;
-    if ((rc = launch_eval_sum<true>(p, (int)nf, dfac, blocks))) return rc;
+    if ((rc = launch_eval_sum<true>(p, p->view(), (int)nf, dfac, blocks, p->scalar.as<double>()))) return rc;
     gather_grad_kernel<<<grid_for(c, p->N, 256), 256, 0, c->stream>>>((int)p->N, dptr, didx, p->gfac.as<double>(), p->g_all.as<double>());
     HIPCHK(c, hipGetLastError());
     if (fac) HIPCHK(c, hipStreamSynchronize(c->stream));   // (lptr / lidx go out of scope)
@@ -1099,6 +1100,36 @@ int eval_grad_on_device(rdis_hip_problem* p, int64_t nf, const int64_t* fac) {
 
 }  // namespace
 
+namespace {
+// the value of the listed factors (dfac on the device, null: all) at x -- the problem's assigned x or a population member's --
+// enqueued on the context's stream; the result is one double at out_dev.  p->partial and, for a long bundle-adjustment list,
+// p->xrot are scratch of the call.
+int enqueue_eval(rdis_hip_problem* p, double* x, int64_t nf, const int* dfac, double* out_dev) {
+    rdis_hip_ctx* c = p->ctx;
+    int rc;
+    ProblemView V = p->view();
+    V.x = x;
+    if (fused_path(p)) {
+        // chunk by chunk, the chunks' sums added in a fixed order: the value rdis_hip_eval_grad returns, bit for bit
+        const int nchunks = (int)((nf + GRAD_LANES - 1) / GRAD_LANES);
+        if ((rc = ensure(c, p->partial, (size_t)nchunks * sizeof(double)))) return rc;
+        if (nf >= 4 * p->ncam_blocks) {   // a long list: the cameras' rotation records once per camera instead of once per factor (the same bits)
+            camera_rotations_kernel<<<(int)((p->ncam_blocks + 255) / 256), 256, 0, c->stream>>>(x, p->cam_blocks.as<int>(), (int)p->ncam_blocks,
+                                                                                                p->xrot.as<double>());
+            V.xrot = p->xrot.as<double>(); V.rot_mode = ROT_CAMFIX;
+        }
+        HIPCHK(c, eval_chunks_launch(c->stream, std::min(nchunks, 16 * std::max(1, c->num_cus)), V, (int)nf, dfac, p->partial.as<double>()));
+        final_sum_kernel<<<1, 256, 0, c->stream>>>(nchunks, p->partial.as<double>(), out_dev);
+        HIPCHK(c, hipGetLastError());
+    } else {
+        const int blocks = grid_for(c, nf, 256);
+        if ((rc = ensure(c, p->partial, (size_t)blocks * sizeof(double)))) return rc;
+        if ((rc = launch_eval_sum<false>(p, V, (int)nf, dfac, blocks, out_dev))) return rc;
+    }
+    return 0;
+}
+}  // namespace
+
 extern "C" int rdis_hip_eval(rdis_hip_problem* p, int64_t nf, const int64_t* fac, double* f) {
     if (!p || !f) return RDIS_HIP_EINVAL;
     rdis_hip_ctx* c = p->ctx;
@@ -1108,24 +1139,7 @@ extern "C" int rdis_hip_eval(rdis_hip_problem* p, int64_t nf, const int64_t* fac
     if (nf == 0) { *f = 0.0; return 0; }
     const int* dfac;
     if ((rc = stage_ids(p, nf, fac, p->F, &dfac))) return rc;
-    if (fused_path(p)) {
-        // chunk by chunk, the chunks' sums added in a fixed order: the value rdis_hip_eval_grad returns, bit for bit
-        const int nchunks = (int)((nf + GRAD_LANES - 1) / GRAD_LANES);
-        if ((rc = ensure(c, p->partial, (size_t)nchunks * sizeof(double)))) return rc;
-        ProblemView V = p->view();
-        if (nf >= 4 * p->ncam_blocks) {   // a long list: the cameras' rotation records once per camera instead of once per factor (the same bits)
-            camera_rotations_kernel<<<(int)((p->ncam_blocks + 255) / 256), 256, 0, c->stream>>>(p->x.as<double>(), p->cam_blocks.as<int>(), (int)p->ncam_blocks,
-                                                                                                p->xrot.as<double>());
-            V.xrot = p->xrot.as<double>(); V.rot_mode = ROT_CAMFIX;
-        }
-        HIPCHK(c, eval_chunks_launch(c->stream, std::min(nchunks, 16 * std::max(1, c->num_cus)), V, (int)nf, dfac, p->partial.as<double>()));
-        final_sum_kernel<<<1, 256, 0, c->stream>>>(nchunks, p->partial.as<double>(), p->scalar.as<double>());
-        HIPCHK(c, hipGetLastError());
-    } else {
-        const int blocks = grid_for(c, nf, 256);
-        if ((rc = ensure(c, p->partial, (size_t)blocks * sizeof(double)))) return rc;
-        if ((rc = launch_eval_sum<false>(p, (int)nf, dfac, blocks))) return rc;
-    }
+    if ((rc = enqueue_eval(p, p->x.as<double>(), nf, dfac, p->scalar.as<double>()))) return rc;
     HIPCHK(c, hipMemcpyAsync(f, p->scalar.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
@@ -2615,13 +2629,14 @@ constexpr int64_t STARTS_MAX_PER_LAUNCH = 65535;       // (the start is the grid
 
 // why a plan cannot be solved from many starts yet.  Two kinds of plan can: every component on the LDS-resident solver (bundle
 // adjustment), or a nonlinear-product problem with every component on the plain batch solver -- *plain_solver says which
-int starts_refusal(rdis_hip_plan* L, const char* who, bool* plain_solver) {
+// (entry: "multi-start" or "population" -- rdis_hip_plan_solve_population shares these checks)
+int starts_refusal(rdis_hip_plan* L, const char* who, bool* plain_solver, const char* entry = "multi-start") {
     rdis_hip_problem* p = L->prob;
     rdis_hip_ctx* c = p->ctx;
-    const std::string w(who);
+    const std::string w(who), en(entry);
     if (L->transient) return fail(c, RDIS_HIP_EINVAL, w + ": needs a persistent plan");
-    if (L->factor_rounding == 1) return fail(c, RDIS_HIP_EINVAL, w + ": the parity option (factor_rounding = 1) has no multi-start entry");
-    if (L->emulate_stale) return fail(c, RDIS_HIP_EINVAL, w + ": emulate_stale_cache has no multi-start entry");
+    if (L->factor_rounding == 1) return fail(c, RDIS_HIP_EINVAL, w + ": the parity option (factor_rounding = 1) has no " + en + " entry");
+    if (L->emulate_stale) return fail(c, RDIS_HIP_EINVAL, w + ": emulate_stale_cache has no " + en + " entry");
     if (L->trace_records > 0) return fail(c, RDIS_HIP_EINVAL, w + ": trace_records must be 0 (a trace belongs to one solve)");
     if (L->dump_iters > 0) return fail(c, RDIS_HIP_EINVAL, w + ": dump_iters must be 0 (a vector dump belongs to one solve)");
     if (L->partition_dirty || (!L->coop.empty() && L->coop_state_gen != p->coop_state_gen)) { int rc = prepare_partition(L); if (rc) return rc; }
@@ -2643,8 +2658,8 @@ int starts_refusal(rdis_hip_plan* L, const char* who, bool* plain_solver) {
     if (!plain_ok) note(plain, "plain batch solver");
     if (!others.empty()) {
         // (a bundle-adjustment component there reads its cameras' rotation records, ProblemView::xrot: they would need replicas too)
-        const char* ba_plain = plain > 0 && p->kind == KIND_BA ? " (bundle-adjustment components on the plain batch solver have no multi-start entry, alone or "
-                                                                 "beside LDS-resident ones: their rotation records would need replicas too)" : "";
+        const std::string ba_plain = plain > 0 && p->kind == KIND_BA ? " (bundle-adjustment components on the plain batch solver have no " + en + " entry, alone or "
+                                                                       "beside LDS-resident ones: their rotation records would need replicas too)" : "";
         return fail(c, RDIS_HIP_EINVAL, w + ": every component of the plan must run on the LDS-resident solver (bundle adjustment, variables fitting a "
                                         "compute unit's LDS) or, all of them, on the plain batch solver of a nonlinear-product problem; this plan sends" +
                                         others + ba_plain);
@@ -2667,7 +2682,7 @@ extern "C" int rdis_hip_plan_solve_starts(rdis_hip_plan* L, int64_t nstarts, con
     if (int rc = refuse_late_exponential(L, "plan_solve_starts")) return rc;
     bool plain = false;
     if (int rc = starts_refusal(L, "plan_solve_starts", &plain)) return rc;
-    if (L->ncomp == 0) { L->ms_n = nstarts; L->ms_per_launch = nstarts; L->ms_launches = 0; L->last_launches = 0; L->timed = false; return 0; }
+    if (L->ncomp == 0) { L->ms_population = false; L->ms_n = nstarts; L->ms_per_launch = nstarts; L->ms_launches = 0; L->last_launches = 0; L->timed = false; return 0; }
 
     // replicas of the per-solve workspace (ws, gfac; the plain solver's x and dir too) a launch may hold within the budget: at least one
     const size_t work_doubles = 5 * (size_t)L->nfree + (size_t)L->ngfac + (plain ? (size_t)p->N : 0), dir_doubles = plain ? (size_t)p->N : 0;
@@ -2686,6 +2701,7 @@ extern "C" int rdis_hip_plan_solve_starts(rdis_hip_plan* L, int64_t nstarts, con
     if (!rc && !L->ms_best.p) rc = plan_alloc(L, L->ms_best, (size_t)L->ncomp * sizeof(int));
     if (rc) return rc;
     L->ms_n = 0;   // (what an earlier call left is overwritten from here on)
+    L->ms_population = false;
 
     // the starts: through pinned memory, so that the caller may reuse x_starts the moment this returns and nothing waits
     if (in_bytes > 0 && in_bytes <= STARTS_STAGE_MAX_BYTES) {
@@ -2743,6 +2759,7 @@ extern "C" int rdis_hip_plan_fetch_starts(rdis_hip_plan* L, double* x_out, doubl
     rdis_hip_ctx* c = L->prob->ctx;
     USE_DEVICE(c);
     if (L->ms_n < 1) return fail(c, RDIS_HIP_EINVAL, "plan_fetch_starts: no multi-start solve to fetch (call rdis_hip_plan_solve_starts first)");
+    if (L->ms_population) return fail(c, RDIS_HIP_EINVAL, "plan_fetch_starts: the plan's last solve of this kind was a population solve (fetch it with rdis_hip_plan_fetch_population)");
     if (L->ncomp == 0) return 0;
     // every array is one contiguous piece of the outputs' block: straight into the caller's memory
     const StartsView S = L->starts_view(L->ms_n);
@@ -2758,6 +2775,215 @@ extern "C" int rdis_hip_plan_fetch_starts(rdis_hip_plan* L, double* x_out, doubl
     HIPCHK(c, get(iters, S.iters, sc * 4));
     HIPCHK(c, get(status, S.status, sc * 4));
     HIPCHK(c, get(best, L->ms_best.p, (size_t)L->ncomp * 4));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// =====================================================================================
+// populations: S complete states on the device, a plan solved on all of them at once (solver_lds_population.hpp)
+// =====================================================================================
+struct rdis_hip_population {
+    rdis_hip_problem* prob = nullptr;
+    int64_t nmembers = 0;
+    DevBuf X;                  // [nmembers][N]
+    DevBuf f;                  // [nmembers] values of the last population_eval
+    DevBuf tmp_val, tmp_out;   // staging of set_x / get_x
+    double* row(int64_t s) const { return X.as<double>() + (size_t)s * (size_t)prob->N; }
+};
+
+namespace {
+int population_range(rdis_hip_population* pop, const char* who, int64_t first, int64_t count, int64_t n, const int64_t* vid) {
+    rdis_hip_ctx* c = pop->prob->ctx;
+    const std::string w(who);
+    if (first < 0 || count < 0 || first > pop->nmembers || count > pop->nmembers - first) return fail(c, RDIS_HIP_EINVAL, w + ": members out of range");
+    if (!vid && n > pop->prob->N) return fail(c, RDIS_HIP_EINVAL, w + ": n > nvars");
+    if ((double)count * (double)n >= 9.0e15) return fail(c, RDIS_HIP_ERANGE, w + ": too many values");
+    return 0;
+}
+}  // namespace
+
+extern "C" int rdis_hip_population_create(rdis_hip_problem* p, int64_t nmembers, const double* x, rdis_hip_population** out) {
+    if (!p || !out) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = p->ctx;
+    USE_DEVICE(c);
+    if (nmembers < 1) return fail(c, RDIS_HIP_EINVAL, "population_create: nmembers must be at least 1");
+    if (nmembers >= (1ll << 31) || (double)nmembers * (double)std::max<int64_t>(p->N, 1) >= 9.0e15)
+        return fail(c, RDIS_HIP_ERANGE, "population_create: too many members");
+    rdis_hip_population* pop = new (std::nothrow) rdis_hip_population;
+    if (!pop) return fail(c, RDIS_HIP_ENOMEM, "population_create: host allocation");
+    pop->prob = p; pop->nmembers = nmembers;
+    const size_t bytes = (size_t)nmembers * (size_t)p->N * sizeof(double);
+    int rc = dalloc(c, pop->X, bytes);
+    if (!rc) rc = dalloc(c, pop->f, (size_t)nmembers * sizeof(double));
+    if (rc) { delete pop; return rc; }
+    hipError_t e = hipSuccess;
+    if (bytes > 0) {
+        if (x) e = hipMemcpyAsync(pop->X.p, x, bytes, hipMemcpyHostToDevice, c->stream);
+        else e = population_copy_rows_launch(c->stream, p->x.as<double>(), pop->X.as<double>(), p->N, nmembers);   // every member: the assigned x
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { delete pop; return fail(c, RDIS_HIP_EDEVICE, std::string("population_create: ") + hipGetErrorString(e)); }
+    *out = pop;
+    return 0;
+}
+
+extern "C" void rdis_hip_population_destroy(rdis_hip_population* pop) {
+    if (!pop) return;
+    if (pop->prob) { (void)make_current(pop->prob->ctx); (void)hipStreamSynchronize(pop->prob->ctx->stream); }
+    delete pop;
+}
+
+extern "C" int rdis_hip_population_set_x(rdis_hip_population* pop, int64_t first, int64_t count, int64_t n, const int64_t* vid, const double* val) {
+    if (!pop || n < 0 || (n && count > 0 && !val)) return RDIS_HIP_EINVAL;
+    rdis_hip_problem* p = pop->prob;
+    rdis_hip_ctx* c = p->ctx;
+    int rc = population_range(pop, "population_set_x", first, count, n, vid);
+    if (rc) return rc;
+    if (n == 0 || count == 0) return 0;
+    USE_DEVICE(c);
+    const size_t bytes = (size_t)count * (size_t)n * sizeof(double);
+    if (!vid && n == p->N) {   // whole rows: straight into place
+        HIPCHK(c, hipMemcpyAsync(pop->row(first), val, bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return 0;
+    }
+    const int* dv;
+    if ((rc = stage_ids(p, n, vid, p->N, &dv))) return rc;
+    if ((rc = ensure(c, pop->tmp_val, bytes))) return rc;
+    HIPCHK(c, hipMemcpyAsync(pop->tmp_val.p, val, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, population_scatter_launch(c->stream, pop->X.as<double>(), p->N, first, count, dv, n, pop->tmp_val.as<double>()));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int rdis_hip_population_get_x(rdis_hip_population* pop, int64_t first, int64_t count, int64_t n, const int64_t* vid, double* out) {
+    if (!pop || n < 0 || (n && count > 0 && !out)) return RDIS_HIP_EINVAL;
+    rdis_hip_problem* p = pop->prob;
+    rdis_hip_ctx* c = p->ctx;
+    int rc = population_range(pop, "population_get_x", first, count, n, vid);
+    if (rc) return rc;
+    if (n == 0 || count == 0) return 0;
+    USE_DEVICE(c);
+    const size_t bytes = (size_t)count * (size_t)n * sizeof(double);
+    if (!vid && n == p->N) {
+        HIPCHK(c, hipMemcpyAsync(out, pop->row(first), bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return 0;
+    }
+    const int* dv;
+    if ((rc = stage_ids(p, n, vid, p->N, &dv))) return rc;
+    if ((rc = ensure(c, pop->tmp_out, bytes))) return rc;
+    HIPCHK(c, population_pick_launch(c->stream, pop->X.as<double>(), p->N, first, count, dv, n, pop->tmp_out.as<double>()));
+    HIPCHK(c, hipMemcpyAsync(out, pop->tmp_out.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int rdis_hip_population_assign(rdis_hip_population* pop, int64_t member) {
+    if (!pop) return RDIS_HIP_EINVAL;
+    rdis_hip_problem* p = pop->prob;
+    rdis_hip_ctx* c = p->ctx;
+    if (member < 0 || member >= pop->nmembers) return fail(c, RDIS_HIP_EINVAL, "population_assign: member out of range");
+    USE_DEVICE(c);
+    HIPCHK(c, population_copy_rows_launch(c->stream, pop->row(member), p->x.as<double>(), p->N, 1));
+    return 0;
+}
+
+extern "C" int rdis_hip_population_eval(rdis_hip_population* pop, int64_t nf, const int64_t* fac, double* f) {
+    if (!pop || !f) return RDIS_HIP_EINVAL;
+    rdis_hip_problem* p = pop->prob;
+    rdis_hip_ctx* c = p->ctx;
+    int rc = check_list(p, nf, fac);
+    if (rc) return rc;
+    USE_DEVICE(c);
+    if (nf == 0) { std::fill(f, f + pop->nmembers, 0.0); return 0; }
+    const int* dfac;
+    if ((rc = stage_ids(p, nf, fac, p->F, &dfac))) return rc;
+    // member by member on the stream, rdis_hip_eval's kernels with the view's x replaced: no wait in between, one copy back
+    for (int64_t s = 0; s < pop->nmembers; ++s)
+        if ((rc = enqueue_eval(p, pop->row(s), nf, dfac, pop->f.as<double>() + s))) return rc;
+    HIPCHK(c, hipMemcpyAsync(f, pop->f.p, (size_t)pop->nmembers * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int rdis_hip_plan_solve_population(rdis_hip_plan* L, rdis_hip_population* pop, int32_t maxiters, double ftol) {
+    if (!L || !pop) return RDIS_HIP_EINVAL;
+    rdis_hip_problem* p = L->prob;
+    rdis_hip_ctx* c = p->ctx;
+    USE_DEVICE(c);
+    const int64_t S_n = pop->nmembers;
+    if (maxiters <= 0) return fail(c, RDIS_HIP_EINVAL, "plan_solve_population: maxiters must be positive");
+    if (pop->prob != p) return fail(c, RDIS_HIP_EINVAL, "plan_solve_population: the population belongs to another problem than the plan's");
+    if (p->kind != KIND_BA)
+        return fail(c, RDIS_HIP_EINVAL, "plan_solve_population: nonlinear-product plans have no population entry yet (bundle adjustment on the LDS-resident solver only)");
+    if (S_n >= (1ll << 31) || (double)S_n * (double)std::max<int64_t>(std::max(L->nfree, L->ncomp), 1) >= 9.0e15)
+        return fail(c, RDIS_HIP_ERANGE, "plan_solve_population: too many members");
+    bool plain = false;
+    if (int rc = starts_refusal(L, "plan_solve_population", &plain, "population")) return rc;
+    if (L->ncomp == 0) { L->ms_population = true; L->ms_n = S_n; L->ms_per_launch = S_n; L->ms_launches = 0; L->last_launches = 0; L->timed = false; return 0; }
+
+    // replicas of the per-solve workspace (ws, gfac) a launch may hold within the budget: the multi-start entry's rule
+    const size_t work_doubles = 5 * (size_t)L->nfree + (size_t)L->ngfac;
+    const size_t rep_bytes = work_doubles * sizeof(double);
+    int64_t R = rep_bytes ? std::max<int64_t>(1, L->starts_workspace_bytes / (int64_t)rep_bytes) : S_n;
+    R = std::min(std::min(R, S_n), STARTS_MAX_PER_LAUNCH);
+    int rc = 0;
+    if (L->ms_work.bytes < (size_t)R * work_doubles * sizeof(double)) rc = plan_alloc(L, L->ms_work, (size_t)R * work_doubles * sizeof(double));
+    const size_t in_bytes = (size_t)S_n * (size_t)L->nfree * sizeof(double);
+    if (!rc && L->ms_in.bytes < in_bytes) rc = plan_alloc(L, L->ms_in, in_bytes);
+    if (!rc && L->ms_out.bytes < L->ms_out_bytes(S_n)) rc = plan_alloc(L, L->ms_out, L->ms_out_bytes(S_n));
+    if (rc) return rc;
+    L->ms_n = 0;   // (what an earlier call left is overwritten from here on)
+
+    const ProblemView P = p->view();
+    PlanView V = L->view();   // (order: the whole batch list -- empty components and those of the LDS-resident solver, heaviest first)
+    StartsView S = L->starts_view(S_n);
+    S.gfac = S.ws + (size_t)R * 5 * (size_t)L->nfree;
+    // every member's start row: its own x at the plan's free variables (plan_set_start(plan, NULL) on that x)
+    HIPCHK(c, population_gather_launch(c->stream, pop->X.as<double>(), p->N, V.free_vid, L->nfree, S_n, L->ms_in.as<double>()));
+    const int threads = L->rest_lds > 0 ? lds_launch_threads(L) : 64;
+    const size_t dyn = L->lds_dyn_bytes(c);
+    L->last_launches = 0;
+    L->timed = false;
+    HIPCHK(c, hipEventRecord(p->ev0, c->stream));
+    for (int64_t first = 0; first < S_n; first += R) {   // (launches on one stream: the next takes the replicas when this one is done)
+        S.first = first;
+        const int ns = (int)std::min(R, S_n - first);
+        HIPCHK(c, population_launch(L->lds_rot_mode, threads, (int)L->h_rest.size(), ns, dyn, c->stream, P, V, S, pop->X.as<double>(),
+                                    maxiters, ftol, L->lds_ns_cap, L->lds_ncb_cap, L->lds_chunk_cap));
+        ++L->last_launches;
+    }
+    HIPCHK(c, hipEventRecord(p->ev1, c->stream));
+    L->timed = true;
+    p->last_timed_plan = L;
+    L->ms_population = true;
+    L->ms_n = S_n;
+    L->ms_per_launch = R;
+    L->ms_launches = L->last_launches;
+    return 0;
+}
+
+extern "C" int rdis_hip_plan_fetch_population(rdis_hip_plan* L, double* x_out, double* fret, double* delta, int32_t* iters, int32_t* status,
+                                              int64_t* nfeval, int64_t* ngeval) {
+    if (!L) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = L->prob->ctx;
+    USE_DEVICE(c);
+    if (L->ms_n < 1) return fail(c, RDIS_HIP_EINVAL, "plan_fetch_population: no population solve to fetch (call rdis_hip_plan_solve_population first)");
+    if (!L->ms_population) return fail(c, RDIS_HIP_EINVAL, "plan_fetch_population: the plan's last solve of this kind was a multi-start solve (fetch it with rdis_hip_plan_fetch_starts)");
+    if (L->ncomp == 0) return 0;
+    const StartsView S = L->starts_view(L->ms_n);
+    const size_t sn = (size_t)L->ms_n * (size_t)L->nfree, sc = (size_t)L->ms_n * (size_t)L->ncomp;
+    auto get = [&](void* dst, const void* src, size_t bytes) {
+        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    HIPCHK(c, get(x_out, S.xout, sn * 8));
+    HIPCHK(c, get(fret, S.fret, sc * 8));
+    HIPCHK(c, get(delta, S.delta, sc * 8));
+    HIPCHK(c, get(nfeval, S.nfeval, sc * 8));
+    HIPCHK(c, get(ngeval, S.ngeval, sc * 8));
+    HIPCHK(c, get(iters, S.iters, sc * 4));
+    HIPCHK(c, get(status, S.status, sc * 4));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

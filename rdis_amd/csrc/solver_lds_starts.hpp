@@ -21,20 +21,7 @@
 
 namespace rdis_hip {
 
-// the view of start (S.first + r), replica r of the launch
-__device__ __forceinline__ PlanView starts_shift(PlanView L, const StartsView& S, int r) {
-    const long long s = S.first + r;
-    L.xstart = S.xstart + s * S.nfree;
-    L.xout = S.xout + s * S.nfree;
-    L.fret = S.fret + s * L.ncomp; L.delta = S.delta + s * L.ncomp;
-    L.iters = S.iters + s * L.ncomp; L.status = S.status + s * L.ncomp;
-    L.nfeval = S.nfeval + s * L.ncomp; L.ngeval = S.ngeval + s * L.ncomp;
-    L.ws = S.ws + (long long)r * 5 * S.nfree;
-    L.gfac = S.gfac + (long long)r * S.ngfac;
-    L.trace = nullptr; L.trace_n = nullptr; L.trace_cap = 0;
-    L.vdump = nullptr; L.dump_iters = 0;
-    return L;
-}
+// (starts_shift, the view of start S.first + r on replica r of the launch: starts_api.hpp -- solver_lds_population.hpp shifts alike)
 
 template <int THREADS, int ROT>
 __global__ void __launch_bounds__(THREADS, (THREADS <= 256 ? 2 : 1))

@@ -30,6 +30,21 @@ struct StartsView {
 
 namespace rdis_hip {
 
+// the view of start (S.first + r), replica r of the launch
+__device__ __forceinline__ PlanView starts_shift(PlanView L, const StartsView& S, int r) {
+    const long long s = S.first + r;
+    L.xstart = S.xstart + s * S.nfree;
+    L.xout = S.xout + s * S.nfree;
+    L.fret = S.fret + s * L.ncomp; L.delta = S.delta + s * L.ncomp;
+    L.iters = S.iters + s * L.ncomp; L.status = S.status + s * L.ncomp;
+    L.nfeval = S.nfeval + s * L.ncomp; L.ngeval = S.ngeval + s * L.ncomp;
+    L.ws = S.ws + (long long)r * 5 * S.nfree;
+    L.gfac = S.gfac + (long long)r * S.ngfac;
+    L.trace = nullptr; L.trace_n = nullptr; L.trace_cap = 0;
+    L.vdump = nullptr; L.dump_iters = 0;
+    return L;
+}
+
 // cgd_lds_starts_kernel<threads, rot>: grid (ncomp_listed, nstarts_of_launch); V.order lists the components
 hipError_t starts_launch(int rot, int threads, int ncomp_listed, int nstarts_of_launch, size_t dyn, hipStream_t stream, const ProblemView& P,
                          const PlanView& V, const StartsView& S, int maxiters, double ftol, int ns_cap, int ncb_cap, int chunk_cap);

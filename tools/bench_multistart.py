@@ -2,13 +2,16 @@
 """Multi-start solves measured: rdis_hip_plan_solve_starts against the same starts solved one by one.
 
   python tools/bench_multistart.py            # both steps, one JSON line
-  python tools/bench_multistart.py --step config3|config5s|config2   # one step, in this process
+  python tools/bench_multistart.py --step config3|config5s|config2|population   # one step, in this process
 
 config3   BASELINE config 3 (ladybug 5 cameras / 30 points, one component): 320 one-ulp starts -- those of the end-value fixture,
           tests/golden/end_values.json -- in one call, and the same 320 by set_start / solve / fetch on the same plan.
 config5s  BASELINE config 5-S (1000 components of 3 cameras x 40 points) x 8 starts, likewise.
 config2   BASELINE config 2 (the 121-variable sinusoid, one component on the plain solver: one workgroup of 512 lanes a solve) from
           1024 starts drawn uniformly in the domains (seed 2), likewise.
+population  ladybug 5 / 30, 256 members drawn from the sampling intervals (examples/ba_multistart.py), one alternation round -- camera
+          plan, then point plan -- as two population launches (rdis_hip_plan_solve_population), against the same round member by
+          member through set_x / set_start(None) / solve / get_x on the problem: the baseline is the way without populations.
 Every step runs in a child process under a time limit of its own; a step that fails ends the run.  Wall times are the median of
 `--repeats` calls after one warm-up call; kernel_ms is rdis_hip_plan_last_kernel_ms of the last call."""
 import argparse
@@ -23,8 +26,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-STEP_LIMIT_S = {"config3": 240, "config5s": 240, "config2": 240}
-STEPS = ("config3", "config5s", "config2")
+STEP_LIMIT_S = {"config3": 240, "config5s": 240, "config2": 240, "population": 240}
+STEPS = ("config3", "config5s", "config2", "population")
 
 
 def ulp_perturbed(x0, rng):
@@ -79,8 +82,77 @@ def measure(pp, starts, repeats):
             "device_bytes": plan.device_bytes()}
 
 
+def measure_population(repeats, members=256):
+    """one alternation round on a population against the same round member by member on the problem"""
+    from rdis_amd import capi, problems as P
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    from ba_multistart import sampling_intervals
+    pp = P.load_bal(ncams=5, npts=30)
+    cams, pts = P.ba_alternation_plans(pp)
+    lo, hi = sampling_intervals(pp)
+    X = np.random.default_rng(0).uniform(lo, hi, size=(members, pp.nvars))
+    ctx = capi.Context(0)
+    g = capi.Problem(ctx, pp)
+    plans = [capi.Plan(g, *cams), capi.Plan(g, *pts)]
+    assert all(p.info("components_lds") == p.ncomp for p in plans)
+    pop = capi.Population(g, members)
+
+    def together():
+        pop.set_x(X)
+        t = time.perf_counter()
+        for plan in plans:
+            plan.solve_population(pop, 25, 3e-8)
+        ctx.synchronize()
+        return time.perf_counter() - t, pop.get_x()
+
+    def kernel_times():   # (the problem's timing events belong to its last solve: read after each launch, outside the timed round)
+        pop.set_x(X)
+        out = []
+        for plan in plans:
+            plan.solve_population(pop, 25, 3e-8)
+            out.append(plan.last_kernel_ms())
+        return [ms for ms, _ in out], sum(n for _, n in out)
+
+    def one_by_one():
+        out = np.empty_like(X)
+        t = time.perf_counter()
+        for s in range(members):
+            g.set_x(X[s])
+            for plan in plans:
+                plan.set_start(None)
+                plan.solve(25, 3e-8)
+            out[s] = g.get_x()
+        return time.perf_counter() - t, out
+
+    g.set_x(X[0]); plans[1].set_start(None); plans[1].solve(25, 3e-8); plans[1].fetch()
+    single_ms = plans[1].last_kernel_ms()[0]
+    together()
+    tt = []
+    for _ in range(repeats):
+        dt, xt = together()
+        tt.append(dt)
+    kernel_ms, launches = kernel_times()
+    one_by_one()
+    ts = []
+    for _ in range(repeats):
+        dt, xs = one_by_one()
+        ts.append(dt)
+    f = pop.eval()
+    wall, seq = float(np.median(tt)), float(np.median(ts))
+    return {"members": members, "camera_components": plans[0].ncomp, "point_components": plans[1].ncomp,
+            "members_per_launch": plans[1].info("starts_per_launch"), "launches_per_round": 2,
+            "wall_ms": 1e3 * wall, "sequential_wall_ms": 1e3 * seq, "speedup": seq / wall,
+            "last_kernel_ms": kernel_ms, "last_kernel_launches": launches, "one_member_point_solve_kernel_ms": single_ms,
+            "point_kernel_in_single_solves": kernel_ms[1] / single_ms,
+            "bits_equal_sequential": bool(xt.tobytes() == xs.tobytes()), "finite_members": int(np.sum(np.isfinite(f))),
+            "best_f": float(np.nanmin(f)) if np.any(np.isfinite(f)) else None,
+            "device_bytes": [p.device_bytes() for p in plans]}
+
+
 def step(name, repeats):
     from rdis_amd import problems as P
+    if name == "population":
+        return measure_population(repeats)
     if name == "config3":
         with open(os.path.join(ROOT, "tests", "golden", "end_values.json")) as fh:
             seed = json.load(fh)["seed"]
