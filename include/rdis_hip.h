@@ -273,7 +273,8 @@ int rdis_hip_plan_fetch_starts(rdis_hip_plan *plan, double *x_out, double *fret,
  * shared by all starts -- cannot express.  A population holds X[nmembers][N] on the device, every member a complete
  * assignment of the problem's variables; plan_solve_population runs a plan on all members in one launch, member s taking
  * both its start and its constants from X[s] and leaving its result there, so that the next plan (the other variables
- * free) follows with no host traffic (rdis_amd/csrc/solver_lds_population.hpp).
+ * free) follows with no host traffic (rdis_amd/csrc/solver_lds_population.hpp; nonlinear-product plans, with the plan
+ * option "population_plain": solver_wg_population.hpp).
  *   population_create   allocates X; x[nmembers][N] row-major, or NULL: every member a copy of the problem's currently
  *                       assigned x.  nmembers >= 1 (RDIS_HIP_EINVAL), below 2^31 and nmembers * N below 9e15
  *                       (RDIS_HIP_ERANGE).  Both problem kinds.  A population belongs to one problem and is destroyed
@@ -299,14 +300,18 @@ int rdis_hip_plan_fetch_starts(rdis_hip_plan *plan, double *x_out, double *fret,
  *                       plan_solve_starts on the plan, whose buffers they share: plan_fetch_starts after a population
  *                       solve, and plan_fetch_population after a multi-start solve or before any, return RDIS_HIP_EINVAL.
  * Workspace: the replicas of the multi-start entry on the LDS-resident solver (5 doubles per free variable and one per
- * partial, per member of a launch), bounded by the plan option "starts_workspace_bytes" with the same splitting into
- * launches of R members (plan_get_info "starts_per_launch" / "starts_launches"), counted by plan_device_bytes;
- * plan_last_kernel_ms covers the solver launches.
+ * partial, per member of a launch; on the plain batch solver also a search direction of the problem's size, N doubles,
+ * but no copy of x: that solver's trial points go into the member's own row X[s], which the independence of the
+ * components allows just as it allows the result), bounded by the plan option "starts_workspace_bytes" with the same
+ * splitting into launches of R members (plan_get_info "starts_per_launch" / "starts_launches"), counted by
+ * plan_device_bytes; plan_last_kernel_ms covers the solver launches.
  * Scope: a bundle-adjustment problem, every non-empty component of the plan on the LDS-resident solver (plan_get_info
- * "components_lds"); a persistent plan; default factor_rounding; emulate_stale_cache, trace_records and dump_iters off; the
- * population must be the plan's problem's.  Not yet: the other solvers, nonlinear-product plans (create, set_x, get_x,
- * assign and eval do work for that kind).  Anything else: RDIS_HIP_EINVAL and a message that names the cause; the plan and
- * the population stay usable. */
+ * "components_lds"); or, with the plan option "population_plain" = 1 (default 0: refused, as before the option existed), a
+ * nonlinear-product problem with every non-empty component on the plain batch solver ("components_plain": BASELINE
+ * configs 1 and 2, every decomposition of the sinusoid) -- the option has no effect on bundle-adjustment plans.  A
+ * persistent plan; default factor_rounding; emulate_stale_cache, trace_records and dump_iters off; the population must be
+ * the plan's problem's.  Not yet: the other solvers; bundle-adjustment components on the plain batch solver.  Anything
+ * else: RDIS_HIP_EINVAL and a message that names the cause; the plan and the population stay usable. */
 typedef struct rdis_hip_population rdis_hip_population;
 int rdis_hip_population_create(rdis_hip_problem *p, int64_t nmembers, const double *x, rdis_hip_population **out);
 void rdis_hip_population_destroy(rdis_hip_population *pop);
@@ -427,7 +432,10 @@ int rdis_hip_comm_allreduce_f64(rdis_hip_comm *comm, double *inout, int32_t n, i
  * it was computed -- emulated in the LDS-resident batch solver and, with factor_rounding = 1, in the cooperative solver's plain
  * layout; refused where other solvers would run),
  * "starts_workspace_bytes" (default 1 GiB: device memory the workspace replicas of a multi-start launch may take,
- * rdis_hip_plan_solve_starts),
+ * rdis_hip_plan_solve_starts, and of a population launch, rdis_hip_plan_solve_population),
+ * "population_plain" (default 0; 1 = rdis_hip_plan_solve_population accepts a nonlinear-product plan whose components all
+ * run on the plain batch solver, one workgroup per (component, member) working in the member's own x; 0 = such a plan is
+ * refused with RDIS_HIP_EINVAL; no effect on bundle-adjustment plans or on any other entry),
  * "trace_records" (per-component trace capacity, 0 = off), "dump_iters" (record p and
  * the search direction at the start of the first k line minimisations, 0 = off). */
 int rdis_hip_plan_set_option(rdis_hip_plan *plan, const char *name, int64_t value);

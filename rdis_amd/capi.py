@@ -618,7 +618,10 @@ class Plan:
         """every component on every member of pop in one launch (asynchronous): member s starts from its own x at the plan's free
         variables, reads its constants from its own x and is left assigned to its result -- what set_start(None) + solve does on a
         problem whose x is that member's.  The problem's x and the plan's ordinary outputs are not touched.  Bundle adjustment,
-        every component on the LDS-resident solver; anything else raises RdisHipError (EINVAL) with the cause"""
+        every component on the LDS-resident solver; or, after set_option("population_plain", 1), a nonlinear-product problem with
+        every component on the plain batch solver (info("components_plain")), whose trial points go into the member's own row
+        during the launch; anything else -- a nonlinear-product plan without that option included -- raises RdisHipError (EINVAL)
+        with the cause"""
         self.ctx.check(self.ctx.lib.rdis_hip_plan_solve_population(self.h, pop.h, maxiters, ftol))
         self._nmembers = pop.nmembers
 

@@ -1,5 +1,5 @@
-// population_api.hpp -- what rdis_hip.hip sees of the population entry of the LDS-resident solver (solver_lds_population.hpp),
-// whose kernels are a translation unit of their own (population_kernels.hip).  The per-solve arrays are the multi-start
+// population_api.hpp -- what rdis_hip.hip sees of the population entries of the LDS-resident solver (solver_lds_population.hpp)
+// and of the plain one-workgroup solver (solver_wg_population.hpp), whose kernels are a translation unit of their own (population_kernels.hip).  The per-solve arrays are the multi-start
 // entry's (starts_api.hpp: StartsView); the population itself is X[members][N], row-major.
 #pragma once
 #include "starts_api.hpp"
@@ -10,6 +10,10 @@ namespace rdis_hip {
 // S.first + blockIdx.y reads its constants from X[S.first + blockIdx.y] and is assigned there
 hipError_t population_launch(int rot, int threads, int ncomp_listed, int members_of_launch, size_t dyn, hipStream_t stream, const ProblemView& P,
                              const PlanView& V, const StartsView& S, double* X, int maxiters, double ftol, int ns_cap, int ncb_cap, int chunk_cap);
+// cgd_wg_population_kernel<KIND_NLP, threads>: the plain solver's, same grid; the member's row of X carries its trial points too,
+// S.dir holds the launch's replicas of dir (S.x is not used: no replica of x)
+hipError_t population_launch_wg(int threads, int ncomp_listed, int members_of_launch, hipStream_t stream, const ProblemView& P, const PlanView& V,
+                                const StartsView& S, double* X, int maxiters, double ftol);
 // population_gather_kernel: xstart[s][nfree] = X[s][free_vid] for s < members
 hipError_t population_gather_launch(hipStream_t stream, const double* X, long long N, const int* free_vid, long long nfree, long long members, double* xstart);
 // population_scatter_kernel / population_pick_kernel: members first .. first + count - 1, n values each (vid null: variables 0 .. n-1)

@@ -1,9 +1,11 @@
-// population_kernels.hip -- the population kernels of the LDS-resident solver (solver_lds_population.hpp) and their launches, a
+// population_kernels.hip -- the population kernels of the LDS-resident solver (solver_lds_population.hpp) and of the plain
+// one-workgroup solver (solver_wg_population.hpp) and their launches, a
 // translation unit of their own (rdis_hip.hip sees them through population_api.hpp).  A workgroup size becomes a template
 // argument through launch_dispatch.hpp, with the list of starts_kernels.hip: 64 ... 768, 1024 for everything else.
 #define RDIS_LDS_NO_LAUNCHER   // (cgd_lds_kernel is instantiated where it is launched: rdis_hip.hip, refround_kernels.hip)
 #include <algorithm>
 #include "solver_lds_population.hpp"
+#include "solver_wg_population.hpp"
 #include "population_api.hpp"
 
 namespace rdis_hip {
@@ -19,6 +21,15 @@ hipError_t population_launch(int rot, int threads, int ncomp_listed, int members
             if (e != hipSuccess) return e;
         }
         kernel<<<dim3((unsigned)ncomp_listed, (unsigned)members_of_launch), T.value, dyn, stream>>>(P, V, S, X, maxiters, ftol, ns_cap, ncb_cap, chunk_cap);
+        return hipGetLastError();
+    });
+}
+
+// (the list of cgd_wg_kernel's launch, rdis_hip.hip launch_wg: a sum's tree depends on the workgroup size)
+hipError_t population_launch_wg(int threads, int ncomp_listed, int members_of_launch, hipStream_t stream, const ProblemView& P, const PlanView& V,
+                                const StartsView& S, double* X, int maxiters, double ftol) {
+    return with_threads<64, 128, 256, 512, 768, 1024>(threads, [&](auto T) {
+        cgd_wg_population_kernel<KIND_NLP, T.value><<<dim3((unsigned)ncomp_listed, (unsigned)members_of_launch), T.value, 0, stream>>>(P, V, S, X, maxiters, ftol);
         return hipGetLastError();
     });
 }

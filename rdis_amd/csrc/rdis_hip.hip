@@ -365,6 +365,7 @@ struct rdis_hip_plan {
     int64_t ms_n = 0;                 // starts of the last multi-start solve (0: none to fetch)
     bool ms_population = false;       // ... which was a population solve (rdis_hip_plan_solve_population: the members are the starts; no ms_best)
     int64_t ms_per_launch = 0, ms_launches = 0;
+    int population_plain = 0;         // option "population_plain": 1 = rdis_hip_plan_solve_population takes a nonlinear-product plan on the plain batch solver (solver_wg_population.hpp)
     ~rdis_hip_plan() { if (ms_stage_ev) (void)hipEventDestroy(ms_stage_ev); }
     // the outputs' block for n starts: xout[n][nfree] fret[n][nc] delta[n][nc] (f64) | nfeval[n][nc] ngeval[n][nc] (i64) | iters[n][nc] status[n][nc] (i32)
     size_t ms_out_bytes(int64_t n) const { return (size_t)n * ((size_t)nfree * 8 + (size_t)ncomp * 40); }
@@ -1631,6 +1632,9 @@ extern "C" int rdis_hip_plan_set_option(rdis_hip_plan* L, const char* name, int6
         // (the bound holds from now on: replicas beyond it go; releasing device memory waits for the work that uses it)
         if (L->ms_work.p && L->ms_work.bytes > (size_t)value) { L->dev_bytes -= std::min(L->dev_bytes, L->ms_work.bytes); L->ms_work.release(); }
         return 0;   // (no table depends on it)
+    } else if (n == "population_plain") {
+        L->population_plain = value != 0;
+        return 0;   // (no table depends on it)
     } else if (n == "trace_records") {
         if (value < 0 || value > (1 << 22)) return fail(c, RDIS_HIP_EINVAL, "trace_records out of range");
         if (L->transient && value) return fail(c, RDIS_HIP_EINVAL, "tracing needs a persistent plan");
@@ -2780,7 +2784,8 @@ extern "C" int rdis_hip_plan_fetch_starts(rdis_hip_plan* L, double* x_out, doubl
 }
 
 // =====================================================================================
-// populations: S complete states on the device, a plan solved on all of them at once (solver_lds_population.hpp)
+// populations: S complete states on the device, a plan solved on all of them at once (solver_lds_population.hpp; with the plan
+// option population_plain, solver_wg_population.hpp for nonlinear-product plans)
 // =====================================================================================
 struct rdis_hip_population {
     rdis_hip_problem* prob = nullptr;
@@ -2915,21 +2920,28 @@ extern "C" int rdis_hip_plan_solve_population(rdis_hip_plan* L, rdis_hip_populat
     const int64_t S_n = pop->nmembers;
     if (maxiters <= 0) return fail(c, RDIS_HIP_EINVAL, "plan_solve_population: maxiters must be positive");
     if (pop->prob != p) return fail(c, RDIS_HIP_EINVAL, "plan_solve_population: the population belongs to another problem than the plan's");
-    if (p->kind != KIND_BA)
-        return fail(c, RDIS_HIP_EINVAL, "plan_solve_population: nonlinear-product plans have no population entry yet (bundle adjustment on the LDS-resident solver only)");
+    if (p->kind != KIND_BA && !L->population_plain)
+        return fail(c, RDIS_HIP_EINVAL, "plan_solve_population: nonlinear-product plans are solved on a population only with the plan option population_plain = 1 "
+                                        "(the plain batch solver, solver_wg_population.hpp; without it: bundle adjustment on the LDS-resident solver only)");
     if (S_n >= (1ll << 31) || (double)S_n * (double)std::max<int64_t>(std::max(L->nfree, L->ncomp), 1) >= 9.0e15)
         return fail(c, RDIS_HIP_ERANGE, "plan_solve_population: too many members");
+    if (int rc = refuse_late_exponential(L, "plan_solve_population")) return rc;   // (nonlinear products only: no bundle-adjustment factor is exponential)
     bool plain = false;
     if (int rc = starts_refusal(L, "plan_solve_population", &plain, "population")) return rc;
     if (L->ncomp == 0) { L->ms_population = true; L->ms_n = S_n; L->ms_per_launch = S_n; L->ms_launches = 0; L->last_launches = 0; L->timed = false; return 0; }
 
-    // replicas of the per-solve workspace (ws, gfac) a launch may hold within the budget: the multi-start entry's rule
-    const size_t work_doubles = 5 * (size_t)L->nfree + (size_t)L->ngfac;
-    const size_t rep_bytes = work_doubles * sizeof(double);
+    // replicas of the per-solve workspace (ws, gfac; the plain solver's dir too -- its x is the member's row) a launch may hold
+    // within the budget: the multi-start entry's rule
+    const size_t work_doubles = 5 * (size_t)L->nfree + (size_t)L->ngfac, dir_doubles = plain ? (size_t)p->N : 0;
+    const size_t rep_bytes = (work_doubles + dir_doubles) * sizeof(double);
     int64_t R = rep_bytes ? std::max<int64_t>(1, L->starts_workspace_bytes / (int64_t)rep_bytes) : S_n;
     R = std::min(std::min(R, S_n), STARTS_MAX_PER_LAUNCH);
     int rc = 0;
     if (L->ms_work.bytes < (size_t)R * work_doubles * sizeof(double)) rc = plan_alloc(L, L->ms_work, (size_t)R * work_doubles * sizeof(double));
+    if (!rc && plain && L->ms_dir.bytes < (size_t)R * dir_doubles * sizeof(double)) {
+        rc = plan_alloc(L, L->ms_dir, (size_t)R * dir_doubles * sizeof(double));
+        if (!rc) HIPCHK(c, hipMemsetAsync(L->ms_dir.p, 0, L->ms_dir.bytes, c->stream));   // (the kernel leaves what it wrote zero again)
+    }
     const size_t in_bytes = (size_t)S_n * (size_t)L->nfree * sizeof(double);
     if (!rc && L->ms_in.bytes < in_bytes) rc = plan_alloc(L, L->ms_in, in_bytes);
     if (!rc && L->ms_out.bytes < L->ms_out_bytes(S_n)) rc = plan_alloc(L, L->ms_out, L->ms_out_bytes(S_n));
@@ -2937,12 +2949,13 @@ extern "C" int rdis_hip_plan_solve_population(rdis_hip_plan* L, rdis_hip_populat
     L->ms_n = 0;   // (what an earlier call left is overwritten from here on)
 
     const ProblemView P = p->view();
-    PlanView V = L->view();   // (order: the whole batch list -- empty components and those of the LDS-resident solver, heaviest first)
+    PlanView V = L->view();   // (order: the whole batch list -- empty components and those of the plan's one solver, heaviest first)
     StartsView S = L->starts_view(S_n);
     S.gfac = S.ws + (size_t)R * 5 * (size_t)L->nfree;
+    if (plain) S.dir = L->ms_dir.as<double>();   // (no replica of x: the member's row serves, solver_wg_population.hpp)
     // every member's start row: its own x at the plan's free variables (plan_set_start(plan, NULL) on that x)
     HIPCHK(c, population_gather_launch(c->stream, pop->X.as<double>(), p->N, V.free_vid, L->nfree, S_n, L->ms_in.as<double>()));
-    const int threads = L->rest_lds > 0 ? lds_launch_threads(L) : 64;
+    const int threads = plain ? wg_launch_threads(L) : L->rest_lds > 0 ? lds_launch_threads(L) : 64;
     const size_t dyn = L->lds_dyn_bytes(c);
     L->last_launches = 0;
     L->timed = false;
@@ -2950,7 +2963,8 @@ extern "C" int rdis_hip_plan_solve_population(rdis_hip_plan* L, rdis_hip_populat
     for (int64_t first = 0; first < S_n; first += R) {   // (launches on one stream: the next takes the replicas when this one is done)
         S.first = first;
         const int ns = (int)std::min(R, S_n - first);
-        HIPCHK(c, population_launch(L->lds_rot_mode, threads, (int)L->h_rest.size(), ns, dyn, c->stream, P, V, S, pop->X.as<double>(),
+        if (plain) HIPCHK(c, population_launch_wg(threads, (int)L->h_rest.size(), ns, c->stream, P, V, S, pop->X.as<double>(), maxiters, ftol));
+        else HIPCHK(c, population_launch(L->lds_rot_mode, threads, (int)L->h_rest.size(), ns, dyn, c->stream, P, V, S, pop->X.as<double>(),
                                     maxiters, ftol, L->lds_ns_cap, L->lds_ncb_cap, L->lds_chunk_cap));
         ++L->last_launches;
     }

@@ -2,7 +2,7 @@
 """Multi-start solves measured: rdis_hip_plan_solve_starts against the same starts solved one by one.
 
   python tools/bench_multistart.py            # both steps, one JSON line
-  python tools/bench_multistart.py --step config3|config5s|config2|population   # one step, in this process
+  python tools/bench_multistart.py --step config3|config5s|config2|population|population-nlp   # one step, in this process
 
 config3   BASELINE config 3 (ladybug 5 cameras / 30 points, one component): 320 one-ulp starts -- those of the end-value fixture,
           tests/golden/end_values.json -- in one call, and the same 320 by set_start / solve / fetch on the same plan.
@@ -12,6 +12,10 @@ config2   BASELINE config 2 (the 121-variable sinusoid, one component on the pla
 population  ladybug 5 / 30, 256 members drawn from the sampling intervals (examples/ba_multistart.py), one alternation round -- camera
           plan, then point plan -- as two population launches (rdis_hip_plan_solve_population), against the same round member by
           member through set_x / set_start(None) / solve / get_x on the problem: the baseline is the way without populations.
+population-nlp  the 121-variable sinusoid, 256 members drawn uniformly in the domains (seed 0), one round -- the root plan (variable 0
+          free), then the three-subtree plan (the root constant: 3 x 40 variables, 3 x 120 factors) -- as two population launches on the
+          plain solver (plan option population_plain; the subtree launch is 768 workgroups of 128 lanes), against the same round member
+          by member through set_x / set_start(None) / solve / get_x.
 Every step runs in a child process under a time limit of its own; a step that fails ends the run.  Wall times are the median of
 `--repeats` calls after one warm-up call; kernel_ms is rdis_hip_plan_last_kernel_ms of the last call."""
 import argparse
@@ -26,8 +30,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-STEP_LIMIT_S = {"config3": 240, "config5s": 240, "config2": 240, "population": 240}
-STEPS = ("config3", "config5s", "config2", "population")
+STEP_LIMIT_S = {"config3": 240, "config5s": 240, "config2": 240, "population": 240, "population-nlp": 240}
+STEPS = ("config3", "config5s", "config2", "population", "population-nlp")
 
 
 def ulp_perturbed(x0, rng):
@@ -149,10 +153,84 @@ def measure_population(repeats, members=256):
             "device_bytes": [p.device_bytes() for p in plans]}
 
 
+def measure_population_nlp(repeats, members=256):
+    """one root / subtrees round of the sinusoid on a population (plain solver) against the same round member by member"""
+    from rdis_amd import capi, problems as P
+    pp = P.make_high_dim_sinusoid()
+    X = np.random.default_rng(0).uniform(pp.lo, pp.hi, size=(members, pp.nvars))
+    ctx = capi.Context(0)
+    g = capi.Problem(ctx, pp)
+    only_root = np.ones(pp.nvars, np.uint8)
+    only_root[0] = 0
+    plans = [capi.Plan(g, *g.components(only_root)), capi.Plan(g, *g.components(1 - only_root))]
+    for plan in plans:
+        plan.set_option("population_plain", 1)
+    assert plans[0].nfree == 1 and plans[1].ncomp == 3 and all(p.info("components_plain") == p.ncomp for p in plans)
+    pop = capi.Population(g, members)
+
+    def together():
+        pop.set_x(X)
+        t = time.perf_counter()
+        for plan in plans:
+            plan.solve_population(pop, 25, 3e-8)
+        ctx.synchronize()
+        return time.perf_counter() - t, pop.get_x()
+
+    def kernel_times():   # (the problem's timing events belong to its last solve: read after each launch, outside the timed round)
+        pop.set_x(X)
+        out = []
+        for plan in plans:
+            plan.solve_population(pop, 25, 3e-8)
+            out.append(plan.last_kernel_ms())
+        return [ms for ms, _ in out], sum(n for _, n in out)
+
+    def one_by_one():
+        out = np.empty_like(X)
+        t = time.perf_counter()
+        for s in range(members):
+            g.set_x(X[s])
+            for plan in plans:
+                plan.set_start(None)
+                plan.solve(25, 3e-8)
+            out[s] = g.get_x()
+        return time.perf_counter() - t, out
+
+    # one member's subtree solve, the device time of its launch (three workgroups of 128 lanes): the median over a few members
+    singles = []
+    for s in range(min(members, 9)):
+        g.set_x(X[s]); plans[1].set_start(None); plans[1].solve(25, 3e-8); plans[1].fetch()
+        singles.append(plans[1].last_kernel_ms()[0])
+    single_ms = float(np.median(singles[1:])) if len(singles) > 1 else singles[0]
+    together()
+    tt = []
+    for _ in range(repeats):
+        dt, xt = together()
+        tt.append(dt)
+    kernel_ms, launches = kernel_times()
+    one_by_one()
+    ts = []
+    for _ in range(repeats):
+        dt, xs = one_by_one()
+        ts.append(dt)
+    f = pop.eval()
+    wall, seq = float(np.median(tt)), float(np.median(ts))
+    return {"members": members, "root_components": plans[0].ncomp, "subtree_components": plans[1].ncomp,
+            "subtree_workgroups": members * plans[1].ncomp,
+            "members_per_launch": plans[1].info("starts_per_launch"), "launches_per_round": 2,
+            "wall_ms": 1e3 * wall, "sequential_wall_ms": 1e3 * seq, "speedup": seq / wall,
+            "last_kernel_ms": kernel_ms, "last_kernel_launches": launches, "one_member_subtree_solve_kernel_ms": single_ms,
+            "subtree_kernel_in_single_solves": kernel_ms[1] / single_ms,
+            "bits_equal_sequential": bool(xt.tobytes() == xs.tobytes()), "finite_members": int(np.sum(np.isfinite(f))),
+            "best_f": float(np.nanmin(f)) if np.any(np.isfinite(f)) else None,
+            "device_bytes": [p.device_bytes() for p in plans]}
+
+
 def step(name, repeats):
     from rdis_amd import problems as P
     if name == "population":
         return measure_population(repeats)
+    if name == "population-nlp":
+        return measure_population_nlp(repeats)
     if name == "config3":
         with open(os.path.join(ROOT, "tests", "golden", "end_values.json")) as fh:
             seed = json.load(fh)["seed"]
