@@ -365,7 +365,10 @@ int rdis_hip_comm_allreduce_f64(rdis_hip_comm *comm, double *inout, int32_t n, i
  * components with at least this many factors fit the device together, each of them gets one and
  * they run side by side in one launch; 0 = off), "coop_workgroups" (cap, 0 = what fits),
  * "coop_threads" (128, 256 or 512), "coop_poll_delay" (x64 cycles between publishing and the
- * first granule sweep), "coop_pipeline" (default 1: cooperative groups run with the control logic,
+ * first granule sweep), "coop_poll_inflight" (pipelined groups, 0 or 1: 1 = a collector that had to wait
+ * for its own lanes keeps several polls of the value+slope slot it sweeps in flight, one issued every
+ * "coop_poll_stagger" x64 cycles (0 ... 64), and looks at each as it returns -- solver_pipe.hpp:
+ * sweep_ring; 0 = one poll at a time; results do not depend on either), "coop_pipeline" (default 1: cooperative groups run with the control logic,
  * the exchange and the factor arithmetic on waves of their own, solver_pipe.hpp, whenever every
  * group of the plan fits that layout of 128 factor lanes per workgroup; 0 = the plain cooperative
  * kernel; same bits either way as long as every variable fed by more than 48 partials has a wave;
@@ -442,7 +445,7 @@ int rdis_hip_plan_set_option(rdis_hip_plan *plan, const char *name, int64_t valu
 /* which solver the plan's components go to (a test and tuning aid; the partition is computed on demand):
  * "components_cooperative", "components_grid_stream", "components_tiny", "components_lds",
  * "components_point_major", "components_plain" (counts), "pipelined" (0/1: cooperative groups use the
- * pipelined layout), "point_major_group" (workgroups per component in the last solve's point-major launch), "point_major_threads" (their lanes), "point_major_round_slots" (slots a gradient round staged), "grid_stream_workgroups" (workgroups of the first component on the grid solver),
+ * pipelined layout), "coop_poll_delay" / "coop_poll_inflight" / "coop_poll_stagger" (the options' values), "point_major_group" (workgroups per component in the last solve's point-major launch), "point_major_threads" (their lanes), "point_major_round_slots" (slots a gradient round staged), "grid_stream_workgroups" (workgroups of the first component on the grid solver),
  * "point_major_wide" (0/1: that launch was a wide group), "point_major_local_cameras" (0, or the most cameras a workgroup of
  * a wide group with local camera numbering holds), "starts_per_launch" / "starts_launches" (starts a launch of the last multi-start
  * solve held; its number of launches) */
@@ -461,12 +464,17 @@ int rdis_hip_plan_last_kernel_ms(rdis_hip_plan *plan, double *ms, int32_t *launc
 int rdis_hip_plan_get_trace(rdis_hip_plan *plan, int64_t comp, double *rec4, int64_t cap,
                             int64_t *nrec);
 
-/* 32 shader-cycle accumulators of the last cooperative solve, as seen by lane 0 of
+/* 48 shader-cycle accumulators of the last cooperative solve, as seen by lane 0 of
  * workgroup 0: {factor arithmetic, workgroup reduce, publish, granule sweep, tail,
  * #exchanges, #sweeps, whole kernel, control step, request hand-over, combine, release,
- * [12..20] cycles per request kind, [22..30] requests per kind}.  All zero unless the
+ * [12..20] cycles per request kind, [22..30] requests per kind; the pipelined solver's
+ * collector, by kind of sweep (one that waited for its own lanes / one that did not):
+ * [32, 35] polls, [33, 36] polling cycles, [34, 37] completed sweeps; [38..41] sweeps that
+ * took 1, 2, 3, 4 or more polls; [42] cycles from a poll's issue to its return, [43] polls
+ * so timed}.  THE BUFFER SIZE CHANGED: the call writes 48 values (it wrote 32 before the collector's
+ * counters were added), so a caller built against the earlier header must enlarge its buffer.  All zero unless the
  * library was built with -DRDIS_COOP_TIMING (profiling aid) */
-int rdis_hip_plan_debug_counters(rdis_hip_plan *plan, int64_t *out32);
+int rdis_hip_plan_debug_counters(rdis_hip_plan *plan, int64_t *out48);
 /* p and search direction at the start of each of the first dump_iters line
  * minimisations of component c: out[dump_iters][2][nfree_c] (dump_iters > 0) */
 int rdis_hip_plan_get_vectors(rdis_hip_plan *plan, int64_t comp, double *out, int64_t cap_doubles);

@@ -569,6 +569,9 @@ class Plan:
             pass
 
     def set_option(self, name: str, value: int):
+        """the options of include/rdis_hip.h, e.g. coop_pipeline, coop_speculate, coop_poll_delay (x64 cycles before a collector's
+        first poll), coop_poll_inflight (0 / 1: the pipelined collector keeps several polls of a slot in flight) and
+        coop_poll_stagger (0 ... 64, x64 cycles between two such polls); info() reports the last three under the same names"""
         self.ctx.check(self.ctx.lib.rdis_hip_plan_set_option(self.h, name.encode(), int(value)))
 
     def set_start(self, x=None):
@@ -667,7 +670,7 @@ class Plan:
         return b.value
 
     def debug_counters(self) -> np.ndarray:
-        out = np.zeros(32, dtype=np.int64)
+        out = np.zeros(48, dtype=np.int64)      # (PIPE_TM of solver_pipe.hpp: the first 32 are the cooperative solvers' COOP_TM)
         self.ctx.check(self.ctx.lib.rdis_hip_plan_debug_counters(self.h, _ptr(out)))
         return out
 

@@ -181,6 +181,8 @@ struct CoopArgs {
                            // order, gradient times direction and the Polak-Ribiere sums over the variables in list order (solver_coop.hpp:
                            // ordered_sums; looked at by the reference-rounding instantiation only, refround_kernels.hip)
     int stale;             // ... with it, plan option emulate_stale_cache: the reference's factor cache (Variable.cpp:66-76, Factor.h:228-234)
+    int poll_inflight;     // pipelined solver, plan option coop_poll_inflight: the collector keeps several polls of a slot in flight (solver_pipe.hpp: sweep_ring)
+    int poll_stagger;      // ... x64 cycles between two of them (coop_poll_stagger)
 };
 
 // One launch solves several components side by side: workgroups [wg0, wg0 + nwg) of the grid form

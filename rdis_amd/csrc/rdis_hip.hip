@@ -345,6 +345,8 @@ struct rdis_hip_plan {
     int camera_records = 1;           // option "camera_records": 0 = every factor forms its rotation itself, 1 = auto, 2 = records wherever possible
     size_t off_cb_ptr = 0, off_cb = 0, off_cb_li = 0;
     int coop_workgroups = 0, coop_threads = 256, coop_poll_delay = 16;
+    int coop_poll_inflight = 0;       // option: the pipelined collector keeps PIPE_POLLS polls of a value+slope slot in flight (solver_pipe.hpp: sweep_ring)
+    int coop_poll_stagger = 2;        // ... one issued every so many x64 cycles (off by default: no setting of the scan beat one poll at a time)
     int coop_speculate = 1;           // option: guesses at the following trial steps ride along with every line-search trial
     int coop_pipeline = 1;            // option: cooperative groups with a control wave of their own (solver_pipe.hpp); 0 = solver_coop.hpp
     bool use_pipe = false;            // decided by prepare_partition: the plan's groups fit the pipelined layout (fewer factor lanes per workgroup)
@@ -1267,9 +1269,10 @@ int ensure_problem_scratch(rdis_hip_problem* p) {
     if (!p->dir.p) {
         int rc = dalloc(c, p->dir, (size_t)p->N * sizeof(double));
         if (!rc) rc = dalloc(c, p->coop_state, coop_state_bytes());
-        if (!rc) rc = dalloc(c, p->coop_timing, COOP_TM * sizeof(long long));
+        if (!rc) rc = dalloc(c, p->coop_timing, PIPE_TM * sizeof(long long));
         if (rc) return rc;
         HIPCHK(c, hipMemsetAsync(p->dir.p, 0, p->dir.bytes, c->stream));
+        HIPCHK(c, hipMemsetAsync(p->coop_timing.p, 0, p->coop_timing.bytes, c->stream));
         HIPCHK(c, hipEventCreate(&p->ev0));
         HIPCHK(c, hipEventCreate(&p->ev1));
         p->h_mark.assign((size_t)p->N, VarMark{0, -1, -1, 0});
@@ -1626,6 +1629,12 @@ extern "C" int rdis_hip_plan_set_option(rdis_hip_plan* L, const char* name, int6
     } else if (n == "coop_poll_delay") {
         if (value < 0 || value > 1024) return fail(c, RDIS_HIP_EINVAL, "coop_poll_delay out of range");
         L->coop_poll_delay = (int)value;
+    } else if (n == "coop_poll_inflight") {
+        if (value < 0 || value > 1) return fail(c, RDIS_HIP_EINVAL, "coop_poll_inflight must be 0 (one poll at a time) or 1 (a ring of polls in flight)");
+        L->coop_poll_inflight = (int)value;
+    } else if (n == "coop_poll_stagger") {
+        if (value < 0 || value > 64) return fail(c, RDIS_HIP_EINVAL, "coop_poll_stagger out of range (0 ... 64)");
+        L->coop_poll_stagger = (int)value;
     } else if (n == "starts_workspace_bytes") {
         if (value < 0) return fail(c, RDIS_HIP_EINVAL, "starts_workspace_bytes < 0");
         L->starts_workspace_bytes = value;
@@ -2137,7 +2146,8 @@ int pack_coop_launches(rdis_hip_plan* L, int cap) {
                            L->coop_ints.as<int>() + it.lane_var, L->coop_ints.as<int>() + it.wave_var, L->xi_glob.as<double>() + it.xi_off, it.comp,
                            // (a small group's sweep is one entry per lane: polling early costs it less than waiting)
                            it.nwg * (L->coop_lanes() / 64) <= 64 ? std::min(4, L->coop_poll_delay) : L->coop_poll_delay,
-                           L->coop_speculate, L->factor_rounding == 1 ? 1 : 0, (L->factor_rounding == 1 && L->emulate_stale) ? 1 : 0};
+                           L->coop_speculate, L->factor_rounding == 1 ? 1 : 0, (L->factor_rounding == 1 && L->emulate_stale) ? 1 : 0,
+                           L->coop_poll_inflight, L->coop_poll_stagger};
             g.wg0 = cl.total_wg; g.nwg = it.nwg;
             hg.push_back(g);
             hw.insert(hw.end(), (size_t)it.nwg, cl.count);
@@ -3204,6 +3214,9 @@ extern "C" int rdis_hip_plan_get_info(rdis_hip_plan* L, const char* name, int64_
     else if (n == "point_major_local_cameras") *value = (L->ptm_wide_last && L->ptm_local) ? L->ptm_ncb_cap : 0;
     else if (n == "components_plain") *value = rest;
     else if (n == "pipelined") *value = L->pipelined() ? 1 : 0;
+    else if (n == "coop_poll_delay") *value = L->coop_poll_delay;
+    else if (n == "coop_poll_inflight") *value = L->coop_poll_inflight;
+    else if (n == "coop_poll_stagger") *value = L->coop_poll_stagger;
     else if (n == "point_major_group") *value = L->ptm_last_group;
     else if (n == "point_major_threads") *value = L->ptm_last_threads;
     else if (n == "point_major_round_slots") *value = L->rounds_slots;
@@ -3331,11 +3344,11 @@ extern "C" int rdis_hip_components_fetch(rdis_hip_problem* p, int64_t* free_ptr,
     return 0;
 }
 
-extern "C" int rdis_hip_plan_debug_counters(rdis_hip_plan* L, int64_t* out32) {
-    if (!L || !out32) return RDIS_HIP_EINVAL;
+extern "C" int rdis_hip_plan_debug_counters(rdis_hip_plan* L, int64_t* out48) {
+    if (!L || !out48) return RDIS_HIP_EINVAL;
     rdis_hip_ctx* c = L->prob->ctx;
     USE_DEVICE(c);
-    HIPCHK(c, hipMemcpyAsync(out32, L->prob->coop_timing.p, COOP_TM * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out48, L->prob->coop_timing.p, PIPE_TM * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -60,6 +60,20 @@ constexpr int PIPE_CTRL = 2;      // stepper + collector
 constexpr int PIPE_LANES = PIPE_THREADS - 64 * PIPE_CTRL;   // factor lanes per workgroup
 constexpr int PIPE_QUIT = 0x7FFFFFFF;
 static_assert(PIPE_NBUF >= 5 * PIPE_DEPTH + 4 && (PIPE_NBUF & (PIPE_NBUF - 1)) == 0, "ring too short for the run-ahead");
+#ifndef RDIS_PIPE_POLLS
+#define RDIS_PIPE_POLLS 2   // (2, 3 and 4 were scanned: profiles/pipe_poll_ring_scan.txt)
+#endif
+constexpr int PIPE_POLLS = RDIS_PIPE_POLLS;   // polls of one slot a collector keeps in flight (PipeSync::sweep_ring)
+constexpr int PIPE_CH = 8;        // entries a lane reads per poll
+static_assert(PIPE_POLLS >= 2 && (PIPE_POLLS - 1) * PIPE_CH <= 63, "s_waitcnt encodes a vmcnt of at most 63");
+static_assert(PIPE_ENT <= 64 * PIPE_CH, "one poll of the ring covers every entry of a group");
+constexpr int PIPE_TM = 48;       // debug counters of this solver: COOP_TM and the collector's polls by kind of sweep
+static_assert(PIPE_TM >= COOP_TM, "the cooperative solvers' counters come first");
+#ifdef RDIS_COOP_TIMING
+#define RDIS_PIPE_TM(...) __VA_ARGS__
+#else
+#define RDIS_PIPE_TM(...)
+#endif
 
 // same memory as a CoopState (one per concurrent group), cut differently
 struct PipeState {
@@ -126,15 +140,44 @@ __device__ __forceinline__ long long lds_int_pair(const int& x) { return *(const
 __device__ __forceinline__ double lds_f64_get(const double& x) { return *(const volatile lds_f64*)&x; }
 __device__ __forceinline__ void lds_f64_set(double& x, double v) { *(volatile lds_f64*)&x = v; }
 
+// The registers the polls of a ring land in.  They belong to the collector's loop, not to a sweep: a sweep that
+// completes leaves its younger polls in flight, and the registers are free again only after the collector's next
+// wait for every memory operation (drain).
+struct PollRing {
+    u64x2 pr[PIPE_POLLS][PIPE_CH];
+    // the compiler does not know that an inline-asm load's destination is pending: an empty asm that
+    // "modifies" a set keeps its registers allocated up to here and its values unread before here
+    // (s is a constant wherever this is called: the loops over the ring are fully unrolled)
+    __device__ __forceinline__ void pin(int s) {
+#pragma unroll
+        for (int j = 0; j < PIPE_CH; ++j) asm volatile("" : "+v"(pr[s][j]));
+    }
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int s = 0; s < PIPE_POLLS; ++s)
+#pragma unroll
+            for (int j = 0; j < PIPE_CH; ++j) { pr[s][j].x = 0ull; pr[s][j].y = 0ull; }
+    }
+    // every poll has landed: after this the registers may be loaded into again
+    __device__ __forceinline__ void drain() {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int s = 0; s < PIPE_POLLS; ++s)
+#pragma unroll
+            for (int j = 0; j < PIPE_CH; ++j) asm volatile("" : "+v"(pr[s][j]));
+    }
+};
+
 struct PipeSync {
     PipeState* st;
     int tid, nwg, wg, nw;        // lane in workgroup, #workgroups, my workgroup, lane waves per workgroup
     int poll_delay;
+    int poll_ring, poll_stagger; // collector: several polls of a value+slope slot in flight (sweep_ring), x64 cycles between two issues
     int e;                       // next exchange number of the request being served (stepper and lanes agree)
     int rearmed;                 // collector: slots <= rearmed are re-armed
     bool dead;
 #ifdef RDIS_COOP_TIMING
-    long long tm[COOP_TM];
+    long long tm[PIPE_TM];
 #endif
     __device__ void tick(int slot, long long dt) {
 #ifdef RDIS_COOP_TIMING
@@ -178,8 +221,12 @@ struct PipeSync {
     // up -- and, if it had to wait, sleeps `delay` (x64 cycles: a store needs about that long to land;
     // polling earlier only slows it down) before the first look at memory.
     // Returns false, v untouched, when the stepper has named another slot in the meantime (`cmd`).
+    // A value+slope sweep (N = 2) that had to wait for its own lanes goes to sweep_ring when the plan asks for it
+    // (poll_ring): there the skew between the workgroups is being waited for, and what matters is how soon after
+    // the last store the collector looks.  A sweep whose lanes were already past the slot finds everything with
+    // its first poll; more polls in flight would only lengthen the drain before the next sweep.
     template <int N, int NMAX>
-    __device__ bool sweep(int ex, double (&v)[N], int delay, const int& cmd, int cmd_mine, const int* pub) {
+    __device__ bool sweep(int ex, double (&v)[N], int delay, const int& cmd, int cmd_mine, const int* pub, PollRing& R) {
         const int lane = tid & 63;
         const int nent = nwg * nw;
         double acc[N];
@@ -188,10 +235,11 @@ struct PipeSync {
         unsigned spins = 0;
         bool ok = !dead;
         const int per = (nent + 63) >> 6;
-        constexpr int CH = 8;
+        constexpr int CH = PIPE_CH;
         const long long tq0 = coop_clock();
+        bool waited = false;
+        [[maybe_unused]] int looks = 0;
         {
-            bool waited = false;
             for (;;) {
                 int lo = lds_int(pub[0]);
 #pragma unroll
@@ -206,6 +254,9 @@ struct PipeSync {
             if (waited) { tick(26, coop_clock() - tq0); tick(27, 1); }
             if (waited) for (int d = 0; d < delay; d += 8) __builtin_amdgcn_s_sleep(8);
         }
+        if constexpr (N == 2 && NMAX == 0) {
+            if (poll_ring != 0 && waited && ok) return sweep_ring(ex, v, cmd, cmd_mine, R);
+        }
         const long long tq1 = coop_clock();
         for (int j0 = 0; j0 < per && ok; j0 += CH) {
             unsigned long long val[CH][N];
@@ -215,6 +266,7 @@ struct PipeSync {
                 for (int k = 0; k < N; ++k) val[j][k] = COOP_SENTINEL;
             for (;;) {
                 tick(6, 1);
+                RDIS_PIPE_TM(++looks);
                 constexpr int NP = N / 2;
                 u64x2 pr[CH][NP > 0 ? NP : 1];
 #pragma unroll
@@ -278,6 +330,114 @@ struct PipeSync {
 #pragma unroll
         for (int k = 0; k < N; ++k) v[k] = k < N - NMAX ? wave_sum(acc[k]) : wave_max(acc[k]);
         tick(5, 1); tick(28, tq2 - tq1); tick(29, coop_clock() - tq2);
+        RDIS_PIPE_TM(tick_polls(waited, looks, tq2 - tq1));
+        return true;
+    }
+    // (timing build) a completed sweep's polls, by kind of sweep: one that waited for its own lanes / one that did not
+    __device__ void tick_polls(bool waited, int looks, long long cycles) {
+        if (waited) { tick(32, looks); tick(33, cycles); tick(34, 1); }
+        else { tick(35, looks); tick(36, cycles); tick(37, 1); }
+        if (looks <= 1) tick(38, 1); else if (looks == 2) tick(39, 1); else if (looks == 3) tick(40, 1); else tick(41, 1);
+    }
+
+    __device__ __forceinline__ void stagger_sleep() const {
+        int d = poll_stagger;
+        for (; d >= 8; d -= 8) __builtin_amdgcn_s_sleep(8);
+        if (d & 4) __builtin_amdgcn_s_sleep(4);
+        if (d & 2) __builtin_amdgcn_s_sleep(2);
+        if (d & 1) __builtin_amdgcn_s_sleep(1);
+    }
+
+    // The value+slope sweep with PIPE_POLLS polls of the slot in flight.  sweep() sends one poll, waits for all of
+    // it and sends the next when something was missing: the moment it sees the last workgroup's store is quantised
+    // to a memory round trip, and a store that lands just after a poll was served costs another whole one.  Here a
+    // poll is issued every poll_stagger x 64 cycles into a ring of register sets, and the wave waits for the
+    // OLDEST one only -- s_waitcnt vmcnt((PIPE_POLLS - 1) * 8).  Loads return in order among loads, and a poll is
+    // always eight of them (entries beyond the group's clamp to entry 0; nothing is skipped for what is already
+    // there), so at most that many operations outstanding means the oldest eight have landed, whatever earlier
+    // re-arming stores or the occasional look at the abort word add to the count: it can only over-wait.
+    // An entry once seen is kept; the sums are formed entry by entry in index order, as sweep() forms them.
+    // Whichever way the sweep ends, PIPE_POLLS polls are still in flight when it returns, and it is the caller that
+    // frees the ring (PollRing::drain: pipe_collector, on the one path every sweep's end takes): after a completed
+    // sweep the sums go to the stepper first, so the younger polls never delay a result.
+    __device__ bool sweep_ring(int ex, double (&v)[2], const int& cmd, int cmd_mine, PollRing& R) {
+        constexpr int CH = PIPE_CH;
+        const int lane = tid & 63;
+        const int nent = nwg * nw;
+        const gu64* at[CH];
+        unsigned long long val[CH][2];
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+            const int ww = lane + (j << 6);
+            at[j] = gran(ex, 0, ww < nent ? ww : 0);
+            val[j][0] = COOP_SENTINEL; val[j][1] = COOP_SENTINEL;
+        }
+        const long long tq1 = coop_clock();
+        [[maybe_unused]] long long ti[PIPE_POLLS];
+        [[maybe_unused]] int looks = 0;
+#pragma unroll
+        for (int s = 0; s < PIPE_POLLS; ++s) {
+            if (s > 0) stagger_sleep();
+            RDIS_PIPE_TM(ti[s] = coop_clock());
+#pragma unroll
+            for (int j = 0; j < CH; ++j) asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(R.pr[s][j]) : "v"(at[j]) : "memory");
+            R.pin(s);
+        }
+        unsigned spins = 0;
+        bool ok = true;
+        double acc[2] = {0.0, 0.0};
+        const int mine_u = __builtin_amdgcn_readfirstlane(cmd_mine);   // (every lane holds the same: read from LDS)
+        // (every test that ends the loop is on a wave-uniform value and leaves by a jump of its own: the exits then are
+        // scalar branches, not lanes masked off up to a common back edge -- tools/check_async_loads.py follows the
+        // paths of the code as built, and the ring's turns must be told apart on them)
+        for (;;) {
+#pragma unroll
+            for (int s = 0; s < PIPE_POLLS; ++s) {
+                // the oldest poll in flight is the one in set s
+                asm volatile("s_waitcnt vmcnt(%0)" : : "n"((PIPE_POLLS - 1) * CH) : "memory");
+                R.pin(s);
+                tick(6, 1);
+                RDIS_PIPE_TM(++looks; tick(42, coop_clock() - ti[s]); tick(43, 1));
+                bool here = true;
+#pragma unroll
+                for (int j = 0; j < CH; ++j) {
+                    if (val[j][0] == COOP_SENTINEL) val[j][0] = R.pr[s][j].x;
+                    if (val[j][1] == COOP_SENTINEL) val[j][1] = R.pr[s][j].y;
+                    here = here && val[j][0] != COOP_SENTINEL && val[j][1] != COOP_SENTINEL;
+                }
+                // set s is read: the next poll goes there, whatever this one showed.  (Issued before the tests below, on the
+                // one path every turn takes: a load issued on some paths only would make the ring's registers values that
+                // differ between paths, which the compiler joins with register copies -- of registers a load is pending on.)
+                RDIS_PIPE_TM(ti[s] = coop_clock());
+#pragma unroll
+                for (int j = 0; j < CH; ++j) asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(R.pr[s][j]) : "v"(at[j]) : "memory");
+                R.pin(s);
+                if (__all(here)) goto complete;
+                if (__builtin_amdgcn_readfirstlane(lds_int(cmd)) != mine_u) return false;   // the stepper wants something else
+                ++spins;
+                if (spins > COOP_SPIN_LIMIT ||
+                    ((spins & 255u) == 0u &&
+                     __builtin_amdgcn_readfirstlane((int)__hip_atomic_load((gu32*)&st->abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0)) {
+                    if (lane == 0) __hip_atomic_store((gu32*)&st->abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    ok = false;
+                    goto complete;
+                }
+                stagger_sleep();
+            }
+        }
+    complete:
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+            if (lane + (j << 6) < nent) {
+                acc[0] += __longlong_as_double(val[j][0]);
+                acc[1] += __longlong_as_double(val[j][1]);
+            }
+        }
+        if (!__all(ok)) dead = true;
+        const long long tq2 = coop_clock();
+        v[0] = wave_sum(acc[0]); v[1] = wave_sum(acc[1]);
+        tick(5, 1); tick(28, tq2 - tq1); tick(29, coop_clock() - tq2);
+        RDIS_PIPE_TM(tick_polls(true, looks, tq2 - tq1));
         return true;
     }
     // after a completed sweep of slot ex (every memory operation of this wave, the previous re-arming
@@ -510,7 +670,7 @@ struct PipeEnv {
 // collector also: 26 cycles waiting for the own lanes' publication (27 how often), 28 polling memory, 29 final reduction
 // lanes also, per full gradient (31 how many): 3 partials + scatter, 18 the grid-wide barrier behind it, 30 per-variable sums
 __device__ __forceinline__ int pipe_slot_owner(int i) {   // 0 stepper, 1 collector, 2 lanes
-    return (i == 0 || i == 2 || i == 3 || i == 18 || (i >= 9 && i <= 11) || i == 30 || i == 31) ? 2 : (i == 1 || (i >= 4 && i <= 6) || (i >= 26 && i <= 29)) ? 1 : 0;
+    return (i == 0 || i == 2 || i == 3 || i == 18 || (i >= 9 && i <= 11) || i == 30 || i == 31) ? 2 : (i == 1 || (i >= 4 && i <= 6) || (i >= 26 && i <= 29) || i >= 32) ? 1 : 0;
 }
 
 // the stepper posts a request (lane 0 writes; LDS operations of a wave execute in order, so whoever
@@ -762,6 +922,8 @@ __device__ __forceinline__ void pipe_collector(PipeSync& X, PipeShared& S) {
     int mine = -1;   // the command last acted on
     int next = -1;   // the slot to go on to without being told
     const bool writer = (X.tid & 63) == 0;
+    PollRing R;      // (sweep_ring: live across the loop, its registers are the collector's alone)
+    R.clear();
     for (;;) {
         const int c = lds_int(S.cmd);
         int ex, n;
@@ -780,18 +942,25 @@ __device__ __forceinline__ void pipe_collector(PipeSync& X, PipeShared& S) {
         double v[3] = {0.0, 0.0, 0.0};
         bool got;
         const long long t0 = coop_clock();
-        if (n == 2) { double w[2]; got = X.sweep<2, 0>(ex, w, delay, S.cmd, mine, S.pub); v[0] = w[0]; v[1] = w[1]; }
-        else if (n == 3) { got = X.sweep<3, 1>(ex, v, delay, S.cmd, mine, S.pub); }
-        else { double w[1]; got = X.sweep<1, 0>(ex, w, delay, S.cmd, mine, S.pub); v[0] = w[0]; }
-        if (!got) { X.tick(4, 1); continue; }
-        X.tick(1, coop_clock() - t0);
-        if (writer) {
-            if (X.dead) lds_set(S.dead, 1);
-            double* r = S.res[ex & (PIPE_RES - 1)];
-            lds_f64_set(r[0], v[0]); lds_f64_set(r[1], v[1]); lds_f64_set(r[2], v[2]);
-            lds_set(S.res_slot[ex & (PIPE_RES - 1)], ex);
+        if (n == 2) { double w[2]; got = X.sweep<2, 0>(ex, w, delay, S.cmd, mine, S.pub, R); v[0] = w[0]; v[1] = w[1]; }
+        else if (n == 3) { got = X.sweep<3, 1>(ex, v, delay, S.cmd, mine, S.pub, R); }
+        else { double w[1]; got = X.sweep<1, 0>(ex, w, delay, S.cmd, mine, S.pub, R); v[0] = w[0]; }
+        if (got) {
+            X.tick(1, coop_clock() - t0);
+            if (writer) {
+                if (X.dead) lds_set(S.dead, 1);
+                double* r = S.res[ex & (PIPE_RES - 1)];
+                lds_f64_set(r[0], v[0]); lds_f64_set(r[1], v[1]); lds_f64_set(r[2], v[2]);
+                lds_set(S.res_slot[ex & (PIPE_RES - 1)], ex);
+            }
+        } else {
+            X.tick(4, 1);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // s_waitcnt vmcnt(0): the polls a ring sweep left in flight (a completed one handed its sums over first, an
+        // abandoned one's land before the ring is used again) and the previous re-arming stores.  The one path
+        // every sweep's end takes: the ring's registers are the same values, in the same registers, on all of them.
+        R.drain();
+        if (!got) continue;
         X.rearm_behind(ex);
         if (n == 2 && !X.dead) {
             // does the chain go on?  (the lanes write a slot's guess down before they evaluate the slot before it)
@@ -917,7 +1086,7 @@ __device__ __forceinline__ void pipe_solve(const ProblemView& P, const PlanView&
     const int gt = tid < 64 * PIPE_CTRL ? -1 : wg * PIPE_LANES + tid - 64 * PIPE_CTRL;
 
     PipeEnv E{P, L, A, S, n, m, f0, c0, gt, tid,
-              PipeSync{(PipeState*)A.st, tid, nwg, wg, PIPE_LANES / 64, A.poll_delay, 0, -1, false
+              PipeSync{(PipeState*)A.st, tid, nwg, wg, PIPE_LANES / 64, A.poll_delay, A.poll_inflight, A.poll_stagger, 0, -1, false
 #ifdef RDIS_COOP_TIMING
                        , {}
 #endif
@@ -961,7 +1130,7 @@ __device__ __forceinline__ void pipe_solve(const ProblemView& P, const PlanView&
 #ifdef RDIS_COOP_TIMING
     if (wg == 0 && (tid & 63) == 0 && tid < 192 && A.timing) {
         if (tid == 0) E.X.tm[7] = coop_clock() - tk0;
-        for (int i = 0; i < COOP_TM; ++i) if (pipe_slot_owner(i) == (tid >> 6)) A.timing[i] = E.X.tm[i];
+        for (int i = 0; i < PIPE_TM; ++i) if (pipe_slot_owner(i) == (tid >> 6)) A.timing[i] = E.X.tm[i];
     }
 #endif
 }

@@ -34,3 +34,9 @@ if tm[7] > 0:
     print("   collector: waited %d times for its own lanes (%.0f cycles each); polling memory %.0f, final reduction %.0f cycles per sweep" % (
         tm[27], tm[26] / max(int(tm[27]), 1), tm[28] / max(int(tm[5]), 1), tm[29] / max(int(tm[5]), 1)))
     print("   lanes gradient: partials+scatter %.0f, barrier %.0f, sums %.0f (x%d)" % (tm[3] / max(int(tm[31]), 1), tm[18] / max(int(tm[31]), 1), tm[30] / max(int(tm[31]), 1), tm[31]))
+    if len(tm) >= 48 and tm[34] + tm[37] > 0:
+        nw, nn = max(int(tm[34]), 1), max(int(tm[37]), 1)
+        print("   collector, sweeps that waited for their own lanes: %d, %.2f polls and %.0f polling cycles each | sweeps that did not: %d, %.2f polls and %.0f cycles each" % (
+            tm[34], tm[32] / nw, tm[33] / nw, tm[37], tm[35] / nn, tm[36] / nn))
+        print("   collector, polls looked at per completed sweep: 1: %d  2: %d  3: %d  4 and more: %d | ring polls, issue to return: %.0f cycles (%d polls)" % (
+            tm[38], tm[39], tm[40], tm[41], tm[42] / max(int(tm[43]), 1), tm[43]))
