@@ -8,10 +8,10 @@ same loop runs one member at a time on the problem itself (set_x, set_start(None
 
   python examples/ba_population.py [members] [rounds] [seed]
 
-Full ladybug (49 cameras, 7776 points) runs the same way with P.load_bal(): its point plan is kept on the LDS-resident solver
-by a large "row_min_components" (by default 7776 three-variable components go to the tiny-component solver), its camera plan
-by "coop_min_factors" = 0 and "coop_group_min_factors" = 0 (by default cameras of hundreds of factors go to the cooperative
-solver).  The script checks "components_lds" before it solves."""
+Full ladybug (49 cameras, 7776 points) is examples/ba_population_full.py: its 7776 three-variable point components stay on the
+tiny-component solver (plan option "population_tiny" = 1), its camera plan is kept on the LDS-resident solver by
+"coop_min_factors" = 0 and "coop_group_min_factors" = 0.  The options below keep every component of the small problem on the
+LDS-resident solver; the script checks "components_lds" before it solves."""
 import os
 import sys
 import time

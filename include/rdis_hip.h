@@ -274,7 +274,8 @@ int rdis_hip_plan_fetch_starts(rdis_hip_plan *plan, double *x_out, double *fret,
  * assignment of the problem's variables; plan_solve_population runs a plan on all members in one launch, member s taking
  * both its start and its constants from X[s] and leaving its result there, so that the next plan (the other variables
  * free) follows with no host traffic (rdis_amd/csrc/solver_lds_population.hpp; nonlinear-product plans, with the plan
- * option "population_plain": solver_wg_population.hpp).
+ * option "population_plain": solver_wg_population.hpp; bundle-adjustment plans with tiny components, with the plan option
+ * "population_tiny": solver_quad_population.hpp).
  *   population_create   allocates X; x[nmembers][N] row-major, or NULL: every member a copy of the problem's currently
  *                       assigned x.  nmembers >= 1 (RDIS_HIP_EINVAL), below 2^31 and nmembers * N below 9e15
  *                       (RDIS_HIP_ERANGE).  Both problem kinds.  A population belongs to one problem and is destroyed
@@ -304,13 +305,24 @@ int rdis_hip_plan_fetch_starts(rdis_hip_plan *plan, double *x_out, double *fret,
  * but no copy of x: that solver's trial points go into the member's own row X[s], which the independence of the
  * components allows just as it allows the result), bounded by the plan option "starts_workspace_bytes" with the same
  * splitting into launches of R members (plan_get_info "starts_per_launch" / "starts_launches"), counted by
- * plan_device_bytes; plan_last_kernel_ms covers the solver launches.
+ * plan_device_bytes; plan_last_kernel_ms covers the solver launches.  With "population_tiny" a replica holds only what
+ * the launch's kernels read: the rotation records of the member's cameras (N doubles) where the tiny-component solver reads
+ * records (cameras constant in the whole plan, "camera_records" not 0), the LDS-resident solver's part only where that solver
+ * has components in the plan -- a plan of points alone with "camera_records" = 0 needs no replica and is never split below
+ * 65535 members; every member of a launch also has a 4-byte queue counter.  A launch of R members is then one launch of the
+ * tiny-component solver (its grid: blocks per member x R, plan_get_info "population_tiny_blocks") followed, where the plan has
+ * other components, by one of the LDS-resident solver; "starts_launches" and plan_last_kernel_ms count both.
  * Scope: a bundle-adjustment problem, every non-empty component of the plan on the LDS-resident solver (plan_get_info
  * "components_lds"); or, with the plan option "population_plain" = 1 (default 0: refused, as before the option existed), a
  * nonlinear-product problem with every non-empty component on the plain batch solver ("components_plain": BASELINE
- * configs 1 and 2, every decomposition of the sinusoid) -- the option has no effect on bundle-adjustment plans.  A
+ * configs 1 and 2, every decomposition of the sinusoid) -- the option has no effect on bundle-adjustment plans; or, with
+ * the plan option "population_tiny" = 1 (default 0: refused, as before the option existed), a bundle-adjustment problem whose
+ * non-empty components run on the tiny-component solver ("components_tiny": a point against constant cameras and the like) or
+ * on the LDS-resident solver, in any mix; the lanes per tiny component are plan_solve's ("quad_min_components",
+ * "row_min_components": the bits depend on them).  A
  * persistent plan; default factor_rounding; emulate_stale_cache, trace_records and dump_iters off; the population must be
- * the plan's problem's.  Not yet: the other solvers; bundle-adjustment components on the plain batch solver.  Anything
+ * the plan's problem's.  Not yet: the cooperative, grid and point-major solvers; bundle-adjustment components on the plain
+ * batch solver; tiny components in plan_solve_starts.  Anything
  * else: RDIS_HIP_EINVAL and a message that names the cause; the plan and the population stay usable. */
 typedef struct rdis_hip_population rdis_hip_population;
 int rdis_hip_population_create(rdis_hip_problem *p, int64_t nmembers, const double *x, rdis_hip_population **out);
@@ -439,6 +451,12 @@ int rdis_hip_comm_allreduce_f64(rdis_hip_comm *comm, double *inout, int32_t n, i
  * "population_plain" (default 0; 1 = rdis_hip_plan_solve_population accepts a nonlinear-product plan whose components all
  * run on the plain batch solver, one workgroup per (component, member) working in the member's own x; 0 = such a plan is
  * refused with RDIS_HIP_EINVAL; no effect on bundle-adjustment plans or on any other entry),
+ * "population_tiny" (default 0; 1 = rdis_hip_plan_solve_population accepts a bundle-adjustment plan with components on the
+ * tiny-component solver, alone or beside components on the LDS-resident solver: a few lanes per (component, member), every
+ * member's blocks walking that member's components, rotation records per member; 0 = such a plan is refused with
+ * RDIS_HIP_EINVAL; no effect on any other entry -- rdis_hip_plan_solve_starts keeps refusing tiny components),
+ * "tiny_population_fill" (default 1, 1 ... 64: that launch takes this many times the blocks the device holds at once; a
+ * measurement aid, no bit depends on it),
  * "trace_records" (per-component trace capacity, 0 = off), "dump_iters" (record p and
  * the search direction at the start of the first k line minimisations, 0 = off). */
 int rdis_hip_plan_set_option(rdis_hip_plan *plan, const char *name, int64_t value);
@@ -448,7 +466,8 @@ int rdis_hip_plan_set_option(rdis_hip_plan *plan, const char *name, int64_t valu
  * pipelined layout), "coop_poll_delay" / "coop_poll_inflight" / "coop_poll_stagger" (the options' values), "point_major_group" (workgroups per component in the last solve's point-major launch), "point_major_threads" (their lanes), "point_major_round_slots" (slots a gradient round staged), "grid_stream_workgroups" (workgroups of the first component on the grid solver),
  * "point_major_wide" (0/1: that launch was a wide group), "point_major_local_cameras" (0, or the most cameras a workgroup of
  * a wide group with local camera numbering holds), "starts_per_launch" / "starts_launches" (starts a launch of the last multi-start
- * solve held; its number of launches) */
+ * solve held; its number of launches), "population_tiny_blocks" (blocks per member of the tiny-component solver's launch in the
+ * last population solve, 0 = it had none) */
 int rdis_hip_plan_get_info(rdis_hip_plan *plan, const char *name, int64_t *value);
 /* device memory the plan holds beyond the problem's (index tables, workspace, per-factor
  * partials, results): what a host-side cache of plans budgets with

@@ -623,8 +623,11 @@ class Plan:
         problem whose x is that member's.  The problem's x and the plan's ordinary outputs are not touched.  Bundle adjustment,
         every component on the LDS-resident solver; or, after set_option("population_plain", 1), a nonlinear-product problem with
         every component on the plain batch solver (info("components_plain")), whose trial points go into the member's own row
-        during the launch; anything else -- a nonlinear-product plan without that option included -- raises RdisHipError (EINVAL)
-        with the cause"""
+        during the launch; or, after set_option("population_tiny", 1), a bundle-adjustment plan whose components run on the
+        tiny-component solver (info("components_tiny"): points against constant cameras) or on the LDS-resident solver, in any
+        mix -- a few lanes per (component, member), with the lanes per component of solve() on the same plan options; anything
+        else -- a nonlinear-product plan or tiny components without their option included -- raises RdisHipError (EINVAL) with
+        the cause"""
         self.ctx.check(self.ctx.lib.rdis_hip_plan_solve_population(self.h, pop.h, maxiters, ftol))
         self._nmembers = pop.nmembers
 

@@ -14,6 +14,14 @@ hipError_t population_launch(int rot, int threads, int ncomp_listed, int members
 // S.dir holds the launch's replicas of dir (S.x is not used: no replica of x)
 hipError_t population_launch_wg(int threads, int ncomp_listed, int members_of_launch, hipStream_t stream, const ProblemView& P, const PlanView& V,
                                 const StartsView& S, double* X, int maxiters, double ftol);
+// cgd_group_population_kernel<group, threads> (solver_quad_population.hpp; group 4: <4, QUAD_THREADS>, else <16, 64>): grid
+// (blocks_per_member, members_of_launch) on the tiny components list[0 .. ntiny); queues[members_of_launch] zero at the start;
+// XR null, or the launch's rotation records [members_of_launch][N] (P.rot_mode == ROT_CAMFIX)
+hipError_t population_launch_tiny(int group, int blocks_per_member, int members_of_launch, hipStream_t stream, const ProblemView& P, const PlanView& V,
+                                  const StartsView& S, double* X, double* XR, const int* list, int ntiny, int* queues, int maxiters, double ftol);
+// population_rotations_kernel: XR[r] = the rotation records of member S.first + r's cameras, r < members_of_launch
+hipError_t population_rotations_launch(hipStream_t stream, const double* X, long long N, long long first, int members_of_launch, const int* cam_blocks,
+                                       int nblocks, double* XR);
 // population_gather_kernel: xstart[s][nfree] = X[s][free_vid] for s < members
 hipError_t population_gather_launch(hipStream_t stream, const double* X, long long N, const int* free_vid, long long nfree, long long members, double* xstart);
 // population_scatter_kernel / population_pick_kernel: members first .. first + count - 1, n values each (vid null: variables 0 .. n-1)

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include "solver_lds_population.hpp"
 #include "solver_wg_population.hpp"
+#include "solver_quad_population.hpp"   // (the tiny-component solver's entry: plan option population_tiny)
 #include "population_api.hpp"
 
 namespace rdis_hip {
@@ -32,6 +33,22 @@ hipError_t population_launch_wg(int threads, int ncomp_listed, int members_of_la
         cgd_wg_population_kernel<KIND_NLP, T.value><<<dim3((unsigned)ncomp_listed, (unsigned)members_of_launch), T.value, 0, stream>>>(P, V, S, X, maxiters, ftol);
         return hipGetLastError();
     });
+}
+
+// (the two instantiations of cgd_group_kernel, rdis_hip.hip: the bits depend on the group size)
+hipError_t population_launch_tiny(int group, int blocks_per_member, int members_of_launch, hipStream_t stream, const ProblemView& P, const PlanView& V,
+                                  const StartsView& S, double* X, double* XR, const int* list, int ntiny, int* queues, int maxiters, double ftol) {
+    const dim3 grid((unsigned)blocks_per_member, (unsigned)members_of_launch);
+    if (group == 4) cgd_group_population_kernel<4, QUAD_THREADS><<<grid, QUAD_THREADS, 0, stream>>>(P, V, S, X, XR, list, ntiny, queues, maxiters, ftol);
+    else cgd_group_population_kernel<16, 64><<<grid, 64, 0, stream>>>(P, V, S, X, XR, list, ntiny, queues, maxiters, ftol);
+    return hipGetLastError();
+}
+
+hipError_t population_rotations_launch(hipStream_t stream, const double* X, long long N, long long first, int members_of_launch, const int* cam_blocks,
+                                       int nblocks, double* XR) {
+    if (nblocks <= 0 || members_of_launch <= 0) return hipSuccess;
+    population_rotations_kernel<<<dim3((unsigned)((nblocks + 255) / 256), (unsigned)members_of_launch), 256, 0, stream>>>(X, N, first, cam_blocks, nblocks, XR);
+    return hipGetLastError();
 }
 
 namespace {

@@ -29,6 +29,7 @@
 #include "ptm_api.hpp"
 #include "starts_api.hpp"
 #include "population_api.hpp"
+#include "population_grid.hpp"
 #include "solver_pipe.hpp"
 #include "solver_quad.hpp"
 #include "solver_stream.hpp"
@@ -368,6 +369,10 @@ struct rdis_hip_plan {
     bool ms_population = false;       // ... which was a population solve (rdis_hip_plan_solve_population: the members are the starts; no ms_best)
     int64_t ms_per_launch = 0, ms_launches = 0;
     int population_plain = 0;         // option "population_plain": 1 = rdis_hip_plan_solve_population takes a nonlinear-product plan on the plain batch solver (solver_wg_population.hpp)
+    int population_tiny = 0;          // option "population_tiny": 1 = ... and a bundle-adjustment plan with components on the tiny-component solver (solver_quad_population.hpp)
+    DevBuf ms_queue;                  // ... whose members of a launch have a queue counter each
+    int tiny_population_fill = 1;     // option "tiny_population_fill" (measurement): the population launch of that solver takes this many times the resident blocks
+    int ms_tiny_blocks = 0;           // ... and this many blocks each in the last such solve (plan_get_info "population_tiny_blocks")
     ~rdis_hip_plan() { if (ms_stage_ev) (void)hipEventDestroy(ms_stage_ev); }
     // the outputs' block for n starts: xout[n][nfree] fret[n][nc] delta[n][nc] (f64) | nfeval[n][nc] ngeval[n][nc] (i64) | iters[n][nc] status[n][nc] (i32)
     size_t ms_out_bytes(int64_t n) const { return (size_t)n * ((size_t)nfree * 8 + (size_t)ncomp * 40); }
@@ -1644,6 +1649,13 @@ extern "C" int rdis_hip_plan_set_option(rdis_hip_plan* L, const char* name, int6
     } else if (n == "population_plain") {
         L->population_plain = value != 0;
         return 0;   // (no table depends on it)
+    } else if (n == "population_tiny") {
+        L->population_tiny = value != 0;
+        return 0;   // (no table depends on it)
+    } else if (n == "tiny_population_fill") {
+        if (value < 1 || value > 64) return fail(c, RDIS_HIP_EINVAL, "tiny_population_fill out of range (1 ... 64)");
+        L->tiny_population_fill = (int)value;
+        return 0;   // (no table depends on it)
     } else if (n == "trace_records") {
         if (value < 0 || value > (1 << 22)) return fail(c, RDIS_HIP_EINVAL, "trace_records out of range");
         if (L->transient && value) return fail(c, RDIS_HIP_EINVAL, "tracing needs a persistent plan");
@@ -2644,7 +2656,8 @@ constexpr int64_t STARTS_MAX_PER_LAUNCH = 65535;       // (the start is the grid
 // why a plan cannot be solved from many starts yet.  Two kinds of plan can: every component on the LDS-resident solver (bundle
 // adjustment), or a nonlinear-product problem with every component on the plain batch solver -- *plain_solver says which
 // (entry: "multi-start" or "population" -- rdis_hip_plan_solve_population shares these checks)
-int starts_refusal(rdis_hip_plan* L, const char* who, bool* plain_solver, const char* entry = "multi-start") {
+// (allow_tiny: the population entry with the plan option population_tiny -- tiny components beside LDS-resident ones pass)
+int starts_refusal(rdis_hip_plan* L, const char* who, bool* plain_solver, const char* entry = "multi-start", bool allow_tiny = false) {
     rdis_hip_problem* p = L->prob;
     rdis_hip_ctx* c = p->ctx;
     const std::string w(who), en(entry);
@@ -2666,7 +2679,7 @@ int starts_refusal(rdis_hip_plan* L, const char* who, bool* plain_solver, const 
     auto note = [&](int64_t count, const char* solver) { if (count > 0) others += (others.empty() ? " " : ", ") + std::to_string(count) + " to the " + solver; };
     note((int64_t)L->coop.size(), "cooperative solver");
     note((int64_t)L->stream.size(), "grid solver");
-    note(tiny, "tiny-component solver");
+    if (!allow_tiny) note(tiny, "tiny-component solver");
     note(ptm, "point-major streaming solver");
     const bool plain_ok = plain > 0 && p->kind == KIND_NLP && others.empty();
     if (!plain_ok) note(plain, "plain batch solver");
@@ -2674,9 +2687,12 @@ int starts_refusal(rdis_hip_plan* L, const char* who, bool* plain_solver, const 
         // (a bundle-adjustment component there reads its cameras' rotation records, ProblemView::xrot: they would need replicas too)
         const std::string ba_plain = plain > 0 && p->kind == KIND_BA ? " (bundle-adjustment components on the plain batch solver have no " + en + " entry, alone or "
                                                                        "beside LDS-resident ones: their rotation records would need replicas too)" : "";
+        // (the population entry takes tiny components with an option of their own; the multi-start entry does not)
+        const std::string tiny_hint = tiny > 0 && !allow_tiny && en == "population" ? " (tiny components are solved on a population with the plan option "
+                                                                                      "population_tiny = 1: solver_quad_population.hpp)" : "";
         return fail(c, RDIS_HIP_EINVAL, w + ": every component of the plan must run on the LDS-resident solver (bundle adjustment, variables fitting a "
                                         "compute unit's LDS) or, all of them, on the plain batch solver of a nonlinear-product problem; this plan sends" +
-                                        others + ba_plain);
+                                        others + ba_plain + tiny_hint);
     }
     *plain_solver = plain_ok;
     return 0;
@@ -2937,21 +2953,30 @@ extern "C" int rdis_hip_plan_solve_population(rdis_hip_plan* L, rdis_hip_populat
         return fail(c, RDIS_HIP_ERANGE, "plan_solve_population: too many members");
     if (int rc = refuse_late_exponential(L, "plan_solve_population")) return rc;   // (nonlinear products only: no bundle-adjustment factor is exponential)
     bool plain = false;
-    if (int rc = starts_refusal(L, "plan_solve_population", &plain, "population")) return rc;
+    if (int rc = starts_refusal(L, "plan_solve_population", &plain, "population", L->population_tiny != 0)) return rc;
     if (L->ncomp == 0) { L->ms_population = true; L->ms_n = S_n; L->ms_per_launch = S_n; L->ms_launches = 0; L->last_launches = 0; L->timed = false; return 0; }
 
-    // replicas of the per-solve workspace (ws, gfac; the plain solver's dir too -- its x is the member's row) a launch may hold
-    // within the budget: the multi-start entry's rule
-    const size_t work_doubles = 5 * (size_t)L->nfree + (size_t)L->ngfac, dir_doubles = plain ? (size_t)p->N : 0;
-    const size_t rep_bytes = (work_doubles + dir_doubles) * sizeof(double);
+    // what a launch runs: the tiny-component solver on the first rest_tiny entries of the batch list (option population_tiny: the
+    // refusal above let them pass), the LDS-resident or the plain solver on the entries behind them, where there are any
+    // (without the option nothing but empty components can be among the first rest_tiny: the whole list goes to the other solver, as before)
+    const int ntiny = (L->population_tiny && !plain) ? L->rest_tiny : 0, nlisted = (int)L->h_rest.size() - ntiny;
+    const bool tiny_records = ntiny > 0 && L->rest_rot_mode == ROT_CAMFIX;   // (the tiny launch reads rotation records: a replica per member)
+    // replicas a launch may hold within the budget, the multi-start entry's rule.  A replica holds only what the launch's kernels
+    // read: ws and gfac where the LDS-resident or the plain solver runs (the plain solver's dir too -- its x is the member's row),
+    // the cameras' rotation records [N] where the tiny-component solver reads records
+    const size_t work_doubles = nlisted > 0 ? 5 * (size_t)L->nfree + (size_t)L->ngfac : 0, rot_doubles = tiny_records ? (size_t)p->N : 0;
+    const size_t dir_doubles = plain ? (size_t)p->N : 0;
+    const size_t rep_bytes = (work_doubles + rot_doubles + dir_doubles) * sizeof(double);
     int64_t R = rep_bytes ? std::max<int64_t>(1, L->starts_workspace_bytes / (int64_t)rep_bytes) : S_n;
     R = std::min(std::min(R, S_n), STARTS_MAX_PER_LAUNCH);
     int rc = 0;
-    if (L->ms_work.bytes < (size_t)R * work_doubles * sizeof(double)) rc = plan_alloc(L, L->ms_work, (size_t)R * work_doubles * sizeof(double));
+    const size_t work_bytes = (size_t)R * (work_doubles + rot_doubles) * sizeof(double);
+    if (L->ms_work.bytes < work_bytes) rc = plan_alloc(L, L->ms_work, work_bytes);
     if (!rc && plain && L->ms_dir.bytes < (size_t)R * dir_doubles * sizeof(double)) {
         rc = plan_alloc(L, L->ms_dir, (size_t)R * dir_doubles * sizeof(double));
         if (!rc) HIPCHK(c, hipMemsetAsync(L->ms_dir.p, 0, L->ms_dir.bytes, c->stream));   // (the kernel leaves what it wrote zero again)
     }
+    if (!rc && ntiny > 0 && L->ms_queue.bytes < (size_t)R * sizeof(int)) rc = plan_alloc(L, L->ms_queue, (size_t)R * sizeof(int));
     const size_t in_bytes = (size_t)S_n * (size_t)L->nfree * sizeof(double);
     if (!rc && L->ms_in.bytes < in_bytes) rc = plan_alloc(L, L->ms_in, in_bytes);
     if (!rc && L->ms_out.bytes < L->ms_out_bytes(S_n)) rc = plan_alloc(L, L->ms_out, L->ms_out_bytes(S_n));
@@ -2959,24 +2984,42 @@ extern "C" int rdis_hip_plan_solve_population(rdis_hip_plan* L, rdis_hip_populat
     L->ms_n = 0;   // (what an earlier call left is overwritten from here on)
 
     const ProblemView P = p->view();
-    PlanView V = L->view();   // (order: the whole batch list -- empty components and those of the plan's one solver, heaviest first)
+    PlanView V = L->view();   // (order: the whole batch list -- tiny components first, then empty ones and those of the plan's other solver, heaviest first)
     StartsView S = L->starts_view(S_n);
-    S.gfac = S.ws + (size_t)R * 5 * (size_t)L->nfree;
+    S.gfac = S.ws + (size_t)R * (work_doubles ? 5 * (size_t)L->nfree : 0);
+    double* const XR = tiny_records ? S.ws + (size_t)R * work_doubles : nullptr;   // [R][N], behind the launch's replicas of ws and gfac
     if (plain) S.dir = L->ms_dir.as<double>();   // (no replica of x: the member's row serves, solver_wg_population.hpp)
     // every member's start row: its own x at the plan's free variables (plan_set_start(plan, NULL) on that x)
     HIPCHK(c, population_gather_launch(c->stream, pop->X.as<double>(), p->N, V.free_vid, L->nfree, S_n, L->ms_in.as<double>()));
     const int threads = plain ? wg_launch_threads(L) : L->rest_lds > 0 ? lds_launch_threads(L) : 64;
     const size_t dyn = L->lds_dyn_bytes(c);
+    ProblemView PT = P;   // the tiny launch's: records of the launch's members or per-factor rotations (the quad solver has no refresh)
+    PT.rot_mode = tiny_records ? ROT_CAMFIX : ROT_PER_FACTOR;
+    PlanView VR = V;      // the other launch's: the batch list behind the tiny components
+    VR.order = V.order + ntiny;
     L->last_launches = 0;
+    L->ms_tiny_blocks = 0;
     L->timed = false;
     HIPCHK(c, hipEventRecord(p->ev0, c->stream));
     for (int64_t first = 0; first < S_n; first += R) {   // (launches on one stream: the next takes the replicas when this one is done)
         S.first = first;
         const int ns = (int)std::min(R, S_n - first);
-        if (plain) HIPCHK(c, population_launch_wg(threads, (int)L->h_rest.size(), ns, c->stream, P, V, S, pop->X.as<double>(), maxiters, ftol));
-        else HIPCHK(c, population_launch(L->lds_rot_mode, threads, (int)L->h_rest.size(), ns, dyn, c->stream, P, V, S, pop->X.as<double>(),
-                                    maxiters, ftol, L->lds_ns_cap, L->lds_ncb_cap, L->lds_chunk_cap));
-        ++L->last_launches;
+        if (ntiny > 0) {
+            // the records of THIS launch's members: the replicas held another launch's until now (solver_quad_population.hpp)
+            if (tiny_records) HIPCHK(c, population_rotations_launch(c->stream, pop->X.as<double>(), p->N, first, ns, p->cam_blocks.as<int>(), (int)p->ncam_blocks, XR));
+            HIPCHK(c, hipMemsetAsync(L->ms_queue.p, 0, (size_t)ns * sizeof(int), c->stream));
+            const int G = L->tiny_group == 4 ? 4 : 16;
+            const int gx = tiny_population_blocks(ntiny, (G == 4 ? QUAD_THREADS : 64) / G, L->tiny_population_fill * std::max(1, G == 4 ? L->group_blocks4 : L->group_blocks16), ns, L->tiny_max_blocks);
+            HIPCHK(c, population_launch_tiny(G, gx, ns, c->stream, PT, V, S, pop->X.as<double>(), XR, L->rest_order.as<int>(), ntiny, L->ms_queue.as<int>(), maxiters, ftol));
+            L->ms_tiny_blocks = gx;
+            ++L->last_launches;
+        }
+        if (nlisted > 0) {
+            if (plain) HIPCHK(c, population_launch_wg(threads, nlisted, ns, c->stream, P, VR, S, pop->X.as<double>(), maxiters, ftol));
+            else HIPCHK(c, population_launch(L->lds_rot_mode, threads, nlisted, ns, dyn, c->stream, P, VR, S, pop->X.as<double>(),
+                                        maxiters, ftol, L->lds_ns_cap, L->lds_ncb_cap, L->lds_chunk_cap));
+            ++L->last_launches;
+        }
     }
     HIPCHK(c, hipEventRecord(p->ev1, c->stream));
     L->timed = true;
@@ -3222,6 +3265,7 @@ extern "C" int rdis_hip_plan_get_info(rdis_hip_plan* L, const char* name, int64_
     else if (n == "point_major_round_slots") *value = L->rounds_slots;
     else if (n == "starts_per_launch") *value = L->ms_per_launch;
     else if (n == "starts_launches") *value = L->ms_launches;
+    else if (n == "population_tiny_blocks") *value = L->ms_tiny_blocks;
     else return fail(c, RDIS_HIP_EINVAL, "plan_get_info: unknown name '" + n + "'");
     return 0;
 }

@@ -2,7 +2,7 @@
 """Multi-start solves measured: rdis_hip_plan_solve_starts against the same starts solved one by one.
 
   python tools/bench_multistart.py            # both steps, one JSON line
-  python tools/bench_multistart.py --step config3|config5s|config2|population|population-nlp   # one step, in this process
+  python tools/bench_multistart.py --step config3|config5s|config2|population|population-nlp|population-tiny   # one step, in this process
 
 config3   BASELINE config 3 (ladybug 5 cameras / 30 points, one component): 320 one-ulp starts -- those of the end-value fixture,
           tests/golden/end_values.json -- in one call, and the same 320 by set_start / solve / fetch on the same plan.
@@ -16,6 +16,11 @@ population-nlp  the 121-variable sinusoid, 256 members drawn uniformly in the do
           free), then the three-subtree plan (the root constant: 3 x 40 variables, 3 x 120 factors) -- as two population launches on the
           plain solver (plan option population_plain; the subtree launch is 768 workgroups of 128 lanes), against the same round member
           by member through set_x / set_start(None) / solve / get_x.
+population-tiny  full ladybug, 64 members drawn from the sampling intervals, the POINT plan only (7776 components of three variables),
+          after one camera step on the population so that the members' cameras differ: (a) on the tiny-component solver (plan option
+          population_tiny), sixteen lanes a point; (b) the same with four lanes (quad_min_components = 1); (c) the way before that
+          option: row_min_components = 1 << 40, a 64-lane workgroup of the LDS-resident solver per point and member; (d) member by member
+          through set_x / set_start(None) / solve / get_x.  (a) again with 2 and 4 times the resident blocks (tiny_population_fill).
 Every step runs in a child process under a time limit of its own; a step that fails ends the run.  Wall times are the median of
 `--repeats` calls after one warm-up call; kernel_ms is rdis_hip_plan_last_kernel_ms of the last call."""
 import argparse
@@ -30,8 +35,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-STEP_LIMIT_S = {"config3": 240, "config5s": 240, "config2": 240, "population": 240, "population-nlp": 240}
-STEPS = ("config3", "config5s", "config2", "population", "population-nlp")
+STEP_LIMIT_S = {"config3": 240, "config5s": 240, "config2": 240, "population": 240, "population-nlp": 240, "population-tiny": 240}
+STEPS = ("config3", "config5s", "config2", "population", "population-nlp", "population-tiny")
 
 
 def ulp_perturbed(x0, rng):
@@ -225,8 +230,76 @@ def measure_population_nlp(repeats, members=256):
             "device_bytes": [p.device_bytes() for p in plans]}
 
 
+def measure_population_tiny(repeats, members=64):
+    """full ladybug's point plan on a population: the tiny-component solver (16 and 4 lanes) against a workgroup of the
+    LDS-resident solver per point and against one member at a time"""
+    from rdis_amd import capi, problems as P
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    from ba_multistart import sampling_intervals
+    pp = P.load_bal()
+    cams, pts = P.ba_alternation_plans(pp)
+    lo, hi = sampling_intervals(pp)
+    ctx = capi.Context(0)
+    g = capi.Problem(ctx, pp)
+    pop = capi.Population(g, x=np.random.default_rng(0).uniform(lo, hi, size=(members, pp.nvars)))
+    plan_c = capi.Plan(g, *cams)
+    for k in ("coop_min_factors", "coop_group_min_factors"):
+        plan_c.set_option(k, 0)
+    plan_c.solve_population(pop, 25, 3e-8)                 # one camera step: every member its own cameras
+    X = pop.get_x()
+    ways = {"tiny16": {"population_tiny": 1}, "tiny4": {"population_tiny": 1, "quad_min_components": 1},
+            "lds_workgroup_per_point": {"row_min_components": 1 << 40},
+            "tiny16_fill2": {"population_tiny": 1, "tiny_population_fill": 2}, "tiny16_fill4": {"population_tiny": 1, "tiny_population_fill": 4}}
+    out = {"members": members, "point_components": len(pts[0]) - 1}
+    rows = {}
+    for name, opts in ways.items():
+        plan = capi.Plan(g, *pts)
+        for k, v in opts.items():
+            plan.set_option(k, v)
+        tt = []
+        for it in range(repeats + 1):                      # (the first call is the warm-up)
+            pop.set_x(X)
+            t = time.perf_counter()
+            plan.solve_population(pop, 25, 3e-8)
+            ctx.synchronize()
+            tt.append(time.perf_counter() - t)
+        ms, launches = plan.last_kernel_ms()
+        rows[name] = pop.get_x()
+        out[name] = {"wall_ms": 1e3 * float(np.median(tt[1:])), "last_kernel_ms": ms, "launches": launches,
+                     "components_tiny": plan.info("components_tiny"), "components_lds": plan.info("components_lds"),
+                     "members_per_launch": plan.info("starts_per_launch"), "blocks_per_member": plan.info("population_tiny_blocks"),
+                     "device_bytes": plan.device_bytes()}
+        plan.close()
+    plan = capi.Plan(g, *pts)
+
+    def one_by_one():
+        res = np.empty_like(X)
+        t = time.perf_counter()
+        for s in range(members):
+            g.set_x(X[s])
+            plan.set_start(None)
+            plan.solve(25, 3e-8)
+            res[s] = g.get_x()
+        return time.perf_counter() - t, res
+
+    one_by_one()
+    ts = []
+    for _ in range(repeats):
+        dt, xs = one_by_one()
+        ts.append(dt)
+    out["member_by_member"] = {"wall_ms": 1e3 * float(np.median(ts)), "one_member_kernel_ms": plan.last_kernel_ms()[0],
+                               "components_tiny": plan.info("components_tiny")}
+    out["tiny16_bits_equal_member_by_member"] = bool(rows["tiny16"].tobytes() == xs.tobytes())
+    out["fill_changes_no_bit"] = bool(rows["tiny16"].tobytes() == rows["tiny16_fill2"].tobytes() == rows["tiny16_fill4"].tobytes())
+    base = out["lds_workgroup_per_point"]["last_kernel_ms"]
+    out["kernel_speedup_over_lds_workgroups"] = {k: base / out[k]["last_kernel_ms"] for k in ways if k != "lds_workgroup_per_point"}
+    return out
+
+
 def step(name, repeats):
     from rdis_amd import problems as P
+    if name == "population-tiny":
+        return measure_population_tiny(repeats)
     if name == "population":
         return measure_population(repeats)
     if name == "population-nlp":
