@@ -3,7 +3,7 @@
 src/RDISOptimizer.cpp:1196-1216), on the device: S whole states of ladybug 5 cameras / 30 points drawn from the sampling
 intervals live in a population, and every round runs the camera plan (points fixed) and then the point plan (cameras fixed)
 on ALL of them -- two launches a round, no host traffic in between: a member's constants are its own cameras / points.  After
-every round the members are evaluated (one call), and at the end the best one is assigned to the problem.  For comparison the
+every round the members are evaluated (one launch) and the best one selected on the device, and at the end it is assigned to the problem.  For comparison the
 same loop runs one member at a time on the problem itself (set_x, set_start(None), solve, get_x), the way without populations.
 
   python examples/ba_population.py [members] [rounds] [seed]
@@ -52,11 +52,12 @@ def main():
     for _ in range(rounds):
         for plan in plans:
             plan.solve_population(pop, 25, 3e-8)
-        f = pop.eval()
-        best.append(int(np.nanargmin(f)) if np.any(np.isfinite(f)) else 0)
-    pop.assign(best[-1])
+        pop.eval_device()                          # (all members in one launch, the values stay on the device)
+        best.append(pop.best()[0])                 # (selected there; kept per round for the line below: the round's one wait)
+    pop.assign_best()
     x_pop = pop.get_x()
     together = time.perf_counter() - t
+    f = pop.eval()
 
     t = time.perf_counter()
     x_seq = np.empty_like(X)
@@ -68,7 +69,7 @@ def main():
                 plan.solve(25, 3e-8)
         x_seq[s] = g.get_x()
     sequential = time.perf_counter() - t
-    pop.assign(best[-1])
+    pop.assign_best()
 
     ok = np.isfinite(f)
     print(f"{members} members from the sampling intervals, {rounds} rounds of camera plan + point plan, 25 CG iterations a solve "

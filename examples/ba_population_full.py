@@ -4,7 +4,7 @@ whole states drawn from the sampling intervals live in a population, and every r
 components of hundreds of factors, on the LDS-resident solver) and then the point plan (cameras fixed: 7776 components of three
 variables, on the tiny-component solver, sixteen lanes a point) on ALL of them.  The point plan takes the plan option
 "population_tiny" = 1 (solver_quad_population.hpp): every member's blocks walk that member's points, with rotation records of
-the member's own cameras.  After every round the members are evaluated (one call); at the end the best one is assigned to the
+the member's own cameras.  After every round the members are evaluated (one launch) and the best one selected on the device; at the end it is assigned to the
 problem.  For comparison the same loop runs one member at a time on the problem itself (set_x, set_start(None), solve, get_x)
 with the same plan options.
 
@@ -50,11 +50,12 @@ def main():
     for _ in range(rounds):
         for plan in plans:
             plan.solve_population(pop, 25, 3e-8)
-        f = pop.eval()
-        best.append(int(np.nanargmin(f)) if np.any(np.isfinite(f)) else 0)
-    pop.assign(best[-1])
+        pop.eval_device()                          # (all members in one launch, the values stay on the device)
+        best.append(pop.best()[0])                 # (selected there; kept per round for the line below: the round's one wait)
+    pop.assign_best()
     x_pop = pop.get_x()
     together = time.perf_counter() - t
+    f = pop.eval()
 
     t = time.perf_counter()
     x_seq = np.empty_like(X)
@@ -66,7 +67,7 @@ def main():
                 plan.solve(25, 3e-8)
         x_seq[s] = g.get_x()
     sequential = time.perf_counter() - t
-    pop.assign(best[-1])
+    pop.assign_best()
 
     ok = np.isfinite(f)
     print(f"full ladybug, {members} members from the sampling intervals, {rounds} rounds of camera plan ({plans[0].ncomp} components, LDS-resident "

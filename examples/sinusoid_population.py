@@ -5,7 +5,7 @@ device: S whole states drawn uniformly in the variables' domains live in a popul
 (variable 0 free, the subtrees constants) and then the three-subtree plan (the root constant) on ALL of them -- two launches a
 round, one workgroup of the plain solver per (component, member), no host traffic in between: a member's constants are its own
 earlier results, which examples/sinusoid_multistart.py, with the root at one value for all starts, cannot do.  After the rounds
-the members are evaluated (one call), the host picks the lowest, and that member is assigned to the problem.  For comparison
+the members are evaluated (one launch), the lowest is selected on the device, and that member is assigned to the problem.  For comparison
 the same loop runs one member at a time on the problem itself (set_x, set_start(None), solve, get_x), the way without
 populations.
 
@@ -44,11 +44,12 @@ def main():
     for _ in range(rounds):
         for plan in plans:
             plan.solve_population(pop, 25, 3e-8)
-    f = pop.eval()
-    best = int(np.nanargmin(f)) if np.any(np.isfinite(f)) else 0
-    pop.assign(best)
+    pop.eval_device()                              # (all members in one launch, the values stay on the device)
+    pop.assign_best()                              # (the lowest is selected and assigned there: nothing waited for)
     x_pop = pop.get_x()
     together = time.perf_counter() - t
+    best, _ = pop.best()
+    f = pop.eval()
 
     t = time.perf_counter()
     x_seq = np.empty_like(X)
@@ -60,7 +61,7 @@ def main():
                 plan.solve(25, 3e-8)
         x_seq[s] = g.get_x()
     sequential = time.perf_counter() - t
-    pop.assign(best)
+    pop.assign_best()
 
     ok = np.isfinite(f)
     print(f"{members} uniform members, {rounds} rounds of root plan ({plans[0].ncomp} component) + subtree plan "

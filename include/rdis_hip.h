@@ -284,9 +284,35 @@ int rdis_hip_plan_fetch_starts(rdis_hip_plan *plan, double *x_out, double *fret,
  *                       vid == NULL: variables 0..n-1 (n <= N); ids and ranges checked like rdis_hip_set_x.
  *   population_assign   the problem's assigned x := that member's x (asynchronous on the context's stream).
  *   population_eval     f[s], s < nmembers: bit for bit what rdis_hip_eval(p, nf, fac, .) returns when member s's x is the
- *                       assigned x -- the same kernels with x replaced, the rotation records of a long bundle-adjustment
+ *                       assigned x -- the same statements with x replaced, the rotation records of a long bundle-adjustment
  *                       list rebuilt from the member's x --, all members enqueued without a wait, one copy back.  The
- *                       problem's assigned x and what eval_grad_device handed out are left as they were.
+ *                       problem's assigned x and what eval_grad_device handed out are left as they were.  The members are a
+ *                       dimension of the grid: per launch of R members one kernel for the chunk (or block) sums and one
+ *                       final-sum workgroup per member, preceded on the rotation-records branch by the records of THAT
+ *                       launch's members -- two or three kernels for the whole population, not per member.  The scratch
+ *                       (R x partial sums, R x N records) is the population's own, bounded by the population option
+ *                       "eval_workspace_bytes": R = min(nmembers, 65535, max(1, bytes / bytes per member)), ceil(nmembers / R)
+ *                       launches, the same bits however it is split.  The problem's scalar, partial sums and rotation
+ *                       records are not written.
+ *   population_eval_device   the same evaluation left on the device: *f_dev points at f[nmembers], valid until the next
+ *                       evaluation of the population.  With fac == NULL nothing is waited for; an explicit list is staged
+ *                       like every id list (one synchronisation).
+ *   population_best     the argmin of the last evaluation: member and its value.  The rule is plan_solve_starts' selection:
+ *                       the lowest value; on a tie (-0.0 against +0.0 is one) the lowest index; a NaN never, unless every
+ *                       value is one: then member 0.  Selected on the device; one copy of 16 bytes and one synchronisation.
+ *   population_assign_best   the same selection, then the problem's assigned x := X[best], the index read on the device:
+ *                       enqueued, no wait, no host round trip.  Afterwards the problem is as population_assign(best) leaves it.
+ *                       So rounds x (plan_solve_population ..., population_eval_device, population_assign_best) run without
+ *                       a synchronisation until the caller asks for a result.
+ *                       best / assign_best refer to the last evaluation of this population (whatever list it took).
+ *                       population_set_x and plan_solve_population write X and mark its values stale; before any evaluation
+ *                       or with stale values both return RDIS_HIP_EINVAL ("evaluate first") and change nothing.
+ *                       population_assign, _get_x and evaluations do not invalidate.
+ *   population_set_option   "eval_workspace_bytes" (default 2^30, the default of "starts_workspace_bytes"; >= 0; lowering it
+ *                       releases scratch beyond it), "eval_batched" (default 1; 0 = the evaluation member by member through
+ *                       the problem's scratch, two or three launches a member: the yardstick of the batched path).
+ *   population_get_info     "eval_members_per_launch" (R of the last evaluation), "eval_launches" (kernels it launched),
+ *                       "eval_valid" (1: best / assign_best are served).  Unknown names: RDIS_HIP_EINVAL.
  *   plan_solve_population   asynchronous on the context's stream.  For every member s and component c exactly what
  *                       plan_set_start(plan, NULL) + plan_solve would do on a problem whose assigned x is X[s] -- the same
  *                       bits in fret, delta, x, iters, status, nfeval, ngeval: the start is X[s][free_vid], clamped at
@@ -333,6 +359,11 @@ int rdis_hip_population_get_x(rdis_hip_population *pop, int64_t first, int64_t c
                               double *out);
 int rdis_hip_population_assign(rdis_hip_population *pop, int64_t member);
 int rdis_hip_population_eval(rdis_hip_population *pop, int64_t nf, const int64_t *fac, double *f);
+int rdis_hip_population_eval_device(rdis_hip_population *pop, int64_t nf, const int64_t *fac, void **f_dev);
+int rdis_hip_population_best(rdis_hip_population *pop, int64_t *member, double *f);
+int rdis_hip_population_assign_best(rdis_hip_population *pop);
+int rdis_hip_population_set_option(rdis_hip_population *pop, const char *name, int64_t value);
+int rdis_hip_population_get_info(rdis_hip_population *pop, const char *name, int64_t *value);
 int rdis_hip_plan_solve_population(rdis_hip_plan *plan, rdis_hip_population *pop, int32_t maxiters, double ftol);
 int rdis_hip_plan_fetch_population(rdis_hip_plan *plan, double *x_out, double *fret, double *delta, int32_t *iters,
                                    int32_t *status, int64_t *nfeval, int64_t *ngeval);

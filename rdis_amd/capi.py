@@ -86,6 +86,11 @@ SYMBOLS = {
     "rdis_hip_population_get_x": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "rdis_hip_population_assign": (C.c_int, [_vp, _i64]),
     "rdis_hip_population_eval": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "rdis_hip_population_eval_device": (C.c_int, [_vp, _i64, _vp, C.POINTER(_vp)]),
+    "rdis_hip_population_best": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
+    "rdis_hip_population_assign_best": (C.c_int, [_vp]),
+    "rdis_hip_population_set_option": (C.c_int, [_vp, C.c_char_p, _i64]),
+    "rdis_hip_population_get_info": (C.c_int, [_vp, C.c_char_p, C.POINTER(_i64)]),
     "rdis_hip_plan_solve_population": (C.c_int, [_vp, _vp, C.c_int32, C.c_double]),
     "rdis_hip_plan_fetch_population": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rdis_hip_plan_objective_device": (C.c_int, [_vp, C.POINTER(_vp)]),
@@ -488,6 +493,35 @@ class Population:
         f = np.empty(self.nmembers)
         self.ctx.check(self.ctx.lib.rdis_hip_population_eval(self.h, nf, _ptr(fac), _ptr(f)))
         return f
+
+    def eval_device(self, fac=None) -> int:
+        """the same evaluation left on the device: the address of f[nmembers] (Context.copy_to_host reads it).  fac=None: nothing
+        is waited for"""
+        fac, nf = self.prob._nf(fac)
+        fd = _vp()
+        self.ctx.check(self.ctx.lib.rdis_hip_population_eval_device(self.h, nf, _ptr(fac), C.byref(fd)))
+        return fd.value
+
+    def best(self):
+        """(member, f): the argmin of the last evaluation, selected on the device -- the lowest value, the lowest index on a tie,
+        a NaN never unless all are (then member 0).  EINVAL before an evaluation or after set_x / Plan.solve_population"""
+        m, f = _i64(), C.c_double()
+        self.ctx.check(self.ctx.lib.rdis_hip_population_best(self.h, C.byref(m), C.byref(f)))
+        return int(m.value), float(f.value)
+
+    def assign_best(self):
+        """the problem's assigned x := the x of the last evaluation's best member; enqueued, nothing waited for"""
+        self.ctx.check(self.ctx.lib.rdis_hip_population_assign_best(self.h))
+
+    def set_option(self, name: str, value: int):
+        """eval_workspace_bytes (scratch of a launch of the evaluation; default 2^30), eval_batched (default 1; 0: member by member)"""
+        self.ctx.check(self.ctx.lib.rdis_hip_population_set_option(self.h, name.encode(), int(value)))
+
+    def info(self, name: str) -> int:
+        """eval_members_per_launch, eval_launches (kernels of the last evaluation), eval_valid"""
+        v = _i64()
+        self.ctx.check(self.ctx.lib.rdis_hip_population_get_info(self.h, name.encode(), C.byref(v)))
+        return int(v.value)
 
 
 class Comm:

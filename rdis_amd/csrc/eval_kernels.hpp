@@ -66,27 +66,34 @@ __device__ __forceinline__ double block_sum(double v, double* red /* [MAX_WAVES]
     return r;
 }
 
-// f partial per block (+ optionally the per-factor partials for the gradient)
+// a block's share of the listed factors (block bx of nb, grid-stride), added per lane in list order and then over the block:
+// the one definition of eval_sum_kernel's sum and of its population form's
 template <int KIND, bool GRAD>
-__global__ void __launch_bounds__(256)
-eval_sum_kernel(ProblemView P, int nf, const int* __restrict__ fac, double* __restrict__ gfac,
-                double* __restrict__ block_partial) {
-    __shared__ double red[MAX_WAVES];
+__device__ __forceinline__ double eval_sum_of(const ProblemView& P, int nf, const int* __restrict__ fac, double* __restrict__ gfac, int bx, int nb,
+                                              double* red /* [MAX_WAVES] */) {
     double acc = 0.0;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nf; i += gridDim.x * blockDim.x) {
+    for (int i = bx * blockDim.x + threadIdx.x; i < nf; i += nb * blockDim.x) {
         const int fid = fac ? fac[i] : i;
         double f, s;
         factor_value<KIND, false>(P, nullptr, fid, f, s);
         acc += f;
         if constexpr (GRAD) factor_partials<KIND>(P, gfac, nullptr, fid);
     }
-    acc = block_sum(acc, red);
+    return block_sum(acc, red);
+}
+
+// f partial per block (+ optionally the per-factor partials for the gradient)
+template <int KIND, bool GRAD>
+__global__ void __launch_bounds__(256)
+eval_sum_kernel(ProblemView P, int nf, const int* __restrict__ fac, double* __restrict__ gfac,
+                double* __restrict__ block_partial) {
+    __shared__ double red[MAX_WAVES];
+    const double acc = eval_sum_of<KIND, GRAD>(P, nf, fac, gfac, (int)blockIdx.x, (int)gridDim.x, red);
     if (threadIdx.x == 0) block_partial[blockIdx.x] = acc;
 }
 
-__global__ void __launch_bounds__(256)
-final_sum_kernel(int n, const double* __restrict__ partial, double* __restrict__ out) {
-    __shared__ double red[MAX_WAVES];
+// partial[0 .. n) added by one workgroup: the one definition of final_sum_kernel's sum and of its population form's
+__device__ __forceinline__ double final_sum_of(int n, const double* __restrict__ partial, double* red /* [MAX_WAVES] */) {
     double acc = 0.0;
     // (eight loads in flight, added in index order: the bits of the plain loop without its round trip per element)
     for (int i0 = threadIdx.x; i0 < n; i0 += 8 * blockDim.x) {
@@ -97,8 +104,82 @@ final_sum_kernel(int n, const double* __restrict__ partial, double* __restrict__
         for (int j = 0; j < 8; ++j)
             if (i0 + j * (int)blockDim.x < n) acc += t[j];
     }
-    acc = block_sum(acc, red);
+    return block_sum(acc, red);
+}
+
+__global__ void __launch_bounds__(256)
+final_sum_kernel(int n, const double* __restrict__ partial, double* __restrict__ out) {
+    __shared__ double red[MAX_WAVES];
+    const double acc = final_sum_of(n, partial, red);
     if (threadIdx.x == 0) out[0] = acc;
+}
+
+// ---- the evaluation of a population, the member a grid dimension (rdis_hip.hip: population_eval_enqueue) ----
+// Block (., r) is member first + r of X[members][N]: the view's x becomes the member's row (wave-uniform: scalar registers), the
+// statement and so the bits are those of the single-x kernel above.  partial: [members of the launch][nb], the population's own.
+
+// eval_sum_kernel<KIND, false> per member: grid (nb, members of the launch), nb the block count rdis_hip_eval takes for nf
+template <int KIND>
+__global__ void __launch_bounds__(256)
+population_eval_sum_kernel(ProblemView P, double* __restrict__ X, long long first, int nf, const int* __restrict__ fac,
+                           double* __restrict__ partial) {
+    __shared__ double red[MAX_WAVES];
+    const long long r = blockIdx.y;
+    P.x = X + (first + r) * (long long)P.N;
+    const double acc = eval_sum_of<KIND, false>(P, nf, fac, nullptr, (int)blockIdx.x, (int)gridDim.x, red);
+    if (threadIdx.x == 0) partial[r * gridDim.x + blockIdx.x] = acc;
+}
+
+// final_sum_kernel per member: grid (members of the launch), f[first + r] = the sum of partial[r][0 .. n)
+__global__ void __launch_bounds__(256)
+population_final_sum_kernel(int n, const double* __restrict__ partial, long long first, double* __restrict__ f) {
+    __shared__ double red[MAX_WAVES];
+    const long long r = blockIdx.x;
+    const double acc = final_sum_of(n, partial + r * n, red);
+    if (threadIdx.x == 0) f[first + r] = acc;
+}
+
+// The member a population keeps, the minimum of f[members]: select_best_start_kernel's rule (solver_lds_starts.hpp), which as a
+// sequential scan reads  b = 0; for s >= 1: if (f[s] < f[b] || (f[b] != f[b] && f[s] == f[s])) b = s  -- the lowest value, on a
+// tie (-0.0 against +0.0 is one) the lowest index, a NaN never unless every value is one: then member 0.  better() is that rule as
+// a strict total order on (value, index) pairs with distinct indices, so the winner is the same whatever the reduction's shape.
+struct MemberValue { double f; long long s; };
+__device__ __forceinline__ bool better(double fa, long long sa, double fb, long long sb) {
+    const bool na = fa != fa, nb = fb != fb;
+    if (na != nb) return nb;              // a number beats a NaN
+    if (!na && fa != fb) return fa < fb;  // two different numbers: the lower
+    return sa < sb;                       // a tie, or two NaNs: the lower index
+}
+// one workgroup of 256 lanes; lanes stride over the members, then wave shuffles, then the waves' winners through LDS
+__global__ void __launch_bounds__(256)
+population_argmin_kernel(long long members, const double* __restrict__ f, MemberValue* __restrict__ best) {
+    __shared__ double wf[MAX_WAVES];
+    __shared__ long long ws[MAX_WAVES];
+    double bf = __builtin_nan("");
+    long long bs = INT64_MAX;             // (no member yet: loses against every member, NaN or not)
+    for (long long s = threadIdx.x; s < members; s += blockDim.x) {
+        const double v = f[s];
+        if (better(v, s, bf, bs)) { bf = v; bs = s; }
+    }
+    for (int m = 1; m < 64; m <<= 1) {
+        const double of = __shfl_xor(bf, m, 64);
+        const long long os = __shfl_xor(bs, m, 64);
+        if (better(of, os, bf, bs)) { bf = of; bs = os; }
+    }
+    if ((threadIdx.x & 63) == 0) { wf[threadIdx.x >> 6] = bf; ws[threadIdx.x >> 6] = bs; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < (int)(blockDim.x >> 6); ++w)
+            if (better(wf[w], ws[w], bf, bs)) { bf = wf[w]; bs = ws[w]; }
+        best->f = bf; best->s = bs;
+    }
+}
+
+// x[0 .. N) = X[best->s][0 .. N): the member's index read on the device (grid-stride, plain stores)
+__global__ void __launch_bounds__(256)
+population_copy_best_kernel(const double* __restrict__ X, long long N, const MemberValue* __restrict__ best, double* __restrict__ x) {
+    const double* row = X + best->s * N;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) x[i] = row[i];
 }
 
 // g[v] = sum of the slots that feed v, in factor-list order (src/State.h:157-210)

@@ -54,6 +54,34 @@ eval_chunks_kernel(ProblemView P, int nf, const int* __restrict__ fac, double* _
     }
 }
 
+// eval_chunks_kernel<KIND_BA, ROT> on a population X[members][N]: grid (chunk blocks, members of the launch); block (., r) is
+// member first + r -- the view's x becomes its row (wave-uniform: scalar registers) and, with ROT_CAMFIX, the view's records
+// replica r of XR[members of the launch][N], which population_rotations_kernel filled for THIS launch.  partial:
+// [members of the launch][nchunks].  The loop is eval_chunks_kernel's, RESTATED line by line (moving it into a function the two
+// kernels share changes that kernel's scalar registers): factor_value, wave_sum, then the waves in order by chunk_sum_of -- a
+// change to either loop is a change to both.
+template <int ROT>
+__global__ void __launch_bounds__(GRAD_LANES)
+population_eval_chunks_kernel(ProblemView P, double* __restrict__ X, long long first, double* __restrict__ XR, int nf, const int* __restrict__ fac,
+                              double* __restrict__ partial) {
+    __shared__ double red[GRAD_LANES / 64];
+    const long long r = blockIdx.y;
+    P.x = X + (first + r) * (long long)P.N;
+    if constexpr (ROT == ROT_CAMFIX) P.xrot = XR + r * (long long)P.N;
+    const int nchunks = (nf + GRAD_LANES - 1) / GRAD_LANES;
+    partial += r * nchunks;
+    for (int ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+        const int j = ch * GRAD_LANES + (int)threadIdx.x;
+        double f = 0.0, s;
+        if (j < nf) factor_value<KIND_BA, false, ROT>(P, nullptr, fac ? fac[j] : j, f, s);
+        f = wave_sum(f);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = f;
+        __syncthreads();
+        if (threadIdx.x == 0) partial[ch] = chunk_sum_of(red);
+        __syncthreads();
+    }
+}
+
 // rows [r0, r1) of a staging area (row stride STRIDE doubles, entry k), added to `s` in row order, eight loads in flight
 template <int STRIDE>
 __device__ __forceinline__ double add_rows(double s, const double* __restrict__ rows, int r0, int r1, int k) {
@@ -288,6 +316,14 @@ hipError_t grad_combine_launch(hipStream_t s, int grid, const GradTables& T, con
     grad_combine_kernel<<<grid, 256, 0, s>>>(T, cstage, pstage, g);
     return hipGetLastError();
 }
+hipError_t population_eval_chunks_launch(hipStream_t s, int grid, int members_of_launch, const ProblemView& P, double* X, long long first, double* XR,
+                                         int nf, const int* fac, double* partial) {
+    const dim3 g((unsigned)grid, (unsigned)members_of_launch);
+    if (XR != nullptr) population_eval_chunks_kernel<ROT_CAMFIX><<<g, GRAD_LANES, 0, s>>>(P, X, first, XR, nf, fac, partial);
+    else population_eval_chunks_kernel<ROT_PER_FACTOR><<<g, GRAD_LANES, 0, s>>>(P, X, first, nullptr, nf, fac, partial);
+    return hipGetLastError();
+}
+
 hipError_t eval_chunks_launch(hipStream_t s, int grid, const ProblemView& P, int nf, const int* fac, double* partial) {
     if (P.kind == KIND_BA && P.rot_mode == ROT_CAMFIX && P.xrot != nullptr) eval_chunks_kernel<KIND_BA, ROT_CAMFIX><<<grid, GRAD_LANES, 0, s>>>(P, nf, fac, partial);
     else if (P.kind == KIND_BA) eval_chunks_kernel<KIND_BA><<<grid, GRAD_LANES, 0, s>>>(P, nf, fac, partial);

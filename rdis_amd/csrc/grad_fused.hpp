@@ -83,5 +83,9 @@ hipError_t grad_fused_launch(hipStream_t s, int grid, size_t dyn, const GradTabl
 hipError_t grad_combine_launch(hipStream_t s, int grid, const GradTables& T, const double* cstage, const double* pstage, double* g);
 // the value alone, chunk by chunk: the same per-chunk sums as grad_fused_launch leaves in `partial` (same bits)
 hipError_t eval_chunks_launch(hipStream_t s, int grid, const ProblemView& P, int nf, const int* fac, double* partial);
+// ... of a population X[members][N] (bundle adjustment), grid (grid, members_of_launch): member first + r's chunk sums to
+// partial[r][nchunks]; XR null: every factor forms its rotation; else the launch's rotation records [members_of_launch][N]
+hipError_t population_eval_chunks_launch(hipStream_t s, int grid, int members_of_launch, const ProblemView& P, double* X, long long first, double* XR,
+                                         int nf, const int* fac, double* partial);
 
 }  // namespace rdis_hip

@@ -1,5 +1,6 @@
-// population_grid.hpp -- the grid of the tiny-component solver's population launch (solver_quad_population.hpp), a pure host
-// function: no HIP call, no plan (tests/cpp/population_tiny_grid_test.cpp runs it without a device).
+// population_grid.hpp -- the grid of the tiny-component solver's population launch (solver_quad_population.hpp) and the members
+// of a launch of the population's evaluation, pure host functions: no HIP call, no plan (tests/cpp/population_tiny_grid_test.cpp
+// and tests/cpp/population_eval_members_test.cpp run them without a device).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -16,6 +17,18 @@ inline int tiny_population_blocks(int64_t ntiny, int groups_per_block, int resid
     int64_t gx = std::min(need, std::max<int64_t>(1, (res + mem - 1) / mem));
     if (cap > 0) gx = std::min<int64_t>(gx, cap);
     return (int)std::min<int64_t>(gx, INT32_MAX);
+}
+
+// Members of one launch of the population's evaluation (rdis_hip_population_eval): the member is the grid's second dimension
+// (at most 65535), and every member of a launch has scratch of its own -- `partials_per_member` doubles (the chunks' or blocks'
+// sums) and, where the launch reads rotation records (`records`), a replica of `nvars` doubles -- within `budget_bytes` (the
+// population option eval_workspace_bytes).  At least one member a launch, whatever the budget.  No bit of a result depends on it.
+inline int64_t eval_member_bytes(int64_t partials_per_member, int64_t nvars, bool records) {
+    return 8 * (std::max<int64_t>(partials_per_member, 1) + (records ? std::max<int64_t>(nvars, 0) : 0));
+}
+inline int64_t eval_members_per_launch(int64_t members, int64_t budget_bytes, int64_t partials_per_member, int64_t nvars, bool records) {
+    const int64_t fit = std::max<int64_t>(1, budget_bytes / eval_member_bytes(partials_per_member, nvars, records));
+    return std::max<int64_t>(1, std::min(std::min<int64_t>(members, 65535), fit));
 }
 
 }  // namespace rdis_hip

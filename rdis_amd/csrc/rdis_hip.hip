@@ -2819,6 +2819,15 @@ struct rdis_hip_population {
     DevBuf X;                  // [nmembers][N]
     DevBuf f;                  // [nmembers] values of the last population_eval
     DevBuf tmp_val, tmp_out;   // staging of set_x / get_x
+    // the batched evaluation (population_eval_enqueue): scratch of the population's own, per member of a launch
+    DevBuf eval_partial;       // [R][chunks or blocks] the members' partial sums
+    DevBuf eval_xr;            // [R][N] the members' rotation records (the records branch only)
+    DevBuf best;               // one MemberValue: the argmin of f (population_argmin_kernel)
+    int64_t eval_workspace_bytes = (int64_t)1 << 30;   // option "eval_workspace_bytes": bounds eval_partial + eval_xr
+    int eval_batched = 1;      // option "eval_batched": 0 = member by member through the problem's scratch (enqueue_eval)
+    int64_t eval_per_launch = 0, eval_launches = 0;    // of the last evaluation: members of a launch, kernels launched
+    bool eval_valid = false;   // f holds the values of X as it is (set_x and plan_solve_population write X: stale)
+    bool best_current = false; // best holds the argmin of f
     double* row(int64_t s) const { return X.as<double>() + (size_t)s * (size_t)prob->N; }
 };
 
@@ -2872,6 +2881,7 @@ extern "C" int rdis_hip_population_set_x(rdis_hip_population* pop, int64_t first
     if (rc) return rc;
     if (n == 0 || count == 0) return 0;
     USE_DEVICE(c);
+    pop->eval_valid = false; pop->best_current = false;   // X is written: the values of the last evaluation are stale
     const size_t bytes = (size_t)count * (size_t)n * sizeof(double);
     if (!vid && n == p->N) {   // whole rows: straight into place
         HIPCHK(c, hipMemcpyAsync(pop->row(first), val, bytes, hipMemcpyHostToDevice, c->stream));
@@ -2920,21 +2930,154 @@ extern "C" int rdis_hip_population_assign(rdis_hip_population* pop, int64_t memb
     return 0;
 }
 
-extern "C" int rdis_hip_population_eval(rdis_hip_population* pop, int64_t nf, const int64_t* fac, double* f) {
-    if (!pop || !f) return RDIS_HIP_EINVAL;
+namespace {
+// f[s] for every member, enqueued on the context's stream: pop->f on the device, nothing waited for.
+// Batched (the default): the member is the grid's second dimension -- per launch of R members (population_grid.hpp) the rotation
+// records of ITS members on the records branch (a replica serves another member in the next launch: rebuilt before every launch,
+// the invariant of solver_quad_population.hpp), the chunk or block sums, one final-sum workgroup per member.  The branch, the
+// chunk size and the block count are enqueue_eval's, so f[s] has rdis_hip_eval's bits.  The scratch is the population's: the
+// problem's x, scalar, partial and xrot are not written.
+int population_eval_enqueue(rdis_hip_population* pop, int64_t nf, const int* dfac) {
+    rdis_hip_problem* p = pop->prob;
+    rdis_hip_ctx* c = p->ctx;
+    const int64_t S_n = pop->nmembers;
+    int rc;
+    pop->eval_valid = false; pop->best_current = false;
+    if (nf == 0) {
+        HIPCHK(c, hipMemsetAsync(pop->f.p, 0, (size_t)S_n * sizeof(double), c->stream));
+        pop->eval_per_launch = S_n; pop->eval_launches = 0; pop->eval_valid = true;
+        return 0;
+    }
+    const bool fused = fused_path(p), records = fused && nf >= 4 * p->ncam_blocks;
+    if (!pop->eval_batched) {
+        // member by member, rdis_hip_eval's kernels with the view's x replaced, through the problem's partial / xrot
+        for (int64_t s = 0; s < S_n; ++s)
+            if ((rc = enqueue_eval(p, pop->row(s), nf, dfac, pop->f.as<double>() + s))) return rc;
+        pop->eval_per_launch = 1; pop->eval_launches = S_n * (records ? 3 : 2); pop->eval_valid = true;
+        return 0;
+    }
+    const int64_t per = fused ? (nf + GRAD_LANES - 1) / GRAD_LANES : grid_for(c, nf, 256);   // a member's partials: chunks, or enqueue_eval's blocks
+    const int64_t R = eval_members_per_launch(S_n, pop->eval_workspace_bytes, per, p->N, records);
+    if ((rc = ensure(c, pop->eval_partial, (size_t)R * (size_t)per * sizeof(double)))) return rc;
+    if (records && (rc = ensure(c, pop->eval_xr, (size_t)R * (size_t)p->N * sizeof(double)))) return rc;
+    const ProblemView V = p->view();
+    double *X = pop->X.as<double>(), *part = pop->eval_partial.as<double>(), *XR = records ? pop->eval_xr.as<double>() : nullptr;
+    int64_t launches = 0;
+    for (int64_t first = 0; first < S_n; first += R) {
+        const int ns = (int)std::min<int64_t>(R, S_n - first);
+        if (fused) {
+            if (records) {
+                HIPCHK(c, population_rotations_launch(c->stream, X, p->N, first, ns, p->cam_blocks.as<int>(), (int)p->ncam_blocks, XR));
+                ++launches;
+            }
+            HIPCHK(c, population_eval_chunks_launch(c->stream, (int)std::min<int64_t>(per, 16 * std::max(1, c->num_cus)), ns, V, X, first, XR, (int)nf, dfac, part));
+        } else {
+            const dim3 grid((unsigned)per, (unsigned)ns);
+            if (p->kind == KIND_BA) population_eval_sum_kernel<KIND_BA><<<grid, 256, 0, c->stream>>>(V, X, first, (int)nf, dfac, part);
+            else population_eval_sum_kernel<KIND_NLP><<<grid, 256, 0, c->stream>>>(V, X, first, (int)nf, dfac, part);
+            HIPCHK(c, hipGetLastError());
+        }
+        population_final_sum_kernel<<<ns, 256, 0, c->stream>>>((int)per, part, first, pop->f.as<double>());
+        HIPCHK(c, hipGetLastError());
+        launches += 2;
+    }
+    pop->eval_per_launch = R; pop->eval_launches = launches; pop->eval_valid = true;
+    return 0;
+}
+
+// the argmin of the last evaluation, left in pop->best (enqueued; once per evaluation)
+int population_select(rdis_hip_population* pop, const char* who) {
+    rdis_hip_ctx* c = pop->prob->ctx;
+    if (!pop->eval_valid)
+        return fail(c, RDIS_HIP_EINVAL, std::string(who) + ": the population has no current values (evaluate first: rdis_hip_population_eval or "
+                                        "_eval_device after the last population_set_x / plan_solve_population)");
+    if (pop->best_current) return 0;
+    int rc;
+    if ((rc = ensure(c, pop->best, sizeof(MemberValue)))) return rc;
+    population_argmin_kernel<<<1, 256, 0, c->stream>>>((long long)pop->nmembers, pop->f.as<double>(), pop->best.as<MemberValue>());
+    HIPCHK(c, hipGetLastError());
+    pop->best_current = true;
+    return 0;
+}
+}  // namespace
+
+extern "C" int rdis_hip_population_eval_device(rdis_hip_population* pop, int64_t nf, const int64_t* fac, void** f_dev) {
+    if (!pop || !f_dev) return RDIS_HIP_EINVAL;
     rdis_hip_problem* p = pop->prob;
     rdis_hip_ctx* c = p->ctx;
     int rc = check_list(p, nf, fac);
     if (rc) return rc;
     USE_DEVICE(c);
-    if (nf == 0) { std::fill(f, f + pop->nmembers, 0.0); return 0; }
-    const int* dfac;
-    if ((rc = stage_ids(p, nf, fac, p->F, &dfac))) return rc;
-    // member by member on the stream, rdis_hip_eval's kernels with the view's x replaced: no wait in between, one copy back
-    for (int64_t s = 0; s < pop->nmembers; ++s)
-        if ((rc = enqueue_eval(p, pop->row(s), nf, dfac, pop->f.as<double>() + s))) return rc;
-    HIPCHK(c, hipMemcpyAsync(f, pop->f.p, (size_t)pop->nmembers * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    const int* dfac = nullptr;
+    if (nf > 0 && (rc = stage_ids(p, nf, fac, p->F, &dfac))) return rc;
+    if ((rc = population_eval_enqueue(pop, nf, dfac))) return rc;
+    *f_dev = pop->f.p;
+    return 0;
+}
+
+extern "C" int rdis_hip_population_eval(rdis_hip_population* pop, int64_t nf, const int64_t* fac, double* f) {
+    if (!pop || !f) return RDIS_HIP_EINVAL;
+    void* fd;
+    int rc = rdis_hip_population_eval_device(pop, nf, fac, &fd);
+    if (rc) return rc;
+    rdis_hip_ctx* c = pop->prob->ctx;
+    HIPCHK(c, hipMemcpyAsync(f, fd, (size_t)pop->nmembers * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int rdis_hip_population_best(rdis_hip_population* pop, int64_t* member, double* f) {
+    if (!pop || !member || !f) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = pop->prob->ctx;
+    USE_DEVICE(c);
+    if (int rc = population_select(pop, "population_best")) return rc;
+    MemberValue b;
+    HIPCHK(c, hipMemcpyAsync(&b, pop->best.p, sizeof b, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *member = (int64_t)b.s; *f = b.f;
+    return 0;
+}
+
+extern "C" int rdis_hip_population_assign_best(rdis_hip_population* pop) {
+    if (!pop) return RDIS_HIP_EINVAL;
+    rdis_hip_problem* p = pop->prob;
+    rdis_hip_ctx* c = p->ctx;
+    USE_DEVICE(c);
+    if (int rc = population_select(pop, "population_assign_best")) return rc;
+    if (p->N > 0) {
+        population_copy_best_kernel<<<grid_for(c, p->N, 256), 256, 0, c->stream>>>(pop->X.as<double>(), (long long)p->N, pop->best.as<MemberValue>(), p->x.as<double>());
+        HIPCHK(c, hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int rdis_hip_population_set_option(rdis_hip_population* pop, const char* name, int64_t value) {
+    if (!pop || !name) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = pop->prob->ctx;
+    const std::string n(name);
+    if (n == "eval_workspace_bytes") {
+        if (value < 0) return fail(c, RDIS_HIP_EINVAL, "population_set_option: eval_workspace_bytes must not be negative");
+        USE_DEVICE(c);
+        pop->eval_workspace_bytes = value;
+        if (pop->eval_partial.bytes + pop->eval_xr.bytes > (size_t)value) {   // scratch beyond the new bound goes (the next evaluation takes what it needs)
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            pop->eval_partial.release(); pop->eval_xr.release();
+        }
+    } else if (n == "eval_batched") {
+        pop->eval_batched = value != 0;
+    } else {
+        return fail(c, RDIS_HIP_EINVAL, "population_set_option: unknown option '" + n + "' (eval_workspace_bytes, eval_batched)");
+    }
+    return 0;
+}
+
+extern "C" int rdis_hip_population_get_info(rdis_hip_population* pop, const char* name, int64_t* value) {
+    if (!pop || !name || !value) return RDIS_HIP_EINVAL;
+    const std::string n(name);
+    if (n == "eval_members_per_launch") *value = pop->eval_per_launch;
+    else if (n == "eval_launches") *value = pop->eval_launches;
+    else if (n == "eval_valid") *value = pop->eval_valid ? 1 : 0;
+    else return fail(pop->prob->ctx, RDIS_HIP_EINVAL, "population_get_info: unknown name '" + n + "' (eval_members_per_launch, eval_launches, eval_valid)");
     return 0;
 }
 
@@ -2954,6 +3097,7 @@ extern "C" int rdis_hip_plan_solve_population(rdis_hip_plan* L, rdis_hip_populat
     if (int rc = refuse_late_exponential(L, "plan_solve_population")) return rc;   // (nonlinear products only: no bundle-adjustment factor is exponential)
     bool plain = false;
     if (int rc = starts_refusal(L, "plan_solve_population", &plain, "population", L->population_tiny != 0)) return rc;
+    pop->eval_valid = false; pop->best_current = false;   // X is written: the values of the last evaluation are stale
     if (L->ncomp == 0) { L->ms_population = true; L->ms_n = S_n; L->ms_per_launch = S_n; L->ms_launches = 0; L->last_launches = 0; L->timed = false; return 0; }
 
     // what a launch runs: the tiny-component solver on the first rest_tiny entries of the batch list (option population_tiny: the

@@ -2,7 +2,7 @@
 """Multi-start solves measured: rdis_hip_plan_solve_starts against the same starts solved one by one.
 
   python tools/bench_multistart.py            # both steps, one JSON line
-  python tools/bench_multistart.py --step config3|config5s|config2|population|population-nlp|population-tiny   # one step, in this process
+  python tools/bench_multistart.py --step config3|config5s|config2|population|population-nlp|population-tiny|population-eval   # one step, in this process
 
 config3   BASELINE config 3 (ladybug 5 cameras / 30 points, one component): 320 one-ulp starts -- those of the end-value fixture,
           tests/golden/end_values.json -- in one call, and the same 320 by set_start / solve / fetch on the same plan.
@@ -21,6 +21,12 @@ population-tiny  full ladybug, 64 members drawn from the sampling intervals, the
           population_tiny), sixteen lanes a point; (b) the same with four lanes (quad_min_components = 1); (c) the way before that
           option: row_min_components = 1 << 40, a 64-lane workgroup of the LDS-resident solver per point and member; (d) member by member
           through set_x / set_start(None) / solve / get_x.  (a) again with 2 and 4 times the resident blocks (tiny_population_fill).
+population-eval  the step that closes a round: 256 members of ladybug 5 / 30 and 64 members of full ladybug from the sampling intervals,
+          after one camera step on the population so that the members' cameras differ.  (a) the wall time of rdis_hip_population_eval
+          with the population option eval_batched = 1 (the member a grid dimension: two or three launches) against eval_batched = 0
+          (member by member, two or three launches each: the path before that option), and of one member's rdis_hip_eval; (b) one
+          round -- camera plan, point plan -- ending in eval_device + assign_best + best() against the round ending in eval()
+          (eval_batched = 0) + the host's argmin + assign(); whether the bytes of f, the member chosen and the problem's x agree.
 Every step runs in a child process under a time limit of its own; a step that fails ends the run.  Wall times are the median of
 `--repeats` calls after one warm-up call; kernel_ms is rdis_hip_plan_last_kernel_ms of the last call."""
 import argparse
@@ -35,8 +41,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-STEP_LIMIT_S = {"config3": 240, "config5s": 240, "config2": 240, "population": 240, "population-nlp": 240, "population-tiny": 240}
-STEPS = ("config3", "config5s", "config2", "population", "population-nlp", "population-tiny")
+STEP_LIMIT_S = {"config3": 240, "config5s": 240, "config2": 240, "population": 240, "population-nlp": 240, "population-tiny": 240, "population-eval": 240}
+STEPS = ("config3", "config5s", "config2", "population", "population-nlp", "population-tiny", "population-eval")
 
 
 def ulp_perturbed(x0, rng):
@@ -296,8 +302,95 @@ def measure_population_tiny(repeats, members=64):
     return out
 
 
+def measure_population_eval(repeats):
+    """the evaluation of a population, batched against member by member, and a round that ends on the device against one that
+    ends on the host"""
+    from rdis_amd import capi, problems as P
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    from ba_multistart import sampling_intervals
+    ctx = capi.Context(0)
+
+    def median_ms(call):
+        call()                                             # (warm-up)
+        tt = []
+        for _ in range(repeats):
+            t = time.perf_counter()
+            call()
+            tt.append(time.perf_counter() - t)
+        return 1e3 * float(np.median(tt))
+
+    def shape(pp, members, cam_opts, pt_opts):
+        cams, pts = P.ba_alternation_plans(pp)
+        lo, hi = sampling_intervals(pp)
+        g = capi.Problem(ctx, pp)
+        plans = [capi.Plan(g, *cams), capi.Plan(g, *pts)]
+        for plan, opts in zip(plans, (cam_opts, pt_opts)):
+            for k, v in opts.items():
+                plan.set_option(k, v)
+        pop = capi.Population(g, x=np.random.default_rng(0).uniform(lo, hi, size=(members, pp.nvars)))
+        plans[0].solve_population(pop, 25, 3e-8)           # one camera step: every member its own cameras
+        X = pop.get_x()
+        out = {"members": members, "factors": int(pp.nfac)}
+        f = {}
+        for batched in (1, 0):
+            pop.set_option("eval_batched", batched)
+            out["eval_batched_%d_wall_ms" % batched] = median_ms(lambda: f.__setitem__(batched, pop.eval()))
+            out["eval_batched_%d_launches" % batched] = pop.info("eval_launches")
+        pop.set_option("eval_batched", 1)
+        pop.eval()
+        out["members_per_launch"] = pop.info("eval_members_per_launch")
+        g.set_x(X[0])
+        out["one_member_eval_wall_ms"] = median_ms(g.eval)
+        out["eval_speedup"] = out["eval_batched_0_wall_ms"] / out["eval_batched_1_wall_ms"]
+        out["batched_eval_in_single_evals"] = out["eval_batched_1_wall_ms"] / out["one_member_eval_wall_ms"]
+        out["f_bytes_equal"] = bool(f[1].tobytes() == f[0].tobytes())
+        res = {}
+
+        def round_device():
+            pop.set_x(X)
+            t = time.perf_counter()
+            for plan in plans:
+                plan.solve_population(pop, 25, 3e-8)
+            pop.eval_device()
+            pop.assign_best()
+            res["device"] = pop.best()
+            return time.perf_counter() - t
+
+        def round_host():
+            pop.set_x(X)
+            t = time.perf_counter()
+            for plan in plans:
+                plan.solve_population(pop, 25, 3e-8)
+            fh = pop.eval()
+            b = int(np.nanargmin(fh)) if not np.all(np.isnan(fh)) else 0      # (the lowest, the first of equals, no NaN unless all are)
+            pop.assign(b)
+            ctx.synchronize()
+            dt = time.perf_counter() - t
+            res["host"] = (b, float(fh[b]))
+            return dt
+
+        for name, call, batched in (("round_on_device_wall_ms", round_device, 1), ("round_on_host_wall_ms", round_host, 0)):
+            pop.set_option("eval_batched", batched)
+            call()                                         # (warm-up)
+            out[name] = 1e3 * float(np.median([call() for _ in range(repeats)]))
+            res[name] = g.get_x()
+        out["round_speedup"] = out["round_on_host_wall_ms"] / out["round_on_device_wall_ms"]
+        out["best_member"], out["best_f"] = res["device"]
+        out["round_results_equal"] = bool(res["device"][0] == res["host"][0] and np.float64(res["device"][1]).tobytes() == np.float64(res["host"][1]).tobytes()
+                                          and res["round_on_device_wall_ms"].tobytes() == res["round_on_host_wall_ms"].tobytes())
+        for o in plans + [pop, g]:
+            o.close()
+        return out
+
+    lds = {"coop_min_factors": 0, "coop_group_min_factors": 0}
+    return {"ladybug_5_30": shape(P.load_bal(ncams=5, npts=30), 256, {}, {}),
+            "ladybug_full": shape(P.load_bal(), 64, lds, {"population_tiny": 1})}
+
+
 def step(name, repeats):
     from rdis_amd import problems as P
+    if name == "population-eval":
+        return measure_population_eval(repeats)
     if name == "population-tiny":
         return measure_population_tiny(repeats)
     if name == "population":
