@@ -275,7 +275,8 @@ int rdis_hip_plan_fetch_starts(rdis_hip_plan *plan, double *x_out, double *fret,
  * both its start and its constants from X[s] and leaving its result there, so that the next plan (the other variables
  * free) follows with no host traffic (rdis_amd/csrc/solver_lds_population.hpp; nonlinear-product plans, with the plan
  * option "population_plain": solver_wg_population.hpp; bundle-adjustment plans with tiny components, with the plan option
- * "population_tiny": solver_quad_population.hpp).
+ * "population_tiny": solver_quad_population.hpp; components too large for the LDS, on the point-major streaming solver, with
+ * the plan option "population_point_major": solver_ptm_population.hpp).
  *   population_create   allocates X; x[nmembers][N] row-major, or NULL: every member a copy of the problem's currently
  *                       assigned x.  nmembers >= 1 (RDIS_HIP_EINVAL), below 2^31 and nmembers * N below 9e15
  *                       (RDIS_HIP_ERANGE).  Both problem kinds.  A population belongs to one problem and is destroyed
@@ -337,7 +338,13 @@ int rdis_hip_plan_fetch_starts(rdis_hip_plan *plan, double *x_out, double *fret,
  * has components in the plan -- a plan of points alone with "camera_records" = 0 needs no replica and is never split below
  * 65535 members; every member of a launch also has a 4-byte queue counter.  A launch of R members is then one launch of the
  * tiny-component solver (its grid: blocks per member x R, plan_get_info "population_tiny_blocks") followed, where the plan has
- * other components, by one of the LDS-resident solver; "starts_launches" and plan_last_kernel_ms count both.
+ * other components, by one of the LDS-resident solver; "starts_launches" and plan_last_kernel_ms count both.  With
+ * "population_point_major" a member of a launch also has a replica of the point-major solver's four per-solve arrays -- p and
+ * xi, g and h, the exact bounds (six doubles a point block each) and the wave-chunks' float boxes: 144 bytes per point block of
+ * the plan's point-major components and 32 per entry of their chunk tables, 1.1 MB a member for full ladybug as one component
+ * -- under the same bound and splitting; a launch of R members is then the tiny-component launch (where the plan has tiny
+ * components), the point-major kernel on a grid of (its components, R), and the LDS-resident kernel (where that solver has
+ * components), in this order, every one counted.
  * Scope: a bundle-adjustment problem, every non-empty component of the plan on the LDS-resident solver (plan_get_info
  * "components_lds"); or, with the plan option "population_plain" = 1 (default 0: refused, as before the option existed), a
  * nonlinear-product problem with every non-empty component on the plain batch solver ("components_plain": BASELINE
@@ -345,10 +352,16 @@ int rdis_hip_plan_fetch_starts(rdis_hip_plan *plan, double *x_out, double *fret,
  * the plan option "population_tiny" = 1 (default 0: refused, as before the option existed), a bundle-adjustment problem whose
  * non-empty components run on the tiny-component solver ("components_tiny": a point against constant cameras and the like) or
  * on the LDS-resident solver, in any mix; the lanes per tiny component are plan_solve's ("quad_min_components",
- * "row_min_components": the bits depend on them).  A
+ * "row_min_components": the bits depend on them); and, with the plan option "population_point_major" = 1 (default 0: refused,
+ * as before the option existed), also components on the point-major streaming solver ("components_point_major": too large for
+ * a compute unit's LDS -- full ladybug as one component, each component of BASELINE config 5-L) as ONE workgroup per component
+ * and member, beside the others in any mix.  The contract is plan_solve's bits, and a group of workgroups per component adds
+ * every sum in another order: the plan is taken only where plan_solve would run one workgroup per component (the plan option
+ * "ptm_group" = 1; the lanes are "ptm_threads", else 768: plan_get_info "population_point_major_threads"), otherwise
+ * RDIS_HIP_EINVAL with a message that names "ptm_group" and the group size plan_solve would pick.  A
  * persistent plan; default factor_rounding; emulate_stale_cache, trace_records and dump_iters off; the population must be
- * the plan's problem's.  Not yet: the cooperative, grid and point-major solvers; bundle-adjustment components on the plain
- * batch solver; tiny components in plan_solve_starts.  Anything
+ * the plan's problem's.  Not yet: the cooperative and grid solvers and point-major components shared by several workgroups;
+ * bundle-adjustment components on the plain batch solver; tiny and point-major components in plan_solve_starts.  Anything
  * else: RDIS_HIP_EINVAL and a message that names the cause; the plan and the population stay usable. */
 typedef struct rdis_hip_population rdis_hip_population;
 int rdis_hip_population_create(rdis_hip_problem *p, int64_t nmembers, const double *x, rdis_hip_population **out);
@@ -486,6 +499,11 @@ int rdis_hip_comm_allreduce_f64(rdis_hip_comm *comm, double *inout, int32_t n, i
  * tiny-component solver, alone or beside components on the LDS-resident solver: a few lanes per (component, member), every
  * member's blocks walking that member's components, rotation records per member; 0 = such a plan is refused with
  * RDIS_HIP_EINVAL; no effect on any other entry -- rdis_hip_plan_solve_starts keeps refusing tiny components),
+ * "population_point_major" (default 0; 1 = rdis_hip_plan_solve_population accepts a bundle-adjustment plan with components on
+ * the point-major streaming solver, alone or beside components of the two solvers above: one workgroup per (component, member)
+ * -- the plan must run one workgroup per component in plan_solve too, "ptm_group" = 1 --, every member of a launch a replica of
+ * that solver's point records; 0 = such a plan is refused with RDIS_HIP_EINVAL; no effect on any other entry --
+ * rdis_hip_plan_solve_starts keeps refusing point-major components),
  * "tiny_population_fill" (default 1, 1 ... 64: that launch takes this many times the blocks the device holds at once; a
  * measurement aid, no bit depends on it),
  * "trace_records" (per-component trace capacity, 0 = off), "dump_iters" (record p and
@@ -498,7 +516,8 @@ int rdis_hip_plan_set_option(rdis_hip_plan *plan, const char *name, int64_t valu
  * "point_major_wide" (0/1: that launch was a wide group), "point_major_local_cameras" (0, or the most cameras a workgroup of
  * a wide group with local camera numbering holds), "starts_per_launch" / "starts_launches" (starts a launch of the last multi-start
  * solve held; its number of launches), "population_tiny_blocks" (blocks per member of the tiny-component solver's launch in the
- * last population solve, 0 = it had none) */
+ * last population solve, 0 = it had none), "population_point_major_threads" (lanes of the point-major kernel's workgroups in
+ * the last population solve, 0 = it had none) */
 int rdis_hip_plan_get_info(rdis_hip_plan *plan, const char *name, int64_t *value);
 /* device memory the plan holds beyond the problem's (index tables, workspace, per-factor
  * partials, results): what a host-side cache of plans budgets with

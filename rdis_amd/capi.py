@@ -659,9 +659,12 @@ class Plan:
         every component on the plain batch solver (info("components_plain")), whose trial points go into the member's own row
         during the launch; or, after set_option("population_tiny", 1), a bundle-adjustment plan whose components run on the
         tiny-component solver (info("components_tiny"): points against constant cameras) or on the LDS-resident solver, in any
-        mix -- a few lanes per (component, member), with the lanes per component of solve() on the same plan options; anything
-        else -- a nonlinear-product plan or tiny components without their option included -- raises RdisHipError (EINVAL) with
-        the cause"""
+        mix -- a few lanes per (component, member), with the lanes per component of solve() on the same plan options; or, after
+        set_option("population_point_major", 1), one whose components run on the point-major streaming solver
+        (info("components_point_major"): too large for the LDS) as one workgroup a component (set_option("ptm_group", 1)), beside
+        the others in any mix -- info("population_point_major_threads") tells the lanes of that kernel; anything
+        else -- a nonlinear-product plan, tiny or point-major components without their option included -- raises RdisHipError
+        (EINVAL) with the cause"""
         self.ctx.check(self.ctx.lib.rdis_hip_plan_solve_population(self.h, pop.h, maxiters, ftol))
         self._nmembers = pop.nmembers
 

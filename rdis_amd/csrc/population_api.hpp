@@ -1,5 +1,6 @@
 // population_api.hpp -- what rdis_hip.hip sees of the population entries of the LDS-resident solver (solver_lds_population.hpp)
-// and of the plain one-workgroup solver (solver_wg_population.hpp), whose kernels are a translation unit of their own (population_kernels.hip).  The per-solve arrays are the multi-start
+// and of the plain one-workgroup solver (solver_wg_population.hpp), whose kernels are a translation unit of their own (population_kernels.hip),
+// and of the point-major streaming solver (solver_ptm_population.hpp; ptm_population_kernels.hip).  The per-solve arrays are the multi-start
 // entry's (starts_api.hpp: StartsView); the population itself is X[members][N], row-major.
 #pragma once
 #include "starts_api.hpp"
@@ -19,6 +20,20 @@ hipError_t population_launch_wg(int threads, int ncomp_listed, int members_of_la
 // XR null, or the launch's rotation records [members_of_launch][N] (P.rot_mode == ROT_CAMFIX)
 hipError_t population_launch_tiny(int group, int blocks_per_member, int members_of_launch, hipStream_t stream, const ProblemView& P, const PlanView& V,
                                   const StartsView& S, double* X, double* XR, const int* list, int ntiny, int* queues, int maxiters, double ftol);
+// The replicas of the point-major streaming solver's per-solve arrays (solver_ptm_population.hpp): replica r of the launch has
+// PlanView::pm_rec at rec + 6 blocks r, pm_gh at gh + 6 blocks r, pm_bex at bex + 6 blocks r and pm_cbox at cbox + 8 chunks r,
+// each laid out like the plan's own array (blocks: point blocks of the plan's point-major components, chunks: entries of pm_cptr)
+struct PtmReplicas {
+    double* rec;
+    double* gh;
+    double* bex;
+    float* cbox;
+    long long blocks, chunks;
+};
+// cgd_ptm_population_kernel<threads, rot> (threads 256 / 512 / 768 as cgd_ptm_kernel's): grid (ncomp_listed, members_of_launch) on
+// the components V.order lists -- point-major ones and components without factors; dyn = ptm_bytes_for(ncb_cap, threads, V.pm_round_slots)
+hipError_t population_launch_ptm(int rot, int threads, int ncomp_listed, int members_of_launch, size_t dyn, hipStream_t stream, const ProblemView& P,
+                                 const PlanView& V, const StartsView& S, const PtmReplicas& RP, double* X, int maxiters, double ftol, int ncb_cap);
 // population_rotations_kernel: XR[r] = the rotation records of member S.first + r's cameras, r < members_of_launch
 hipError_t population_rotations_launch(hipStream_t stream, const double* X, long long N, long long first, int members_of_launch, const int* cam_blocks,
                                        int nblocks, double* XR);

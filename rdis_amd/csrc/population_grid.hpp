@@ -1,6 +1,8 @@
-// population_grid.hpp -- the grid of the tiny-component solver's population launch (solver_quad_population.hpp) and the members
-// of a launch of the population's evaluation, pure host functions: no HIP call, no plan (tests/cpp/population_tiny_grid_test.cpp
-// and tests/cpp/population_eval_members_test.cpp run them without a device).
+// population_grid.hpp -- the grid of the tiny-component solver's population launch (solver_quad_population.hpp), the members
+// of a launch of the population's evaluation, and the replica of a population launch with point-major components
+// (solver_ptm_population.hpp) with the members of a launch it allows, pure host functions: no HIP call, no plan
+// (tests/cpp/population_tiny_grid_test.cpp, tests/cpp/population_eval_members_test.cpp and
+// tests/cpp/population_ptm_replica_test.cpp run them without a device).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -29,6 +31,21 @@ inline int64_t eval_member_bytes(int64_t partials_per_member, int64_t nvars, boo
 inline int64_t eval_members_per_launch(int64_t members, int64_t budget_bytes, int64_t partials_per_member, int64_t nvars, bool records) {
     const int64_t fit = std::max<int64_t>(1, budget_bytes / eval_member_bytes(partials_per_member, nvars, records));
     return std::max<int64_t>(1, std::min(std::min<int64_t>(members, 65535), fit));
+}
+
+// Bytes of one replica of a population launch with point-major components (solver_ptm_population.hpp): the replica's pm_rec, pm_gh
+// and pm_bex -- six doubles a point block each -- and its pm_cbox, eight floats per entry of pm_cptr; where the LDS-resident kernel
+// runs in the same launch (`lds_part`) its ws and gfac too, 8 (5 nfree + ngfac).  A plan without point blocks has no such part.
+inline int64_t ptm_population_replica_bytes(int64_t pm_blocks, int64_t pm_cptr_len, bool lds_part, int64_t nfree, int64_t ngfac) {
+    const int64_t ptm = std::max<int64_t>(pm_blocks, 0) * (6 + 6 + 6) * 8 + (pm_blocks > 0 ? std::max<int64_t>(pm_cptr_len, 0) * 32 : 0);
+    return ptm + (lds_part ? 8 * (5 * std::max<int64_t>(nfree, 0) + std::max<int64_t>(ngfac, 0)) : 0);
+}
+// Members of one launch of a population solve: the member is the grid's second dimension (at most 65535) and every member of a
+// launch has a replica of `replica_bytes` within `budget_bytes` (the plan option starts_workspace_bytes) -- at least one member a
+// launch, whatever the budget; a replica of nothing bounds nothing.  No bit of a result depends on it.
+inline int64_t population_members_per_launch(int64_t members, int64_t budget_bytes, int64_t replica_bytes) {
+    const int64_t fit = replica_bytes > 0 ? std::max<int64_t>(1, budget_bytes / replica_bytes) : members;
+    return std::min(std::min(fit, members), (int64_t)65535);
 }
 
 }  // namespace rdis_hip

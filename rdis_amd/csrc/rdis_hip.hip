@@ -373,6 +373,9 @@ struct rdis_hip_plan {
     DevBuf ms_queue;                  // ... whose members of a launch have a queue counter each
     int tiny_population_fill = 1;     // option "tiny_population_fill" (measurement): the population launch of that solver takes this many times the resident blocks
     int ms_tiny_blocks = 0;           // ... and this many blocks each in the last such solve (plan_get_info "population_tiny_blocks")
+    int population_point_major = 0;   // option "population_point_major": 1 = ... and one with components on the point-major streaming solver, a workgroup each (solver_ptm_population.hpp)
+    DevBuf ms_ptm;                    // ... whose members of a launch have a replica each of pm_rec, pm_gh, pm_bex and pm_cbox (within "starts_workspace_bytes" too)
+    int ms_ptm_threads = 0;           // ... and the lanes of that kernel in the last population solve, 0 = it had none (plan_get_info "population_point_major_threads")
     ~rdis_hip_plan() { if (ms_stage_ev) (void)hipEventDestroy(ms_stage_ev); }
     // the outputs' block for n starts: xout[n][nfree] fret[n][nc] delta[n][nc] (f64) | nfeval[n][nc] ngeval[n][nc] (i64) | iters[n][nc] status[n][nc] (i32)
     size_t ms_out_bytes(int64_t n) const { return (size_t)n * ((size_t)nfree * 8 + (size_t)ncomp * 40); }
@@ -1644,7 +1647,13 @@ extern "C" int rdis_hip_plan_set_option(rdis_hip_plan* L, const char* name, int6
         if (value < 0) return fail(c, RDIS_HIP_EINVAL, "starts_workspace_bytes < 0");
         L->starts_workspace_bytes = value;
         // (the bound holds from now on: replicas beyond it go; releasing device memory waits for the work that uses it)
-        if (L->ms_work.p && L->ms_work.bytes > (size_t)value) { L->dev_bytes -= std::min(L->dev_bytes, L->ms_work.bytes); L->ms_work.release(); }
+        if (L->ms_work.bytes + L->ms_ptm.bytes > (size_t)value) {
+            for (DevBuf* b : {&L->ms_work, &L->ms_ptm})
+                if (b->p) { L->dev_bytes -= std::min(L->dev_bytes, b->bytes); b->release(); }
+        }
+        return 0;   // (no table depends on it)
+    } else if (n == "population_point_major") {
+        L->population_point_major = value != 0;
         return 0;   // (no table depends on it)
     } else if (n == "population_plain") {
         L->population_plain = value != 0;
@@ -2376,6 +2385,60 @@ int launch_ptm_groups(rdis_hip_plan* L, hipStream_t stream, int threads, int fir
     HIPCHK(c, hipLaunchCooperativeKernel(fn, dim3(grid), dim3(threads), args, dyn, stream));
     return 0;
 }
+// The shape of the point-major launch of an ordinary solve (L->rest_ptm > 0): lanes a workgroup, workgroups a component (1:
+// launch_ptm, else launch_ptm_groups) and whether the groups are wide.  `overlap`: the batch runs beside cooperative launches.
+// (The population entry asks too: it takes a plan only where this says one workgroup a component -- the bits depend on it.)
+int ptm_launch_shape(rdis_hip_plan* L, bool overlap, int* threads_out, int* K_out, bool* wide_out) {
+    rdis_hip_ctx* c = L->prob->ctx;
+    // 768 lanes, three waves per SIMD (1000 / 500 components of ladybug's size: 187 / 99 ms, 196 / 109 with 256 lanes and two
+    // workgroups per compute unit).  Fewer components than resident workgroups: K workgroups share a component
+    // (cooperative launch, every workgroup of it resident), of 256 lanes -- two per compute unit, the finer grain
+    // loses less to whole wave-chunks -- as long as a workgroup keeps some twenty wave-chunks of points per trial point
+    // (below that the exchange costs what the split saves: 125 components of 2048 points 9.6 ms alone, 9.7 as pairs;
+    // of 7776 points 35.8 ms alone, 27.7 as groups of four)
+    int threads = L->ptm_threads ? L->ptm_threads : L->ptm_wide_wanted ? PTM_WIDE_THREADS : 768;
+    int K = 1;
+    if (L->ptm_group != 1 && !overlap && L->coop.empty() && L->stream.empty()) {
+        // groups of K workgroups: of 512 lanes (a workgroup per compute unit) or of 256 (two) -- whichever brings more
+        // lanes to a component, at equal lanes the larger workgroup (125 components of ladybug's size: pairs of 512
+        // lanes 16.0 ms, fours of 256 17.0, one workgroup of 768 each 24.2; round 4)
+        const int slots8 = 8 * ((L->rest_ptm + 7) / 8);   // (groups are placed eight at a time, one per XCD)
+        const int useful = (int)std::max<int64_t>(1, (L->ptm_min_points + 63) / 64 / 24);
+        int best_lanes = 0, best_threads = 0, best_K = 1;
+        const int cands[2] = {L->ptm_threads ? L->ptm_threads : 512, 256};
+        for (int ci = 0; ci < (L->ptm_threads ? 1 : 2); ++ci) {
+            const int gt = cands[ci];
+            int cap = 0;
+            int rc = ptmg_resident_workgroups(L, gt, &cap);
+            if (rc) return rc;
+            const int fit = std::min(std::min(PTM_MAX_GROUP, cap / slots8), SMALL_COOP_ENTRIES / (gt / 64));
+            const int Kc = L->ptm_group > 1 ? std::min(L->ptm_group, fit) : std::min(fit, useful);
+            if (Kc >= 2 && Kc * gt > best_lanes) { best_lanes = Kc * gt; best_threads = gt; best_K = Kc; }
+        }
+        // (a group must bring more lanes to a component than the one workgroup it replaces: 250 components of
+        // ladybug's size 50.4 ms a workgroup of 768 lanes each, 56.0 as pairs of 256)
+        if (best_K >= 2 && (L->ptm_group > 1 || best_lanes > threads)) { K = best_K; threads = best_threads; }
+    }
+    // A few components and a device: wide groups -- as many workgroups of 512 lanes a component as are resident and have some
+    // twenty wave-chunks of points each (one component of 8e6 factors: 256 workgroups, 15 chunks a wave)
+    bool wide = false;
+    if (L->ptm_local) {   // (its tables are made for this group size)
+        K = L->ptm_local_K; threads = PTM_WIDE_THREADS; wide = true;
+        if (overlap || !L->coop.empty() || !L->stream.empty())
+            return fail(c, RDIS_HIP_EINVAL, "a wide group with local camera numbering takes the device to itself: no cooperative or grid launch beside it");
+    } else if (L->ptm_group != 1 && !overlap && L->coop.empty() && L->stream.empty() && L->rest_ptm <= 8 &&
+        (L->ptm_threads == 0 || L->ptm_threads == PTM_WIDE_THREADS)) {
+        int cap = 0;
+        int rc = ptmg_resident_workgroups(L, PTM_WIDE_THREADS, &cap, true);
+        if (rc) return rc;
+        const int useful = (int)std::max<int64_t>(1, (L->ptm_min_points + 63) / 64 / 24);
+        const int fit = std::min(std::min(PTM_WIDE_MAX_GROUP, cap / L->rest_ptm), COOP_MAX_WG * COOP_MAX_WAVES / (PTM_WIDE_THREADS / 64));
+        const int Kw = L->ptm_group > 1 ? std::min(L->ptm_group, fit) : std::min(fit, useful);
+        if (Kw > PTM_MAX_GROUP && Kw * PTM_WIDE_THREADS > K * threads) { K = Kw; threads = PTM_WIDE_THREADS; wide = true; }
+    }
+    *threads_out = threads; *K_out = std::max(K, 1); *wide_out = wide;
+    return 0;
+}
 // the workgroup size of the LDS-resident launch (a sum's tree depends on it: the multi-start entry takes the same)
 int lds_launch_threads(const rdis_hip_plan* L) {
     const rdis_hip_ctx* c = L->prob->ctx;
@@ -2544,52 +2607,9 @@ extern "C" int rdis_hip_plan_solve(rdis_hip_plan* L, int32_t maxiters, double ft
         ++L->last_launches;
     }
     if (L->rest_ptm > 0) {
-        // 768 lanes, three waves per SIMD (1000 / 500 components of ladybug's size: 187 / 99 ms, 196 / 109 with 256 lanes and two
-        // workgroups per compute unit).  Fewer components than resident workgroups: K workgroups share a component
-        // (cooperative launch, every workgroup of it resident), of 256 lanes -- two per compute unit, the finer grain
-        // loses less to whole wave-chunks -- as long as a workgroup keeps some twenty wave-chunks of points per trial point
-        // (below that the exchange costs what the split saves: 125 components of 2048 points 9.6 ms alone, 9.7 as pairs;
-        // of 7776 points 35.8 ms alone, 27.7 as groups of four)
-        int threads = L->ptm_threads ? L->ptm_threads : L->ptm_wide_wanted ? PTM_WIDE_THREADS : 768;
-        int K = 1;
-        if (L->ptm_group != 1 && !overlap && L->coop.empty() && L->stream.empty()) {
-            // groups of K workgroups: of 512 lanes (a workgroup per compute unit) or of 256 (two) -- whichever brings more
-            // lanes to a component, at equal lanes the larger workgroup (125 components of ladybug's size: pairs of 512
-            // lanes 16.0 ms, fours of 256 17.0, one workgroup of 768 each 24.2; round 4)
-            const int slots8 = 8 * ((L->rest_ptm + 7) / 8);   // (groups are placed eight at a time, one per XCD)
-            const int useful = (int)std::max<int64_t>(1, (L->ptm_min_points + 63) / 64 / 24);
-            int best_lanes = 0, best_threads = 0, best_K = 1;
-            const int cands[2] = {L->ptm_threads ? L->ptm_threads : 512, 256};
-            for (int ci = 0; ci < (L->ptm_threads ? 1 : 2); ++ci) {
-                const int gt = cands[ci];
-                int cap = 0;
-                int rc = ptmg_resident_workgroups(L, gt, &cap);
-                if (rc) return rc;
-                const int fit = std::min(std::min(PTM_MAX_GROUP, cap / slots8), SMALL_COOP_ENTRIES / (gt / 64));
-                const int Kc = L->ptm_group > 1 ? std::min(L->ptm_group, fit) : std::min(fit, useful);
-                if (Kc >= 2 && Kc * gt > best_lanes) { best_lanes = Kc * gt; best_threads = gt; best_K = Kc; }
-            }
-            // (a group must bring more lanes to a component than the one workgroup it replaces: 250 components of
-            // ladybug's size 50.4 ms a workgroup of 768 lanes each, 56.0 as pairs of 256)
-            if (best_K >= 2 && (L->ptm_group > 1 || best_lanes > threads)) { K = best_K; threads = best_threads; }
-        }
-        // A few components and a device: wide groups -- as many workgroups of 512 lanes a component as are resident and have some
-        // twenty wave-chunks of points each (one component of 8e6 factors: 256 workgroups, 15 chunks a wave)
+        int threads = 0, K = 1;
         bool wide = false;
-        if (L->ptm_local) {   // (its tables are made for this group size)
-            K = L->ptm_local_K; threads = PTM_WIDE_THREADS; wide = true;
-            if (overlap || !L->coop.empty() || !L->stream.empty())
-                return fail(c, RDIS_HIP_EINVAL, "a wide group with local camera numbering takes the device to itself: no cooperative or grid launch beside it");
-        } else if (L->ptm_group != 1 && !overlap && L->coop.empty() && L->stream.empty() && L->rest_ptm <= 8 &&
-            (L->ptm_threads == 0 || L->ptm_threads == PTM_WIDE_THREADS)) {
-            int cap = 0;
-            int rc = ptmg_resident_workgroups(L, PTM_WIDE_THREADS, &cap, true);
-            if (rc) return rc;
-            const int useful = (int)std::max<int64_t>(1, (L->ptm_min_points + 63) / 64 / 24);
-            const int fit = std::min(std::min(PTM_WIDE_MAX_GROUP, cap / L->rest_ptm), COOP_MAX_WG * COOP_MAX_WAVES / (PTM_WIDE_THREADS / 64));
-            const int Kw = L->ptm_group > 1 ? std::min(L->ptm_group, fit) : std::min(fit, useful);
-            if (Kw > PTM_MAX_GROUP && Kw * PTM_WIDE_THREADS > K * threads) { K = Kw; threads = PTM_WIDE_THREADS; wide = true; }
-        }
+        if (int rc = ptm_launch_shape(L, overlap, &threads, &K, &wide)) return rc;
         L->ptm_last_group = std::max(K, 1);
         L->ptm_last_threads = threads;
         L->ptm_wide_last = wide;
@@ -2656,8 +2676,9 @@ constexpr int64_t STARTS_MAX_PER_LAUNCH = 65535;       // (the start is the grid
 // why a plan cannot be solved from many starts yet.  Two kinds of plan can: every component on the LDS-resident solver (bundle
 // adjustment), or a nonlinear-product problem with every component on the plain batch solver -- *plain_solver says which
 // (entry: "multi-start" or "population" -- rdis_hip_plan_solve_population shares these checks)
-// (allow_tiny: the population entry with the plan option population_tiny -- tiny components beside LDS-resident ones pass)
-int starts_refusal(rdis_hip_plan* L, const char* who, bool* plain_solver, const char* entry = "multi-start", bool allow_tiny = false) {
+// (allow_tiny: the population entry with the plan option population_tiny -- tiny components beside LDS-resident ones pass;
+// allow_ptm: with population_point_major, point-major components too -- the entry itself then asks for one workgroup a component)
+int starts_refusal(rdis_hip_plan* L, const char* who, bool* plain_solver, const char* entry = "multi-start", bool allow_tiny = false, bool allow_ptm = false) {
     rdis_hip_problem* p = L->prob;
     rdis_hip_ctx* c = p->ctx;
     const std::string w(who), en(entry);
@@ -2680,7 +2701,7 @@ int starts_refusal(rdis_hip_plan* L, const char* who, bool* plain_solver, const 
     note((int64_t)L->coop.size(), "cooperative solver");
     note((int64_t)L->stream.size(), "grid solver");
     if (!allow_tiny) note(tiny, "tiny-component solver");
-    note(ptm, "point-major streaming solver");
+    if (!allow_ptm) note(ptm, "point-major streaming solver");
     const bool plain_ok = plain > 0 && p->kind == KIND_NLP && others.empty();
     if (!plain_ok) note(plain, "plain batch solver");
     if (!others.empty()) {
@@ -2690,9 +2711,11 @@ int starts_refusal(rdis_hip_plan* L, const char* who, bool* plain_solver, const 
         // (the population entry takes tiny components with an option of their own; the multi-start entry does not)
         const std::string tiny_hint = tiny > 0 && !allow_tiny && en == "population" ? " (tiny components are solved on a population with the plan option "
                                                                                       "population_tiny = 1: solver_quad_population.hpp)" : "";
+        const std::string ptm_hint = ptm > 0 && !allow_ptm && en == "population" ? " (point-major components are solved on a population, one workgroup each, with "
+                                                                                   "the plan option population_point_major = 1: solver_ptm_population.hpp)" : "";
         return fail(c, RDIS_HIP_EINVAL, w + ": every component of the plan must run on the LDS-resident solver (bundle adjustment, variables fitting a "
                                         "compute unit's LDS) or, all of them, on the plain batch solver of a nonlinear-product problem; this plan sends" +
-                                        others + ba_plain + tiny_hint);
+                                        others + ba_plain + tiny_hint + ptm_hint);
     }
     *plain_solver = plain_ok;
     return 0;
@@ -3096,24 +3119,48 @@ extern "C" int rdis_hip_plan_solve_population(rdis_hip_plan* L, rdis_hip_populat
         return fail(c, RDIS_HIP_ERANGE, "plan_solve_population: too many members");
     if (int rc = refuse_late_exponential(L, "plan_solve_population")) return rc;   // (nonlinear products only: no bundle-adjustment factor is exponential)
     bool plain = false;
-    if (int rc = starts_refusal(L, "plan_solve_population", &plain, "population", L->population_tiny != 0)) return rc;
+    if (int rc = starts_refusal(L, "plan_solve_population", &plain, "population", L->population_tiny != 0, L->population_point_major != 0)) return rc;
+    // point-major components (option population_point_major: the refusal above let them pass) run as one workgroup a component, the
+    // bits of launch_ptm -- a group, a wide group or local camera numbering changes the order of every sum
+    const int nptm = (L->population_point_major && !plain) ? L->rest_ptm : 0;
+    int ptm_threads = 0;
+    if (nptm > 0) {
+        int K = 1;
+        bool wide = false;
+        if (int rc = ptm_launch_shape(L, false, &ptm_threads, &K, &wide)) return rc;
+        if (K >= 2)
+            return fail(c, RDIS_HIP_EINVAL, "plan_solve_population: point-major components are solved on a population as one workgroup a component, and this plan's "
+                                            "ordinary solve would run them as " + std::string(wide ? "wide " : "") + "groups of " + std::to_string(K) +
+                                            " workgroups (other sums, other bits): set the plan option ptm_group = 1");
+    }
     pop->eval_valid = false; pop->best_current = false;   // X is written: the values of the last evaluation are stale
     if (L->ncomp == 0) { L->ms_population = true; L->ms_n = S_n; L->ms_per_launch = S_n; L->ms_launches = 0; L->last_launches = 0; L->timed = false; return 0; }
 
     // what a launch runs: the tiny-component solver on the first rest_tiny entries of the batch list (option population_tiny: the
     // refusal above let them pass), the LDS-resident or the plain solver on the entries behind them, where there are any
     // (without the option nothing but empty components can be among the first rest_tiny: the whole list goes to the other solver, as before)
-    const int ntiny = (L->population_tiny && !plain) ? L->rest_tiny : 0, nlisted = (int)L->h_rest.size() - ntiny;
+    // With point-major components the list behind the tiny ones splits once more: the point-major kernel takes the entries up to
+    // the LDS-resident slice (empty components among them: it knows them), the LDS-resident kernel its own slice
+    const int ntiny = (L->population_tiny && !plain) ? L->rest_tiny : 0;
+    const int nptm_listed = nptm > 0 ? (int)L->h_rest.size() - ntiny - L->rest_lds : 0;
+    const int nlisted = (int)L->h_rest.size() - ntiny - nptm_listed;
     const bool tiny_records = ntiny > 0 && L->rest_rot_mode == ROT_CAMFIX;   // (the tiny launch reads rotation records: a replica per member)
     // replicas a launch may hold within the budget, the multi-start entry's rule.  A replica holds only what the launch's kernels
     // read: ws and gfac where the LDS-resident or the plain solver runs (the plain solver's dir too -- its x is the member's row),
     // the cameras' rotation records [N] where the tiny-component solver reads records
     const size_t work_doubles = nlisted > 0 ? 5 * (size_t)L->nfree + (size_t)L->ngfac : 0, rot_doubles = tiny_records ? (size_t)p->N : 0;
     const size_t dir_doubles = plain ? (size_t)p->N : 0;
-    const size_t rep_bytes = (work_doubles + rot_doubles + dir_doubles) * sizeof(double);
-    int64_t R = rep_bytes ? std::max<int64_t>(1, L->starts_workspace_bytes / (int64_t)rep_bytes) : S_n;
-    R = std::min(std::min(R, S_n), STARTS_MAX_PER_LAUNCH);
+    // ... and the four per-solve arrays of the point-major solver (population_grid.hpp: ptm_population_replica_bytes)
+    const size_t ptm_bytes = nptm > 0 ? (size_t)ptm_population_replica_bytes(L->pm_blocks, L->pm_cptr_len, false, 0, 0) : 0;
+    const size_t rep_bytes = (work_doubles + rot_doubles + dir_doubles) * sizeof(double) + ptm_bytes;
+    const int64_t R = population_members_per_launch(S_n, L->starts_workspace_bytes, (int64_t)rep_bytes);
     int rc = 0;
+    if (nptm > 0) {
+        // the round tables of that workgroup size, one workgroup a component, before the first launch (launch_ptm's)
+        rc = ptm_build_rounds(L, ptm_threads, 1);
+        if (!rc && L->ms_ptm.bytes < (size_t)R * ptm_bytes) rc = plan_alloc(L, L->ms_ptm, (size_t)R * ptm_bytes);
+        if (rc) return rc;
+    }
     const size_t work_bytes = (size_t)R * (work_doubles + rot_doubles) * sizeof(double);
     if (L->ms_work.bytes < work_bytes) rc = plan_alloc(L, L->ms_work, work_bytes);
     if (!rc && plain && L->ms_dir.bytes < (size_t)R * dir_doubles * sizeof(double)) {
@@ -3139,10 +3186,21 @@ extern "C" int rdis_hip_plan_solve_population(rdis_hip_plan* L, rdis_hip_populat
     const size_t dyn = L->lds_dyn_bytes(c);
     ProblemView PT = P;   // the tiny launch's: records of the launch's members or per-factor rotations (the quad solver has no refresh)
     PT.rot_mode = tiny_records ? ROT_CAMFIX : ROT_PER_FACTOR;
-    PlanView VR = V;      // the other launch's: the batch list behind the tiny components
-    VR.order = V.order + ntiny;
+    PlanView VM = V;      // the point-major launch's: the batch list behind the tiny components, up to the LDS-resident slice
+    VM.order = V.order + ntiny;
+    PlanView VR = V;      // the other launch's: the rest of the batch list
+    VR.order = V.order + ntiny + nptm_listed;
+    // the launch's replicas of pm_rec, pm_gh, pm_bex (six doubles a point block each) and, behind them, of pm_cbox
+    PtmReplicas RP{nullptr, nullptr, nullptr, nullptr, L->pm_blocks, L->pm_cptr_len};
+    if (nptm > 0) {
+        const size_t plane = (size_t)R * PT_REC * (size_t)L->pm_blocks;
+        RP.rec = L->ms_ptm.as<double>(); RP.gh = RP.rec + plane; RP.bex = RP.gh + plane;
+        RP.cbox = reinterpret_cast<float*>(RP.bex + plane);
+    }
+    const size_t ptm_dyn = nptm > 0 ? ptm_bytes_for(L->ptm_ncb_cap, ptm_threads, L->rounds_slots) : 0;
     L->last_launches = 0;
     L->ms_tiny_blocks = 0;
+    L->ms_ptm_threads = nptm > 0 ? ptm_threads : 0;
     L->timed = false;
     HIPCHK(c, hipEventRecord(p->ev0, c->stream));
     for (int64_t first = 0; first < S_n; first += R) {   // (launches on one stream: the next takes the replicas when this one is done)
@@ -3156,6 +3214,11 @@ extern "C" int rdis_hip_plan_solve_population(rdis_hip_plan* L, rdis_hip_populat
             const int gx = tiny_population_blocks(ntiny, (G == 4 ? QUAD_THREADS : 64) / G, L->tiny_population_fill * std::max(1, G == 4 ? L->group_blocks4 : L->group_blocks16), ns, L->tiny_max_blocks);
             HIPCHK(c, population_launch_tiny(G, gx, ns, c->stream, PT, V, S, pop->X.as<double>(), XR, L->rest_order.as<int>(), ntiny, L->ms_queue.as<int>(), maxiters, ftol));
             L->ms_tiny_blocks = gx;
+            ++L->last_launches;
+        }
+        if (nptm_listed > 0) {
+            HIPCHK(c, population_launch_ptm(L->ptm_rot_mode, ptm_threads, nptm_listed, ns, ptm_dyn, c->stream, P, VM, S, RP, pop->X.as<double>(), maxiters, ftol,
+                                            L->ptm_ncb_cap));
             ++L->last_launches;
         }
         if (nlisted > 0) {
@@ -3410,6 +3473,7 @@ extern "C" int rdis_hip_plan_get_info(rdis_hip_plan* L, const char* name, int64_
     else if (n == "starts_per_launch") *value = L->ms_per_launch;
     else if (n == "starts_launches") *value = L->ms_launches;
     else if (n == "population_tiny_blocks") *value = L->ms_tiny_blocks;
+    else if (n == "population_point_major_threads") *value = L->ms_ptm_threads;
     else return fail(c, RDIS_HIP_EINVAL, "plan_get_info: unknown name '" + n + "'");
     return 0;
 }

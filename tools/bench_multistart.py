@@ -2,7 +2,7 @@
 """Multi-start solves measured: rdis_hip_plan_solve_starts against the same starts solved one by one.
 
   python tools/bench_multistart.py            # both steps, one JSON line
-  python tools/bench_multistart.py --step config3|config5s|config2|population|population-nlp|population-tiny|population-eval   # one step, in this process
+  python tools/bench_multistart.py --step config3|config5s|config2|population|population-nlp|population-tiny|population-eval|population-point-major   # one step, in this process
 
 config3   BASELINE config 3 (ladybug 5 cameras / 30 points, one component): 320 one-ulp starts -- those of the end-value fixture,
           tests/golden/end_values.json -- in one call, and the same 320 by set_start / solve / fetch on the same plan.
@@ -27,6 +27,12 @@ population-eval  the step that closes a round: 256 members of ladybug 5 / 30 and
           (member by member, two or three launches each: the path before that option), and of one member's rdis_hip_eval; (b) one
           round -- camera plan, point plan -- ending in eval_device + assign_best + best() against the round ending in eval()
           (eval_batched = 0) + the host's argmin + assign(); whether the bytes of f, the member chosen and the problem's x agree.
+population-point-major  full ladybug as ONE component (what optBA's sample loop runs per sample when it calls CGD on everything) on the
+          point-major streaming solver, one workgroup of 768 lanes a member (plan options population_point_major = 1, ptm_group = 1):
+          64 and 256 members from the sampling intervals, 25 iterations, one population launch each, against the same members one by
+          one through set_x / set_start(None) / solve / get_x; last_kernel_ms of the population launch in units of one ordinary
+          solve's (cgd_ptm_kernel, whose code and registers are the parent commit's); whether both routes left the same bytes.
+          Not part of the run without --step (it is asked for by name).
 Every step runs in a child process under a time limit of its own; a step that fails ends the run.  Wall times are the median of
 `--repeats` calls after one warm-up call; kernel_ms is rdis_hip_plan_last_kernel_ms of the last call."""
 import argparse
@@ -41,7 +47,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-STEP_LIMIT_S = {"config3": 240, "config5s": 240, "config2": 240, "population": 240, "population-nlp": 240, "population-tiny": 240, "population-eval": 240}
+STEP_LIMIT_S = {"config3": 240, "config5s": 240, "config2": 240, "population": 240, "population-nlp": 240, "population-tiny": 240, "population-eval": 240,
+                "population-point-major": 420}
 STEPS = ("config3", "config5s", "config2", "population", "population-nlp", "population-tiny", "population-eval")
 
 
@@ -302,6 +309,82 @@ def measure_population_tiny(repeats, members=64):
     return out
 
 
+def measure_population_point_major(repeats, sizes=(64, 256)):
+    """full ladybug as one component: S workgroups of the point-major solver in one launch against S ordinary solves"""
+    from rdis_amd import capi, problems as P
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    from ba_multistart import sampling_intervals
+    pp = P.load_bal().single_component()
+    lo, hi = sampling_intervals(pp)
+    ctx = capi.Context(0)
+    g = capi.Problem(ctx, pp)
+    plan = capi.Plan(g)
+    for k, v in {"coop_min_factors": 0, "coop_group_min_factors": 0, "ptm_stream": 2, "ptm_group": 1, "ptm_threads": 768,
+                 "population_point_major": 1}.items():
+        plan.set_option(k, v)
+    Xall = np.random.default_rng(0).uniform(lo, hi, size=(max(sizes), pp.nvars))
+    out = {"factors": int(pp.nfac), "variables": int(pp.nvars), "maxiters": 25}
+    # the unit: one ordinary solve from x0 and from the first member (their iteration counts differ)
+    unit = {}
+    for name, x in (("x0", pp.x0), ("member_0", Xall[0])):
+        kk = []
+        for _ in range(repeats + 1):
+            g.set_x(x)
+            plan.set_start(None)
+            plan.solve(25, 3e-8)
+            r = plan.fetch()
+            kk.append(plan.last_kernel_ms()[0])
+        unit[name] = {"last_kernel_ms": float(np.median(kk[1:])), "nfeval": int(r.nfeval[0]), "iters": int(r.iters[0])}
+    out["one_ordinary_solve"] = unit
+    out["components_point_major"] = plan.info("components_point_major")
+    out["point_major_threads"] = plan.info("point_major_threads")
+    for members in sizes:
+        X = Xall[:members]
+        pop = capi.Population(g, x=X)
+        tt, kk = [], []
+        for _ in range(repeats + 1):                       # (the first call is the warm-up)
+            pop.set_x(X)
+            ctx.synchronize()
+            t = time.perf_counter()
+            plan.solve_population(pop, 25, 3e-8)
+            ctx.synchronize()
+            tt.append(time.perf_counter() - t)
+            kk.append(plan.last_kernel_ms()[0])
+        xt = pop.get_x()
+        pr = plan.fetch_population(want_x=False)
+
+        def one_by_one():
+            res = np.empty_like(X)
+            km = 0.0
+            t = time.perf_counter()
+            for s in range(members):
+                g.set_x(X[s])
+                plan.set_start(None)
+                plan.solve(25, 3e-8)
+                res[s] = g.get_x()
+                km += plan.last_kernel_ms()[0]
+            return time.perf_counter() - t, res, km
+
+        one_by_one()
+        ts, ks = [], []
+        for _ in range(repeats):
+            dt, xs, km = one_by_one()
+            ts.append(dt)
+            ks.append(km)
+        kernel, seq_kernel = float(np.median(kk[1:])), float(np.median(ks))
+        out["members_%d" % members] = {
+            "wall_ms": 1e3 * float(np.median(tt[1:])), "last_kernel_ms": kernel, "launches": plan.last_kernel_ms()[1],
+            "members_per_launch": plan.info("starts_per_launch"), "threads": plan.info("population_point_major_threads"),
+            "sequential_wall_ms": 1e3 * float(np.median(ts)), "sequential_kernel_ms_summed": seq_kernel,
+            "speedup_wall": float(np.median(ts)) / float(np.median(tt[1:])),
+            "kernel_in_ordinary_solves_of_member_0": kernel / unit["member_0"]["last_kernel_ms"],
+            "kernel_in_mean_member_solves": kernel / (seq_kernel / members),
+            "nfeval_min_max": [int(pr.nfeval.min()), int(pr.nfeval.max())],
+            "bits_equal_member_by_member": bool(xt.tobytes() == xs.tobytes()), "device_bytes": plan.device_bytes()}
+        pop.close()
+    return out
+
+
 def measure_population_eval(repeats):
     """the evaluation of a population, batched against member by member, and a round that ends on the device against one that
     ends on the host"""
@@ -393,6 +476,8 @@ def step(name, repeats):
         return measure_population_eval(repeats)
     if name == "population-tiny":
         return measure_population_tiny(repeats)
+    if name == "population-point-major":
+        return measure_population_point_major(repeats)
     if name == "population":
         return measure_population(repeats)
     if name == "population-nlp":
