@@ -18,8 +18,9 @@ decltype(auto) with_threads(int threads, F&& f) {
 }
 
 // kernel<<<grid, threads, dyn, stream>>>(args...), the kernel's dynamic-LDS limit raised first where dyn needs it
+// (grid: a dim3, or an int for a grid of one dimension)
 template <class... KA, class... A>
-hipError_t launch_dyn(void (*kernel)(KA...), int grid, int threads, size_t dyn, hipStream_t stream, const A&... args) {
+hipError_t launch_dyn(void (*kernel)(KA...), dim3 grid, int threads, size_t dyn, hipStream_t stream, const A&... args) {
     if (dyn > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
         if (e != hipSuccess) return e;

@@ -17,12 +17,7 @@ hipError_t population_launch(int rot, int threads, int ncomp_listed, int members
         auto* kernel = rot == ROT_CAMFIX ? cgd_lds_population_kernel<T.value, ROT_CAMFIX>
                      : rot == ROT_RECORDS ? cgd_lds_population_kernel<T.value, ROT_RECORDS>
                                           : cgd_lds_population_kernel<T.value, ROT_PER_FACTOR>;
-        if (dyn > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-            if (e != hipSuccess) return e;
-        }
-        kernel<<<dim3((unsigned)ncomp_listed, (unsigned)members_of_launch), T.value, dyn, stream>>>(P, V, S, X, maxiters, ftol, ns_cap, ncb_cap, chunk_cap);
-        return hipGetLastError();
+        return launch_dyn(kernel, dim3((unsigned)ncomp_listed, (unsigned)members_of_launch), T.value, dyn, stream, P, V, S, X, maxiters, ftol, ns_cap, ncb_cap, chunk_cap);
     });
 }
 

@@ -16,13 +16,8 @@ template <int ROT>
 static hipError_t population_launch_ptm_rot(int threads, int ncomp_listed, int members_of_launch, size_t dyn, hipStream_t stream, const ProblemView& P,
                                             const PlanView& V, const StartsView& S, const PtmReplicas& RP, double* X, int maxiters, double ftol, int ncb_cap) {
     return with_threads<256, 512, 768>(threads, [&](auto T) {
-        auto* kernel = cgd_ptm_population_kernel<T.value, ROT>;
-        if (dyn > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-            if (e != hipSuccess) return e;
-        }
-        kernel<<<dim3((unsigned)ncomp_listed, (unsigned)members_of_launch), T.value, dyn, stream>>>(P, V, S, RP, X, maxiters, ftol, ncb_cap);
-        return hipGetLastError();
+        return launch_dyn(cgd_ptm_population_kernel<T.value, ROT>, dim3((unsigned)ncomp_listed, (unsigned)members_of_launch), T.value, dyn, stream, P, V, S, RP,
+                          X, maxiters, ftol, ncb_cap);
     });
 }
 

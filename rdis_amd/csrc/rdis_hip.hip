@@ -2720,6 +2720,36 @@ int starts_refusal(rdis_hip_plan* L, const char* who, bool* plain_solver, const 
     *plain_solver = plain_ok;
     return 0;
 }
+
+// rdis_hip_plan_fetch_starts and rdis_hip_plan_fetch_population: the rows of the last such solve (best: the former's only)
+int fetch_many(rdis_hip_plan* L, bool population, double* x_out, double* fret, double* delta, int32_t* iters, int32_t* status, int64_t* nfeval,
+               int64_t* ngeval, int32_t* best) {
+    rdis_hip_ctx* c = L->prob->ctx;
+    USE_DEVICE(c);
+    if (L->ms_n < 1)
+        return fail(c, RDIS_HIP_EINVAL, population ? "plan_fetch_population: no population solve to fetch (call rdis_hip_plan_solve_population first)"
+                                                   : "plan_fetch_starts: no multi-start solve to fetch (call rdis_hip_plan_solve_starts first)");
+    if (L->ms_population != population)
+        return fail(c, RDIS_HIP_EINVAL, population ? "plan_fetch_population: the plan's last solve of this kind was a multi-start solve (fetch it with rdis_hip_plan_fetch_starts)"
+                                                   : "plan_fetch_starts: the plan's last solve of this kind was a population solve (fetch it with rdis_hip_plan_fetch_population)");
+    if (L->ncomp == 0) return 0;
+    // every array is one contiguous piece of the outputs' block: straight into the caller's memory
+    const StartsView S = L->starts_view(L->ms_n);
+    const size_t sn = (size_t)L->ms_n * (size_t)L->nfree, sc = (size_t)L->ms_n * (size_t)L->ncomp;
+    auto get = [&](void* dst, const void* src, size_t bytes) {
+        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    HIPCHK(c, get(x_out, S.xout, sn * 8));
+    HIPCHK(c, get(fret, S.fret, sc * 8));
+    HIPCHK(c, get(delta, S.delta, sc * 8));
+    HIPCHK(c, get(nfeval, S.nfeval, sc * 8));
+    HIPCHK(c, get(ngeval, S.ngeval, sc * 8));
+    HIPCHK(c, get(iters, S.iters, sc * 4));
+    HIPCHK(c, get(status, S.status, sc * 4));
+    if (!population) HIPCHK(c, get(best, L->ms_best.p, (size_t)L->ncomp * 4));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
 }  // namespace
 
 extern "C" int rdis_hip_plan_solve_starts(rdis_hip_plan* L, int64_t nstarts, const double* x_starts, int32_t maxiters, double ftol) {
@@ -2809,27 +2839,7 @@ extern "C" int rdis_hip_plan_solve_starts(rdis_hip_plan* L, int64_t nstarts, con
 extern "C" int rdis_hip_plan_fetch_starts(rdis_hip_plan* L, double* x_out, double* fret, double* delta, int32_t* iters, int32_t* status,
                                           int64_t* nfeval, int64_t* ngeval, int32_t* best) {
     if (!L) return RDIS_HIP_EINVAL;
-    rdis_hip_ctx* c = L->prob->ctx;
-    USE_DEVICE(c);
-    if (L->ms_n < 1) return fail(c, RDIS_HIP_EINVAL, "plan_fetch_starts: no multi-start solve to fetch (call rdis_hip_plan_solve_starts first)");
-    if (L->ms_population) return fail(c, RDIS_HIP_EINVAL, "plan_fetch_starts: the plan's last solve of this kind was a population solve (fetch it with rdis_hip_plan_fetch_population)");
-    if (L->ncomp == 0) return 0;
-    // every array is one contiguous piece of the outputs' block: straight into the caller's memory
-    const StartsView S = L->starts_view(L->ms_n);
-    const size_t sn = (size_t)L->ms_n * (size_t)L->nfree, sc = (size_t)L->ms_n * (size_t)L->ncomp;
-    auto get = [&](void* dst, const void* src, size_t bytes) {
-        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-    };
-    HIPCHK(c, get(x_out, S.xout, sn * 8));
-    HIPCHK(c, get(fret, S.fret, sc * 8));
-    HIPCHK(c, get(delta, S.delta, sc * 8));
-    HIPCHK(c, get(nfeval, S.nfeval, sc * 8));
-    HIPCHK(c, get(ngeval, S.ngeval, sc * 8));
-    HIPCHK(c, get(iters, S.iters, sc * 4));
-    HIPCHK(c, get(status, S.status, sc * 4));
-    HIPCHK(c, get(best, L->ms_best.p, (size_t)L->ncomp * 4));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return fetch_many(L, false, x_out, fret, delta, iters, status, nfeval, ngeval, best);
 }
 
 // =====================================================================================
@@ -3241,25 +3251,7 @@ extern "C" int rdis_hip_plan_solve_population(rdis_hip_plan* L, rdis_hip_populat
 extern "C" int rdis_hip_plan_fetch_population(rdis_hip_plan* L, double* x_out, double* fret, double* delta, int32_t* iters, int32_t* status,
                                               int64_t* nfeval, int64_t* ngeval) {
     if (!L) return RDIS_HIP_EINVAL;
-    rdis_hip_ctx* c = L->prob->ctx;
-    USE_DEVICE(c);
-    if (L->ms_n < 1) return fail(c, RDIS_HIP_EINVAL, "plan_fetch_population: no population solve to fetch (call rdis_hip_plan_solve_population first)");
-    if (!L->ms_population) return fail(c, RDIS_HIP_EINVAL, "plan_fetch_population: the plan's last solve of this kind was a multi-start solve (fetch it with rdis_hip_plan_fetch_starts)");
-    if (L->ncomp == 0) return 0;
-    const StartsView S = L->starts_view(L->ms_n);
-    const size_t sn = (size_t)L->ms_n * (size_t)L->nfree, sc = (size_t)L->ms_n * (size_t)L->ncomp;
-    auto get = [&](void* dst, const void* src, size_t bytes) {
-        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-    };
-    HIPCHK(c, get(x_out, S.xout, sn * 8));
-    HIPCHK(c, get(fret, S.fret, sc * 8));
-    HIPCHK(c, get(delta, S.delta, sc * 8));
-    HIPCHK(c, get(nfeval, S.nfeval, sc * 8));
-    HIPCHK(c, get(ngeval, S.ngeval, sc * 8));
-    HIPCHK(c, get(iters, S.iters, sc * 4));
-    HIPCHK(c, get(status, S.status, sc * 4));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return fetch_many(L, true, x_out, fret, delta, iters, status, nfeval, ngeval, nullptr);
 }
 
 extern "C" int rdis_hip_plan_objective_device(rdis_hip_plan* L, void** dev_ptr) {
