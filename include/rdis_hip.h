@@ -362,7 +362,45 @@ int rdis_hip_plan_fetch_starts(rdis_hip_plan *plan, double *x_out, double *fret,
  * persistent plan; default factor_rounding; emulate_stale_cache, trace_records and dump_iters off; the population must be
  * the plan's problem's.  Not yet: the cooperative and grid solvers and point-major components shared by several workgroups;
  * bundle-adjustment components on the plain batch solver; tiny and point-major components in plan_solve_starts.  Anything
- * else: RDIS_HIP_EINVAL and a message that names the cause; the plan and the population stay usable. */
+ * else: RDIS_HIP_EINVAL and a message that names the cause; the plan and the population stay usable.
+ *
+ * A restart loop on one stream: draw -> solve -> evaluate -> rank -> keep -> redraw -> solve, nothing crossing to the host until
+ * the caller asks for a result (rdis_amd/csrc/population_select.hpp; examples/ba_population_halving.py).
+ *   population_set_sampling   lo[N], hi[N]: the intervals random states are drawn from (VariableDomain::getSamplingInterval),
+ *                       copied once and kept on the device with the population (2 N doubles).  Both NULL: the problem's
+ *                       domains, the state before the first call.  One of them NULL, a non-finite bound or lo[v] > hi[v]:
+ *                       RDIS_HIP_EINVAL, the message names the first such variable, nothing changes.
+ *   population_sample   members first .. first + count - 1 at the variables vid[0 .. n) (vid == NULL: variables 0 .. n-1,
+ *                       n <= N; ranges checked like population_set_x) are drawn on the device:
+ *                       X[s][v] = closestVal_v(slo[v] + u (shi[v] - slo[v])), u = (double)(z >> 11) 2^-53, z = splitmix64 of
+ *                       seed + 0x9E3779B97F4A7C15 (stream + 1) + 0xBF58476D1CE4E5B9 (s + 1) + 0x94D049BB133111EB (v + 1) --
+ *                       HipRDISLevelOptimizer::restartValue(seed, node = stream, restart = s, vid = v, dom) bit for bit (the
+ *                       product is rounded before it is added, as the host's is), s the member's absolute row, closestVal
+ *                       clamping into the problem's lo / hi.  A value depends on (seed, stream, s, v) only -- not on how a
+ *                       range is cut into calls.  stream in [0, 2^31 - 2] (RDIS_HIP_EINVAL otherwise) is what a caller
+ *                       varies from round to round.  Asynchronous on the context's stream: with vid == NULL nothing is
+ *                       waited for; an explicit list is staged like every id list (one synchronisation).  Marks the
+ *                       evaluation stale, as population_set_x does.
+ *   population_sort     puts the members into the order of their last evaluation -- best's rule as a total order: numbers
+ *                       ascending, a tie (-0.0 against +0.0 is one) by lower index, NaNs last by index.  With order[r] the
+ *                       member of rank r, afterwards X_new[r] = X_old[order[r]] and f_new[r] = f_old[order[r]]: a pure
+ *                       permutation, the evaluation stays valid ("eval_valid" stays 1, the address population_eval_device
+ *                       handed out holds the permuted values), population_best returns member 0 and population_assign_best
+ *                       assigns row 0.  Before any evaluation or with stale values: RDIS_HIP_EINVAL ("evaluate first").
+ *                       order_out == NULL: enqueued, no wait; otherwise order_out[nmembers] is copied out (one
+ *                       synchronisation).  What a plan kept of an earlier solve (plan_fetch_population) refers to the members
+ *                       as they were numbered when that solve ran.  Memory: the permuted rows go into a second buffer of X's
+ *                       size, allocated at the first sort -- the population's device memory doubles from then on -- and the
+ *                       two buffers swap roles; RDIS_HIP_ENOMEM at that allocation leaves the population as it was.  Rank by
+ *                       counting is quadratic in the members: nmembers > 2^18 returns RDIS_HIP_ERANGE before anything is
+ *                       launched.
+ *   plan_solve_population_range   plan_solve_population restricted to members first .. first + count - 1: every (member,
+ *                       component) of the range gets the bits a whole-population solve leaves for that member, the rows
+ *                       outside the range are untouched.  count >= 1 and the range inside the population, else
+ *                       RDIS_HIP_EINVAL.  plan_fetch_population afterwards returns [count][...] arrays, row i belonging to
+ *                       member first + i.  The splitting by "starts_workspace_bytes" ("starts_per_launch" /
+ *                       "starts_launches" of count members), plan_last_kernel_ms and every refusal are the whole-population
+ *                       entry's. */
 typedef struct rdis_hip_population rdis_hip_population;
 int rdis_hip_population_create(rdis_hip_problem *p, int64_t nmembers, const double *x, rdis_hip_population **out);
 void rdis_hip_population_destroy(rdis_hip_population *pop);
@@ -377,7 +415,13 @@ int rdis_hip_population_best(rdis_hip_population *pop, int64_t *member, double *
 int rdis_hip_population_assign_best(rdis_hip_population *pop);
 int rdis_hip_population_set_option(rdis_hip_population *pop, const char *name, int64_t value);
 int rdis_hip_population_get_info(rdis_hip_population *pop, const char *name, int64_t *value);
+int rdis_hip_population_set_sampling(rdis_hip_population *pop, const double *lo, const double *hi);
+int rdis_hip_population_sample(rdis_hip_population *pop, int64_t first, int64_t count, int64_t n, const int64_t *vid,
+                               uint64_t seed, int64_t stream);
+int rdis_hip_population_sort(rdis_hip_population *pop, int64_t *order_out);
 int rdis_hip_plan_solve_population(rdis_hip_plan *plan, rdis_hip_population *pop, int32_t maxiters, double ftol);
+int rdis_hip_plan_solve_population_range(rdis_hip_plan *plan, rdis_hip_population *pop, int64_t first, int64_t count,
+                                         int32_t maxiters, double ftol);
 int rdis_hip_plan_fetch_population(rdis_hip_plan *plan, double *x_out, double *fret, double *delta, int32_t *iters,
                                    int32_t *status, int64_t *nfeval, int64_t *ngeval);
 /* sum of fret over the plan's components, left on the device (for the RCCL

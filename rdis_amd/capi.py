@@ -91,7 +91,11 @@ SYMBOLS = {
     "rdis_hip_population_assign_best": (C.c_int, [_vp]),
     "rdis_hip_population_set_option": (C.c_int, [_vp, C.c_char_p, _i64]),
     "rdis_hip_population_get_info": (C.c_int, [_vp, C.c_char_p, C.POINTER(_i64)]),
+    "rdis_hip_population_set_sampling": (C.c_int, [_vp, _vp, _vp]),
+    "rdis_hip_population_sample": (C.c_int, [_vp, _i64, _i64, _i64, _vp, C.c_uint64, _i64]),
+    "rdis_hip_population_sort": (C.c_int, [_vp, _vp]),
     "rdis_hip_plan_solve_population": (C.c_int, [_vp, _vp, C.c_int32, C.c_double]),
+    "rdis_hip_plan_solve_population_range": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int32, C.c_double]),
     "rdis_hip_plan_fetch_population": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rdis_hip_plan_objective_device": (C.c_int, [_vp, C.POINTER(_vp)]),
     "rdis_hip_comm_unique_id": (C.c_int, [_vp]),
@@ -513,6 +517,29 @@ class Population:
         """the problem's assigned x := the x of the last evaluation's best member; enqueued, nothing waited for"""
         self.ctx.check(self.ctx.lib.rdis_hip_population_assign_best(self.h))
 
+    def set_sampling(self, lo=None, hi=None):
+        """the intervals sample() draws from, [nvars] each, kept on the device; both None: the problem's domains (the default)"""
+        lo, hi = (None if lo is None else _f(lo)), (None if hi is None else _f(hi))
+        for a in (lo, hi):
+            if a is not None and a.shape != (self.nvars,):
+                raise ValueError("lo and hi must be [nvars]")
+        self.ctx.check(self.ctx.lib.rdis_hip_population_set_sampling(self.h, _ptr(lo), _ptr(hi)))
+
+    def sample(self, seed, stream, first=0, count=None, vid=None):
+        """members first .. first + count - 1 (default: to the last) drawn on the device at the variables vid (None: all): per value
+        oracle.levels.splitmix_restart_value(seed, stream, member, variable, ...) bit for bit.  Enqueued; vid=None waits for nothing"""
+        first, count = self._range(first, count)
+        vid = _i(vid)
+        n = self.nvars if vid is None else vid.shape[0]
+        self.ctx.check(self.ctx.lib.rdis_hip_population_sample(self.h, first, count, n, _ptr(vid), int(seed) & ((1 << 64) - 1), int(stream)))
+
+    def sort(self, want_order=True):
+        """the members put into the order of their last evaluation (best()'s rule: numbers ascending, ties by index, NaNs last);
+        returns order [nmembers] (int64: new row r was row order[r]), or with want_order=False None without waiting"""
+        order = np.empty(self.nmembers, np.int64) if want_order else None
+        self.ctx.check(self.ctx.lib.rdis_hip_population_sort(self.h, _ptr(order)))
+        return order
+
     def set_option(self, name: str, value: int):
         """eval_workspace_bytes (scratch of a launch of the evaluation; default 2^30), eval_batched (default 1; 0: member by member)"""
         self.ctx.check(self.ctx.lib.rdis_hip_population_set_option(self.h, name.encode(), int(value)))
@@ -651,7 +678,7 @@ class Plan:
                                                                _ptr(r.status), _ptr(r.nfeval), _ptr(r.ngeval), _ptr(r.best)))
         return r
 
-    def solve_population(self, pop: "Population", maxiters=50, ftol=3e-8):
+    def solve_population(self, pop: "Population", maxiters=50, ftol=3e-8, first=0, count=None):
         """every component on every member of pop in one launch (asynchronous): member s starts from its own x at the plan's free
         variables, reads its constants from its own x and is left assigned to its result -- what set_start(None) + solve does on a
         problem whose x is that member's.  The problem's x and the plan's ordinary outputs are not touched.  Bundle adjustment,
@@ -664,9 +691,15 @@ class Plan:
         (info("components_point_major"): too large for the LDS) as one workgroup a component (set_option("ptm_group", 1)), beside
         the others in any mix -- info("population_point_major_threads") tells the lanes of that kernel; anything
         else -- a nonlinear-product plan, tiny or point-major components without their option included -- raises RdisHipError
-        (EINVAL) with the cause"""
-        self.ctx.check(self.ctx.lib.rdis_hip_plan_solve_population(self.h, pop.h, maxiters, ftol))
-        self._nmembers = pop.nmembers
+        (EINVAL) with the cause.  first / count given: members first .. first + count - 1 only (rdis_hip_plan_solve_population_range:
+        the same bits for them, the other rows untouched); fetch_population then returns count rows, row i member first + i"""
+        if first == 0 and count is None:
+            self.ctx.check(self.ctx.lib.rdis_hip_plan_solve_population(self.h, pop.h, maxiters, ftol))
+            self._nmembers = pop.nmembers
+            return
+        first, count = pop._range(first, count)
+        self.ctx.check(self.ctx.lib.rdis_hip_plan_solve_population_range(self.h, pop.h, first, count, maxiters, ftol))
+        self._nmembers = count
 
     def fetch_population(self, want_x=True) -> StartsResult:
         """the last population solve's results, member by member (best is None: nothing is selected)"""

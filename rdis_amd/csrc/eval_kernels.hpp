@@ -9,6 +9,7 @@
 // single-block final pass), so results are bit-reproducible.
 #pragma once
 #include "solver_wg.hpp"
+#include "population_select.hpp"
 
 namespace rdis_hip {
 
@@ -139,17 +140,9 @@ population_final_sum_kernel(int n, const double* __restrict__ partial, long long
     if (threadIdx.x == 0) f[first + r] = acc;
 }
 
-// The member a population keeps, the minimum of f[members]: select_best_start_kernel's rule (solver_lds_starts.hpp), which as a
-// sequential scan reads  b = 0; for s >= 1: if (f[s] < f[b] || (f[b] != f[b] && f[s] == f[s])) b = s  -- the lowest value, on a
-// tie (-0.0 against +0.0 is one) the lowest index, a NaN never unless every value is one: then member 0.  better() is that rule as
-// a strict total order on (value, index) pairs with distinct indices, so the winner is the same whatever the reduction's shape.
+// The member a population keeps, the minimum of f[members], by better() (population_select.hpp: the argmin rule as a strict total
+// order on (value, index) pairs, shared with the population's ranking -- one definition)
 struct MemberValue { double f; long long s; };
-__device__ __forceinline__ bool better(double fa, long long sa, double fb, long long sb) {
-    const bool na = fa != fa, nb = fb != fb;
-    if (na != nb) return nb;              // a number beats a NaN
-    if (!na && fa != fb) return fa < fb;  // two different numbers: the lower
-    return sa < sb;                       // a tie, or two NaNs: the lower index
-}
 // one workgroup of 256 lanes; lanes stride over the members, then wave shuffles, then the waves' winners through LDS
 __global__ void __launch_bounds__(256)
 population_argmin_kernel(long long members, const double* __restrict__ f, MemberValue* __restrict__ best) {

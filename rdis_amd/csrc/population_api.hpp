@@ -44,5 +44,14 @@ hipError_t population_scatter_launch(hipStream_t stream, double* X, long long N,
 hipError_t population_pick_launch(hipStream_t stream, const double* X, long long N, long long first, long long count, const int* vid, long long n, double* out);
 // population_copy_rows_kernel: `rows` rows of dst, each a copy of src[N]
 hipError_t population_copy_rows_launch(hipStream_t stream, const double* src, double* dst, long long N, long long rows);
+// population_sample_kernel (population_select.hpp): members first .. first + count - 1 at the variables vid[0 .. n) (null: 0 .. n-1)
+// drawn from (seed, stream, member, variable); slo / shi the sampling intervals, lo / hi the domains, [N] each
+hipError_t population_sample_launch(hipStream_t stream, double* X, long long N, long long first, long long count, const int* vid, long long n,
+                                    unsigned long long seed, long long stream_id, const double* slo, const double* shi, const double* lo, const double* hi);
+// population_rank_kernel: order[rank of s] = s under better() on (f[s], s)
+hipError_t population_rank_launch(hipStream_t stream, long long members, const double* f, long long* order);
+// population_permute_rows_kernel: X2[r] = X[order[r]], f2[r] = f[order[r]]
+hipError_t population_permute_rows_launch(hipStream_t stream, long long members, long long N, const long long* order, const double* X, const double* f,
+                                          double* X2, double* f2);
 
 }  // namespace rdis_hip

@@ -1,12 +1,15 @@
 // population_kernels.hip -- the population kernels of the LDS-resident solver (solver_lds_population.hpp) and of the plain
 // one-workgroup solver (solver_wg_population.hpp) and their launches, a
-// translation unit of their own (rdis_hip.hip sees them through population_api.hpp).  A workgroup size becomes a template
+// translation unit of their own (rdis_hip.hip sees them through population_api.hpp), and the kernels that draw, rank and reorder
+// the members (population_select.hpp).  A workgroup size becomes a template
 // argument through launch_dispatch.hpp, with the list of starts_kernels.hip: 64 ... 768, 1024 for everything else.
+#define RDIS_POPULATION_SELECT_KERNELS   // (population_select.hpp: its three kernels are defined here and nowhere else)
 #define RDIS_LDS_NO_LAUNCHER   // (cgd_lds_kernel is instantiated where it is launched: rdis_hip.hip, refround_kernels.hip)
 #include <algorithm>
 #include "solver_lds_population.hpp"
 #include "solver_wg_population.hpp"
 #include "solver_quad_population.hpp"   // (the tiny-component solver's entry: plan option population_tiny)
+#include "population_select.hpp"        // (draw, rank, permute: what a restart loop does between two solves)
 #include "population_api.hpp"
 
 namespace rdis_hip {
@@ -75,6 +78,29 @@ hipError_t population_copy_rows_launch(hipStream_t stream, const double* src, do
     const long long total = rows * N;
     if (total <= 0) return hipSuccess;
     population_copy_rows_kernel<<<helper_grid(total), 256, 0, stream>>>(src, dst, N, total);
+    return hipGetLastError();
+}
+
+// grid (blocks over the row, members): the second dimension holds at most 65535, the kernels stride over the rest
+hipError_t population_sample_launch(hipStream_t stream, double* X, long long N, long long first, long long count, const int* vid, long long n,
+                                    unsigned long long seed, long long stream_id, const double* slo, const double* shi, const double* lo, const double* hi) {
+    if (count <= 0 || n <= 0) return hipSuccess;
+    const dim3 grid((unsigned)std::min<long long>((n + 255) / 256, 4096), (unsigned)std::min<long long>(count, 65535));
+    population_sample_kernel<<<grid, 256, 0, stream>>>(X, N, first, count, vid, n, seed, stream_id, slo, shi, lo, hi);
+    return hipGetLastError();
+}
+
+hipError_t population_rank_launch(hipStream_t stream, long long members, const double* f, long long* order) {
+    if (members <= 0) return hipSuccess;
+    population_rank_kernel<<<(unsigned)((members + 255) / 256), 256, 0, stream>>>(members, f, order);
+    return hipGetLastError();
+}
+
+hipError_t population_permute_rows_launch(hipStream_t stream, long long members, long long N, const long long* order, const double* X, const double* f,
+                                          double* X2, double* f2) {
+    if (members <= 0) return hipSuccess;
+    const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>((N + 255) / 256, 4096)), (unsigned)std::min<long long>(members, 65535));
+    population_permute_rows_kernel<<<grid, 256, 0, stream>>>(members, N, order, X, f, X2, f2);
     return hipGetLastError();
 }
 

@@ -2861,6 +2861,9 @@ struct rdis_hip_population {
     int64_t eval_per_launch = 0, eval_launches = 0;    // of the last evaluation: members of a launch, kernels launched
     bool eval_valid = false;   // f holds the values of X as it is (set_x and plan_solve_population write X: stale)
     bool best_current = false; // best holds the argmin of f
+    DevBuf slo, shi;           // [N] each: the sampling intervals of population_sample (population_set_sampling) ...
+    bool sampling_set = false; // ... false: the problem's domains
+    DevBuf X2, f2, order;      // population_sort: the other buffer of X's size (X and X2 swap roles), the permuted values, order[nmembers] (int64)
     double* row(int64_t s) const { return X.as<double>() + (size_t)s * (size_t)prob->N; }
 };
 
@@ -3114,22 +3117,101 @@ extern "C" int rdis_hip_population_get_info(rdis_hip_population* pop, const char
     return 0;
 }
 
-extern "C" int rdis_hip_plan_solve_population(rdis_hip_plan* L, rdis_hip_population* pop, int32_t maxiters, double ftol) {
-    if (!L || !pop) return RDIS_HIP_EINVAL;
+// ---- what a restart loop does between two solves: draw, rank, keep (population_select.hpp) ----
+
+extern "C" int rdis_hip_population_set_sampling(rdis_hip_population* pop, const double* lo, const double* hi) {
+    if (!pop) return RDIS_HIP_EINVAL;
+    rdis_hip_problem* p = pop->prob;
+    rdis_hip_ctx* c = p->ctx;
+    if (!lo && !hi) { pop->sampling_set = false; return 0; }   // the problem's domains again (the buffers stay: a later call reuses them)
+    if (!lo || !hi) return fail(c, RDIS_HIP_EINVAL, "population_set_sampling: lo and hi are given together (both NULL: the problem's domains)");
+    for (int64_t v = 0; v < p->N; ++v)
+        if (!std::isfinite(lo[v]) || !std::isfinite(hi[v]) || lo[v] > hi[v])
+            return fail(c, RDIS_HIP_EINVAL, "population_set_sampling: variable " + std::to_string(v) + ": the sampling interval must be finite with lo <= hi");
+    USE_DEVICE(c);
+    const size_t bytes = (size_t)p->N * sizeof(double);
+    int rc;
+    if ((rc = ensure(c, pop->slo, bytes)) || (rc = ensure(c, pop->shi, bytes))) return rc;
+    if (bytes > 0) {
+        HIPCHK(c, hipMemcpyAsync(pop->slo.p, lo, bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(pop->shi.p, hi, bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // (copied once: the caller's arrays are free again)
+    }
+    pop->sampling_set = true;
+    return 0;
+}
+
+extern "C" int rdis_hip_population_sample(rdis_hip_population* pop, int64_t first, int64_t count, int64_t n, const int64_t* vid, uint64_t seed,
+                                          int64_t stream) {
+    if (!pop || n < 0) return RDIS_HIP_EINVAL;
+    rdis_hip_problem* p = pop->prob;
+    rdis_hip_ctx* c = p->ctx;
+    if (stream < 0 || stream > 2147483646ll) return fail(c, RDIS_HIP_EINVAL, "population_sample: stream out of range (0 ... 2^31 - 2)");
+    int rc = population_range(pop, "population_sample", first, count, n, vid);
+    if (rc) return rc;
+    if (n == 0 || count == 0) return 0;
+    USE_DEVICE(c);
+    const int* dv;
+    if ((rc = stage_ids(p, n, vid, p->N, &dv))) return rc;
+    pop->eval_valid = false; pop->best_current = false;   // X is written: the values of the last evaluation are stale
+    const double *lo = p->lo.as<double>(), *hi = p->hi.as<double>();
+    HIPCHK(c, population_sample_launch(c->stream, pop->X.as<double>(), p->N, first, count, dv, n, (unsigned long long)seed, stream,
+                                       pop->sampling_set ? pop->slo.as<double>() : lo, pop->sampling_set ? pop->shi.as<double>() : hi, lo, hi));
+    return 0;
+}
+
+extern "C" int rdis_hip_population_sort(rdis_hip_population* pop, int64_t* order_out) {
+    if (!pop) return RDIS_HIP_EINVAL;
+    rdis_hip_problem* p = pop->prob;
+    rdis_hip_ctx* c = p->ctx;
+    const int64_t S_n = pop->nmembers;
+    if (S_n > (1ll << 18))
+        return fail(c, RDIS_HIP_ERANGE, "population_sort: rank by counting is quadratic in the members: at most 2^18 = 262144 (this population has " +
+                                        std::to_string(S_n) + ")");
+    if (!pop->eval_valid)
+        return fail(c, RDIS_HIP_EINVAL, "population_sort: the population has no current values (evaluate first: rdis_hip_population_eval or "
+                                        "_eval_device after the last population_set_x / population_sample / plan_solve_population)");
+    USE_DEVICE(c);
+    int rc;
+    // the second buffer of X's size, at the first sort (a failure leaves the population as it was: nothing has been launched)
+    if ((rc = ensure(c, pop->X2, pop->X.bytes)) || (rc = ensure(c, pop->f2, (size_t)S_n * sizeof(double))) ||
+        (rc = ensure(c, pop->order, (size_t)S_n * sizeof(long long))))
+        return rc;
+    HIPCHK(c, population_rank_launch(c->stream, S_n, pop->f.as<double>(), pop->order.as<long long>()));
+    HIPCHK(c, population_permute_rows_launch(c->stream, S_n, p->N, pop->order.as<long long>(), pop->X.as<double>(), pop->f.as<double>(),
+                                             pop->X2.as<double>(), pop->f2.as<double>()));
+    // X and X2 swap roles (every entry reads pop->X when it is called, and the stream orders the work); f keeps its address -- what
+    // population_eval_device handed out stays valid -- and takes the permuted values
+    std::swap(pop->X.p, pop->X2.p);
+    std::swap(pop->X.bytes, pop->X2.bytes);
+    HIPCHK(c, hipMemcpyAsync(pop->f.p, pop->f2.p, (size_t)S_n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    pop->best_current = false;   // (the argmin is member 0 now: selected again when it is asked for; eval_valid stays)
+    if (order_out) {
+        static_assert(sizeof(long long) == sizeof(int64_t), "order is copied out as it lies");
+        HIPCHK(c, hipMemcpyAsync(order_out, pop->order.p, (size_t)S_n * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
+namespace {
+// rdis_hip_plan_solve_population on members first0 .. first0 + S_n - 1: the member base is X + first0 N, the per-call arrays
+// (start rows, outputs, replicas) are sized and indexed for the S_n members of the range, so member first0 + i is row i of
+// plan_fetch_population.  `who` names the entry in messages.
+int solve_population_range(rdis_hip_plan* L, rdis_hip_population* pop, int64_t first0, const int64_t S_n, int32_t maxiters, double ftol, const char* who_name) {
     rdis_hip_problem* p = L->prob;
     rdis_hip_ctx* c = p->ctx;
-    USE_DEVICE(c);
-    const int64_t S_n = pop->nmembers;
-    if (maxiters <= 0) return fail(c, RDIS_HIP_EINVAL, "plan_solve_population: maxiters must be positive");
-    if (pop->prob != p) return fail(c, RDIS_HIP_EINVAL, "plan_solve_population: the population belongs to another problem than the plan's");
+    const std::string who(who_name);
+    if (maxiters <= 0) return fail(c, RDIS_HIP_EINVAL, who + ": maxiters must be positive");
+    if (pop->prob != p) return fail(c, RDIS_HIP_EINVAL, who + ": the population belongs to another problem than the plan's");
     if (p->kind != KIND_BA && !L->population_plain)
-        return fail(c, RDIS_HIP_EINVAL, "plan_solve_population: nonlinear-product plans are solved on a population only with the plan option population_plain = 1 "
+        return fail(c, RDIS_HIP_EINVAL, who + ": nonlinear-product plans are solved on a population only with the plan option population_plain = 1 "
                                         "(the plain batch solver, solver_wg_population.hpp; without it: bundle adjustment on the LDS-resident solver only)");
     if (S_n >= (1ll << 31) || (double)S_n * (double)std::max<int64_t>(std::max(L->nfree, L->ncomp), 1) >= 9.0e15)
-        return fail(c, RDIS_HIP_ERANGE, "plan_solve_population: too many members");
-    if (int rc = refuse_late_exponential(L, "plan_solve_population")) return rc;   // (nonlinear products only: no bundle-adjustment factor is exponential)
+        return fail(c, RDIS_HIP_ERANGE, who + ": too many members");
+    if (int rc = refuse_late_exponential(L, who_name)) return rc;   // (nonlinear products only: no bundle-adjustment factor is exponential)
     bool plain = false;
-    if (int rc = starts_refusal(L, "plan_solve_population", &plain, "population", L->population_tiny != 0, L->population_point_major != 0)) return rc;
+    if (int rc = starts_refusal(L, who_name, &plain, "population", L->population_tiny != 0, L->population_point_major != 0)) return rc;
     // point-major components (option population_point_major: the refusal above let them pass) run as one workgroup a component, the
     // bits of launch_ptm -- a group, a wide group or local camera numbering changes the order of every sum
     const int nptm = (L->population_point_major && !plain) ? L->rest_ptm : 0;
@@ -3139,7 +3221,7 @@ extern "C" int rdis_hip_plan_solve_population(rdis_hip_plan* L, rdis_hip_populat
         bool wide = false;
         if (int rc = ptm_launch_shape(L, false, &ptm_threads, &K, &wide)) return rc;
         if (K >= 2)
-            return fail(c, RDIS_HIP_EINVAL, "plan_solve_population: point-major components are solved on a population as one workgroup a component, and this plan's "
+            return fail(c, RDIS_HIP_EINVAL, who + ": point-major components are solved on a population as one workgroup a component, and this plan's "
                                             "ordinary solve would run them as " + std::string(wide ? "wide " : "") + "groups of " + std::to_string(K) +
                                             " workgroups (other sums, other bits): set the plan option ptm_group = 1");
     }
@@ -3184,6 +3266,7 @@ extern "C" int rdis_hip_plan_solve_population(rdis_hip_plan* L, rdis_hip_populat
     if (rc) return rc;
     L->ms_n = 0;   // (what an earlier call left is overwritten from here on)
 
+    double* const Xb = pop->row(first0);   // the range's member 0: every launch below counts its members from here
     const ProblemView P = p->view();
     PlanView V = L->view();   // (order: the whole batch list -- tiny components first, then empty ones and those of the plan's other solver, heaviest first)
     StartsView S = L->starts_view(S_n);
@@ -3191,7 +3274,7 @@ extern "C" int rdis_hip_plan_solve_population(rdis_hip_plan* L, rdis_hip_populat
     double* const XR = tiny_records ? S.ws + (size_t)R * work_doubles : nullptr;   // [R][N], behind the launch's replicas of ws and gfac
     if (plain) S.dir = L->ms_dir.as<double>();   // (no replica of x: the member's row serves, solver_wg_population.hpp)
     // every member's start row: its own x at the plan's free variables (plan_set_start(plan, NULL) on that x)
-    HIPCHK(c, population_gather_launch(c->stream, pop->X.as<double>(), p->N, V.free_vid, L->nfree, S_n, L->ms_in.as<double>()));
+    HIPCHK(c, population_gather_launch(c->stream, Xb, p->N, V.free_vid, L->nfree, S_n, L->ms_in.as<double>()));
     const int threads = plain ? wg_launch_threads(L) : L->rest_lds > 0 ? lds_launch_threads(L) : 64;
     const size_t dyn = L->lds_dyn_bytes(c);
     ProblemView PT = P;   // the tiny launch's: records of the launch's members or per-factor rotations (the quad solver has no refresh)
@@ -3218,22 +3301,22 @@ extern "C" int rdis_hip_plan_solve_population(rdis_hip_plan* L, rdis_hip_populat
         const int ns = (int)std::min(R, S_n - first);
         if (ntiny > 0) {
             // the records of THIS launch's members: the replicas held another launch's until now (solver_quad_population.hpp)
-            if (tiny_records) HIPCHK(c, population_rotations_launch(c->stream, pop->X.as<double>(), p->N, first, ns, p->cam_blocks.as<int>(), (int)p->ncam_blocks, XR));
+            if (tiny_records) HIPCHK(c, population_rotations_launch(c->stream, Xb, p->N, first, ns, p->cam_blocks.as<int>(), (int)p->ncam_blocks, XR));
             HIPCHK(c, hipMemsetAsync(L->ms_queue.p, 0, (size_t)ns * sizeof(int), c->stream));
             const int G = L->tiny_group == 4 ? 4 : 16;
             const int gx = tiny_population_blocks(ntiny, (G == 4 ? QUAD_THREADS : 64) / G, L->tiny_population_fill * std::max(1, G == 4 ? L->group_blocks4 : L->group_blocks16), ns, L->tiny_max_blocks);
-            HIPCHK(c, population_launch_tiny(G, gx, ns, c->stream, PT, V, S, pop->X.as<double>(), XR, L->rest_order.as<int>(), ntiny, L->ms_queue.as<int>(), maxiters, ftol));
+            HIPCHK(c, population_launch_tiny(G, gx, ns, c->stream, PT, V, S, Xb, XR, L->rest_order.as<int>(), ntiny, L->ms_queue.as<int>(), maxiters, ftol));
             L->ms_tiny_blocks = gx;
             ++L->last_launches;
         }
         if (nptm_listed > 0) {
-            HIPCHK(c, population_launch_ptm(L->ptm_rot_mode, ptm_threads, nptm_listed, ns, ptm_dyn, c->stream, P, VM, S, RP, pop->X.as<double>(), maxiters, ftol,
+            HIPCHK(c, population_launch_ptm(L->ptm_rot_mode, ptm_threads, nptm_listed, ns, ptm_dyn, c->stream, P, VM, S, RP, Xb, maxiters, ftol,
                                             L->ptm_ncb_cap));
             ++L->last_launches;
         }
         if (nlisted > 0) {
-            if (plain) HIPCHK(c, population_launch_wg(threads, nlisted, ns, c->stream, P, VR, S, pop->X.as<double>(), maxiters, ftol));
-            else HIPCHK(c, population_launch(L->lds_rot_mode, threads, nlisted, ns, dyn, c->stream, P, VR, S, pop->X.as<double>(),
+            if (plain) HIPCHK(c, population_launch_wg(threads, nlisted, ns, c->stream, P, VR, S, Xb, maxiters, ftol));
+            else HIPCHK(c, population_launch(L->lds_rot_mode, threads, nlisted, ns, dyn, c->stream, P, VR, S, Xb,
                                         maxiters, ftol, L->lds_ns_cap, L->lds_ncb_cap, L->lds_chunk_cap));
             ++L->last_launches;
         }
@@ -3246,6 +3329,23 @@ extern "C" int rdis_hip_plan_solve_population(rdis_hip_plan* L, rdis_hip_populat
     L->ms_per_launch = R;
     L->ms_launches = L->last_launches;
     return 0;
+}
+}  // namespace
+
+extern "C" int rdis_hip_plan_solve_population(rdis_hip_plan* L, rdis_hip_population* pop, int32_t maxiters, double ftol) {
+    if (!L || !pop) return RDIS_HIP_EINVAL;
+    USE_DEVICE(L->prob->ctx);
+    return solve_population_range(L, pop, 0, pop->nmembers, maxiters, ftol, "plan_solve_population");
+}
+
+extern "C" int rdis_hip_plan_solve_population_range(rdis_hip_plan* L, rdis_hip_population* pop, int64_t first, int64_t count, int32_t maxiters,
+                                                    double ftol) {
+    if (!L || !pop) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = L->prob->ctx;
+    USE_DEVICE(c);
+    if (count < 1 || first < 0 || first > pop->nmembers || count > pop->nmembers - first)
+        return fail(c, RDIS_HIP_EINVAL, "plan_solve_population_range: members out of range (count >= 1, first + count <= nmembers)");
+    return solve_population_range(L, pop, first, count, maxiters, ftol, "plan_solve_population_range");
 }
 
 extern "C" int rdis_hip_plan_fetch_population(rdis_hip_plan* L, double* x_out, double* fret, double* delta, int32_t* iters, int32_t* status,

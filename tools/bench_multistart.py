@@ -2,7 +2,7 @@
 """Multi-start solves measured: rdis_hip_plan_solve_starts against the same starts solved one by one.
 
   python tools/bench_multistart.py            # both steps, one JSON line
-  python tools/bench_multistart.py --step config3|config5s|config2|population|population-nlp|population-tiny|population-eval|population-point-major   # one step, in this process
+  python tools/bench_multistart.py --step config3|config5s|config2|population|population-nlp|population-tiny|population-eval|population-point-major|population-halving   # one step, in this process
 
 config3   BASELINE config 3 (ladybug 5 cameras / 30 points, one component): 320 one-ulp starts -- those of the end-value fixture,
           tests/golden/end_values.json -- in one call, and the same 320 by set_start / solve / fetch on the same plan.
@@ -33,6 +33,14 @@ population-point-major  full ladybug as ONE component (what optBA's sample loop 
           one through set_x / set_start(None) / solve / get_x; last_kernel_ms of the population launch in units of one ordinary
           solve's (cgd_ptm_kernel, whose code and registers are the parent commit's); whether both routes left the same bytes.
           Not part of the run without --step (it is asked for by name).
+population-halving  ladybug 5 / 30, 256 members DRAWN ON THE DEVICE from the sampling intervals (rdis_hip_population_sample), four rounds of
+          camera plan + point plan on the members 0 .. k-1, evaluation, ranking, k //= 2 (256, 128, 64, 32 members solved): (a) through
+          rdis_hip_plan_solve_population_range / _population_eval_device / _population_sort, one read at the end; (b) the same halving
+          the way before those entries: eval, the host's sort by the same rule, get_x of the survivors, a new population from them;
+          (c) all 256 members in all four rounds (context).  The ways alternate within the job.  Wall time and summed kernel ms of each,
+          whether (a) and (b) end with the same order and the same bytes in the surviving rows, the best value of (a) and (c).  Then the
+          wall time of sort alone (between two synchronisations) at 256, 4096 and 65535 members, and of sample of 256 whole members of
+          full ladybug against the host's draw + set_x of the same 48.7 MB.  Asked for by name, like population-point-major.
 Every step runs in a child process under a time limit of its own; a step that fails ends the run.  Wall times are the median of
 `--repeats` calls after one warm-up call; kernel_ms is rdis_hip_plan_last_kernel_ms of the last call."""
 import argparse
@@ -48,7 +56,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 STEP_LIMIT_S = {"config3": 240, "config5s": 240, "config2": 240, "population": 240, "population-nlp": 240, "population-tiny": 240, "population-eval": 240,
-                "population-point-major": 420}
+                "population-point-major": 420, "population-halving": 420}
 STEPS = ("config3", "config5s", "config2", "population", "population-nlp", "population-tiny", "population-eval")
 
 
@@ -470,8 +478,143 @@ def measure_population_eval(repeats):
             "ladybug_full": shape(P.load_bal(), 64, lds, {"population_tiny": 1})}
 
 
+def measure_population_halving(repeats, members=256, rounds=4):
+    """successive halving on the device against the way without sample / sort / a member range, and the three pieces alone"""
+    from rdis_amd import capi, problems as P
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    from ba_multistart import sampling_intervals
+    from ba_population import OPTIONS
+    seed = 0x5D15
+    pp = P.load_bal(ncams=5, npts=30)
+    cams, pts = P.ba_alternation_plans(pp)
+    lo, hi = sampling_intervals(pp)
+    ctx = capi.Context(0)
+    g = capi.Problem(ctx, pp)
+    plans = [capi.Plan(g, *cams), capi.Plan(g, *pts)]
+    for plan in plans:
+        for k, v in OPTIONS.items():
+            plan.set_option(k, v)
+        assert plan.info("components_lds") == plan.ncomp
+    pop = capi.Population(g, members)
+    pop.set_sampling(lo, hi)
+    pop.sample(seed, 0)
+    X0 = pop.get_x()
+
+    def rule_order(f):
+        return np.array(sorted(range(len(f)), key=lambda s: (f[s] != f[s], 0.0 if f[s] != f[s] else f[s], s)), dtype=np.int64)
+
+    def on_device(halve=True, read_orders=False, kernel_ms=None):
+        """(a), or with halve=False (c): all members in every round"""
+        t = time.perf_counter()
+        pop.sample(seed, 0)
+        k, ids = members, np.arange(members)
+        for _ in range(rounds):
+            for plan in plans:
+                plan.solve_population(pop, 25, 3e-8, first=0, count=k)
+                if kernel_ms is not None:
+                    kernel_ms.append(plan.last_kernel_ms()[0])
+            pop.eval_device()
+            order = pop.sort(want_order=read_orders)
+            if read_orders:
+                ids = ids[order]
+            if halve:
+                k //= 2
+        pop.assign_best()
+        x = g.get_x()                                       # the one read
+        return time.perf_counter() - t, x, ids, k
+
+    def on_host(kernel_ms=None):
+        """(b): eval, the host's sort by the same rule, get_x of the survivors, a new Population from them"""
+        t = time.perf_counter()
+        part, ids = capi.Population(g, x=X0), np.arange(members)
+        for _ in range(rounds):
+            for plan in plans:
+                plan.solve_population(part, 25, 3e-8)
+                if kernel_ms is not None:
+                    kernel_ms.append(plan.last_kernel_ms()[0])
+            keep = rule_order(part.eval())[:part.nmembers // 2]
+            rows = part.get_x()[keep]
+            ids = ids[keep]
+            part.close()
+            part = capi.Population(g, x=rows)
+        part.assign(0)
+        x = g.get_x()
+        dt = time.perf_counter() - t
+        part.close()
+        return dt, x, ids, rows
+
+    on_device(); on_host(); on_device(halve=False)          # (warm-up: tables, buffers, first launches)
+    ta, tb, tc = [], [], []
+    for _ in range(repeats):                                # the ways alternate within the job
+        ta.append(on_device()[0]); tb.append(on_host()[0]); tc.append(on_device(halve=False)[0])
+    ka, kb, kc = [], [], []
+    _, xa, ids_a, k_end = on_device(read_orders=True, kernel_ms=ka)
+    rows_a = pop.get_x(first=0, count=k_end)
+    fa = pop.best()[1]
+    _, xb, ids_b, rows_b = on_host(kernel_ms=kb)
+    on_device(halve=False, kernel_ms=kc)
+    fc = pop.best()[1]
+    out = {"members": members, "rounds": rounds, "survivors": k_end,
+           "device_wall_ms": 1e3 * float(np.median(ta)), "device_wall_ms_all": [1e3 * t for t in ta], "device_kernel_ms": float(sum(ka)),
+           "host_wall_ms": 1e3 * float(np.median(tb)), "host_wall_ms_all": [1e3 * t for t in tb], "host_kernel_ms": float(sum(kb)),
+           "all_members_wall_ms": 1e3 * float(np.median(tc)), "all_members_kernel_ms": float(sum(kc)),
+           "same_order": bool(ids_a[:k_end].tolist() == ids_b.tolist()), "same_surviving_rows": bool(rows_a.tobytes() == rows_b.tobytes()),
+           "same_x": bool(xa.tobytes() == xb.tobytes()), "best_f_halving": fa, "best_f_all_members": fc}
+    out["host_over_device"] = out["host_wall_ms"] / out["device_wall_ms"]
+    out["device_faster_beyond_host_spread"] = bool(out["host_wall_ms"] - out["device_wall_ms"] > 1e3 * (max(tb) - min(tb)))
+    pop.close()
+
+    # sort alone: eval once, then sort (enqueued) + synchronize, the wall time between two synchronisations
+    sort_ms = {}
+    for n in (256, 4096, 65535):
+        q = capi.Population(g, n)
+        q.set_sampling(lo, hi)
+        q.sample(seed, 1)
+        q.eval_device()
+        q.sort(want_order=False)                            # (the second buffer, the first launch)
+        ts = []
+        for r in range(5):
+            q.sample(seed, 2 + r)
+            q.eval_device()
+            ctx.synchronize()
+            t = time.perf_counter()
+            q.sort(want_order=False)
+            ctx.synchronize()
+            ts.append(time.perf_counter() - t)
+        sort_ms[str(n)] = 1e3 * float(np.median(ts))
+        q.close()
+    out["sort_wall_ms_by_members"] = sort_ms
+
+    # sample alone: 256 whole members of full ladybug against the host's draw + set_x of the same bytes
+    pf = P.load_bal()
+    gf = capi.Problem(ctx, pf)
+    flo, fhi = sampling_intervals(pf)
+    q = capi.Population(gf, 256)
+    q.set_sampling(flo, fhi)
+    rng = np.random.default_rng(0)
+
+    def draw_device():
+        t = time.perf_counter()
+        q.sample(seed, 0)
+        ctx.synchronize()
+        return time.perf_counter() - t
+
+    def draw_host():
+        t = time.perf_counter()
+        q.set_x(rng.uniform(flo, fhi, size=(256, pf.nvars)))
+        return time.perf_counter() - t
+
+    draw_device(); draw_host()
+    out["sample_full_ladybug"] = {"members": 256, "bytes": 256 * pf.nvars * 8,
+                                  "device_wall_ms": 1e3 * float(np.median([draw_device() for _ in range(5)])),
+                                  "host_draw_set_x_wall_ms": 1e3 * float(np.median([draw_host() for _ in range(5)]))}
+    return out
+
+
 def step(name, repeats):
     from rdis_amd import problems as P
+    if name == "population-halving":
+        return measure_population_halving(repeats)
     if name == "population-eval":
         return measure_population_eval(repeats)
     if name == "population-tiny":
