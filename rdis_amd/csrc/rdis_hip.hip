@@ -1,33 +1,20 @@
 // rdis_hip.hip -- implementation of the C ABI in include/rdis_hip.h: handle
 // management, uploads, plan construction (validation + gather lists) and kernel
-// launches.  gfx950 only; no CPU evaluation path exists in this library.
-#include "../../include/rdis_hip.h"
+// launches.  gfx950 only; no CPU evaluation path exists in this library.  The collectives (comm.hip) and a plan's queries
+// (plan_query.hip) are host-only translation units of their own; abi_state.hpp is what the three share.
+#include "abi_state.hpp"
 
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <chrono>
-#include <cstring>
-#include <memory>
 #include <new>
 #include <numeric>
-#include <string>
-#include <vector>
 
-#include "host_blocks.hpp"
-#include "plan_tables.hpp"
-#include "components.hpp"
-#include "lm_solver.hpp"
 #include "eval_kernels.hpp"
-#include "grad_fused.hpp"
 #include "refround_api.hpp"
 #include "solver_coop.hpp"
 #include "solver_lds.hpp"
-#include "ptm_api.hpp"
-#include "starts_api.hpp"
 #include "population_api.hpp"
 #include "population_grid.hpp"
 #include "solver_pipe.hpp"
@@ -36,6 +23,10 @@
 
 using namespace rdis_hip;
 
+// what abi_state.hpp and plan_options.hpp restate of the headers above for the translation units that do not see them
+static_assert(ABI_LDS_MAX_BYTES == LDS_MAX_BYTES && ABI_PIPE_TM == PIPE_TM && OPTION_QUAD_MAX_VARS == QUAD_MAX_VARS &&
+              OPTION_COOP_MAX_WG == COOP_MAX_WG && OPTION_PTM_MAX_GROUP == PTM_WIDE_MAX_GROUP, "a restated constant differs from its original");
+
 // The one place that knows there are two roundings: a solver's launches in the default rounding (fused multiply-adds), and
 // the set to use (refround_api.hpp).  A plan asks with coop_reference_rounding() or batch_reference_rounding().
 static const SolverSet& solver_set(bool reference_rounding) {
@@ -43,396 +34,16 @@ static const SolverSet& solver_set(bool reference_rounding) {
     return reference_rounding ? refround_solvers() : fused;
 }
 
-struct rdis_hip_ctx {
-    int device = 0;                   // the device as the caller names it
-    int phys = 0;                     // ... and the GPU behind it (the same, except under RDIS_HIP_VIRTUAL_DEVICES: tests)
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    int num_cus = 0;
-    std::string err;
-    // second stream for the batched launch of a plan that also has cooperative launches (they overlap)
-    hipStream_t aux = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    // resident-workgroup caps of the cooperative layouts on THIS device (occupancy queries, asked once per context)
-    int cap_pipe = -1, cap_coop[3] = {-1, -1, -1};
-    int cap_pipe_rr = -1, cap_coop_rr[3] = {-1, -1, -1};   // ... of the reference-rounding instantiations (refround_api.hpp)
-    // dynamic LDS a launch may ask for on THIS device: what a compute unit has, less the solvers' static share (at most
-    // solver_lds.hpp's LDS_MAX_BYTES, which is gfx950's); components that do not fit go to the solvers that need none
-    size_t lds_limit = LDS_MAX_BYTES;
-};
-
-namespace {
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    bool owned = true;  // false: a slice of the problem's arena
-    bool host = false;  // pinned host memory (hipHostMalloc), mapped into the device's address space
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes), owned(o.owned), host(o.host) { o.p = nullptr; o.bytes = 0; }
-    ~DevBuf() { release(); }
-    void release() { if (p && owned) (void)(host ? hipHostFree(p) : hipFree(p)); p = nullptr; bytes = 0; owned = true; host = false; }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-int fail(rdis_hip_ctx* c, int code, const std::string& msg) {
-    if (c) c->err = msg;
-    return code;
+// (the plan's methods that need a solver header)
+int rdis_hip_plan::coop_lanes() const { return pipelined() ? PIPE_LANES : coop_threads; }
+bool rdis_hip_plan::lds_matrix_on(const rdis_hip_ctx* c) const {
+    return lds_matrix != 0 && !emulate_stale && factor_rounding != 1 &&
+           lds_matrix_offset(lds_bytes_for(lds_ns_cap, lds_ncb_cap, lds_chunk_cap)) + lds_matrix_bytes(lds_ncb_cap) <= c->lds_limit;
 }
-// Several contexts from one thread (OptimizableFunction::setDevices): every entry point must make its context's device current
-// before it allocates or launches.  A box with ONE GPU cannot show a forgotten one -- so RDIS_HIP_VIRTUAL_DEVICES=n (tests) makes
-// the library offer n devices that all stand on GPU 0, remember which of them the calling thread made current last
-// (make_current), and refuse every HIP call issued for a context while another context's device is the current one.
-inline int virtual_devices() {
-    static const int n = [] { const char* e = std::getenv("RDIS_HIP_VIRTUAL_DEVICES"); return e ? std::max(0, std::atoi(e)) : 0; }();
-    return n;
+size_t rdis_hip_plan::lds_dyn_bytes(const rdis_hip_ctx* c) const {
+    const size_t base = lds_bytes_for(lds_ns_cap, lds_ncb_cap, lds_chunk_cap);
+    return lds_matrix_on(c) ? lds_matrix_offset(base) + lds_matrix_bytes(lds_ncb_cap) : base;
 }
-inline int& current_logical_device() { static thread_local int d = -1; return d; }
-inline hipError_t make_current(const rdis_hip_ctx* c) { current_logical_device() = c->device; return hipSetDevice(c->phys); }
-#define HIPCHK(ctx, expr)                                                                    \
-    do {                                                                                     \
-        if (virtual_devices() > 0 && (ctx) != nullptr && current_logical_device() != (ctx)->device)  \
-            return fail((ctx), RDIS_HIP_EDEVICE, std::string(#expr) + ": issued while device " + std::to_string(current_logical_device()) + \
-                        " is current, for a context of device " + std::to_string((ctx)->device) + " (an entry point that did not make its device current)"); \
-        hipError_t e__ = (expr);                                                             \
-        if (e__ != hipSuccess)                                                               \
-            return fail((ctx), e__ == hipErrorOutOfMemory ? RDIS_HIP_ENOMEM : RDIS_HIP_EDEVICE, \
-                        std::string(#expr) + ": " + hipGetErrorString(e__));                 \
-    } while (0)
-
-// Every entry point makes its context's device the calling thread's current one first: a host that drives several
-// contexts from one thread (rdis::OptimizableFunction::setDevices) would otherwise allocate, create events and launch
-// on whichever device its previous call left current.
-#define USE_DEVICE(ctx)                                        \
-    do {                                                       \
-        hipError_t d__ = make_current(ctx);                    \
-        HIPCHK((ctx), d__);                                    \
-    } while (0)
-
-int dalloc(rdis_hip_ctx* c, DevBuf& b, size_t bytes) {
-    b.release();
-    if (bytes == 0) bytes = 8;
-    HIPCHK(c, hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
-    b.owned = true;
-    return 0;
-}
-// pinned host memory, mapped into the device's address space (the same pointer on both sides)
-int halloc(rdis_hip_ctx* c, DevBuf& b, size_t bytes) {
-    b.release();
-    if (bytes == 0) bytes = 8;
-    HIPCHK(c, hipHostMalloc(&b.p, bytes, hipHostMallocDefault));
-    b.bytes = bytes;
-    b.owned = true;
-    b.host = true;
-    return 0;
-}
-template <class T>
-int upload(rdis_hip_ctx* c, DevBuf& b, const T* src, size_t n) {
-    int rc = dalloc(c, b, n * sizeof(T));
-    if (rc) return rc;
-    if (n) HIPCHK(c, hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
-    return 0;
-}
-template <class T>
-int upload(rdis_hip_ctx* c, DevBuf& b, const std::vector<T>& v) { return upload(c, b, v.data(), v.size()); }
-inline int upload(rdis_hip_ctx* c, DevBuf& b, const ivec& v) { return upload(c, b, v.data(), v.size()); }
-
-int grid_for(const rdis_hip_ctx* c, long long work, int threads) {
-    long long blocks = (work + threads - 1) / threads;
-    const long long cap = (long long)std::max(1, c->num_cus) * 8;  // grid-stride beyond 8 blocks/CU
-    return (int)std::max(1ll, std::min(blocks, cap));
-}
-
-}  // namespace
-
-struct VarMark { int stamp, owner, gidx, pad; };
-
-// the fused gradient pass's tables for one factor list (grad_fused.hpp), kept by the problem
-struct GradPlan {
-    unsigned long long key0 = 0, key1 = 0, used = 0;   // two hashes of the id list (0, 0: all factors); last use
-    int64_t nf = 0;
-    DevBuf ints, shorts, fac;      // one int32 block, one 16-bit block, the list as int32 (explicit lists)
-    DevBuf cstage, pstage, partial;
-    std::vector<int64_t> ids;      // the list itself (explicit lists): compared on a hash hit -- two lists with the same hashes must not share tables
-    size_t device_bytes() const { return ints.bytes + shorts.bytes + fac.bytes + cstage.bytes + pstage.bytes + partial.bytes; }
-    rdis_hip::GradTables T{};
-};
-
-struct rdis_hip_problem {
-    rdis_hip_ctx* ctx = nullptr;
-    int kind = KIND_BA;
-    int64_t N = 0, F = 0, nnz = 0;
-    int each_rounding = 0;             // rdis_hip_set_factor_rounding: how eval_each / grad_each_ba round (1: like the reference's build)
-    DevBuf x, lo, hi, cam, pt, obs, coeff, rowptr, vid, expo, cons, sine;
-    DevBuf useexp;                     // per factor: value = coeff * exp(-product) (rdis_hip_nlp_set_exponential)
-    std::vector<uint8_t> h_useexp;     // empty: no factor has it
-    DevBuf cam_blocks, xrot;                        // distinct camera blocks; their rotation records (shadow of x)
-    int64_t ncam_blocks = 0;
-    ivec h_block_of;                    // [N] first variable id of the camera block a variable belongs to, -1 = none
-    ivec h_ptblock_of;                  // [N] ... of the point block, -1 = none (valid when ncam_blocks > 0)
-    ivec h_blk_stamp, h_blk_idx;        // [N] scratch of the slot tables (solver_lds.hpp), valid by stamp
-    ivec h_cam, h_pt, h_rowptr, h_vid;  // host copies for plan building
-    // scratch for the eval entry points
-    DevBuf gfac, partial, scalar, tmp_idx, tmp_val, tmp_out, g_all;
-    DevBuf all_v2s_ptr, all_v2s_idx;  // gather lists for "all factors"
-    bool have_all_v2s = false;
-    // fused value + gradient (bundle adjustment with disjoint blocks): per-call camera records, the lists' tables
-    DevBuf camrec;
-    ivec h_cam_ord;                   // [N] ordinal of the camera block that starts at a variable id, -1 = none
-    std::vector<std::unique_ptr<GradPlan>> grad_plans;
-    unsigned long long grad_tick = 0;
-    // shared by the plans of this problem (solves on a context are serialised)
-    DevBuf dir, coop_state, coop_timing;   // search direction by variable id (kept zero between solves), ...
-    int coop_state_gen = 0;                // bumped whenever coop_state moves: plans re-derive the pointers they baked in
-    DevBuf arena;                          // memory of the transient plan of rdis_hip_cgd_batch
-    DevBuf stage_x;                        // pinned staging of a resident plan's start point (rdis_hip_plan_set_start)
-    hipEvent_t stage_ev = nullptr;         // ... recorded behind its copy: the next use waits for it
-    bool stage_busy = false;
-    size_t arena_used = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct rdis_hip_plan* last_timed_plan = nullptr;
-    ivec h_local, h_owner_stamp, h_fac_stamp;  // validity by stamp: no O(N) clears per call
-    std::vector<VarMark> h_mark;           // [N] plan_create's view of a variable: free in which component, where in the free list
-    LmWorkspace lm_ws;                     // scratch of rdis_hip_lm_optimize, kept between calls
-    CcWorkspace cc_ws;                     // ... and of rdis_hip_components
-    ComponentLists comps;                  // result of the last rdis_hip_components call
-    DevBuf assigned;
-    int stamp = 0;
-    ~rdis_hip_problem() { if (ev0) (void)hipEventDestroy(ev0); if (ev1) (void)hipEventDestroy(ev1); if (stage_ev) (void)hipEventDestroy(stage_ev); }
-
-    ProblemView view() const {
-        ProblemView v{};
-        v.kind = kind; v.N = (int)N; v.F = (int)F;
-        v.x = x.as<double>(); v.lo = lo.as<double>(); v.hi = hi.as<double>();
-        v.cam = cam.as<int>(); v.pt = pt.as<int>(); v.obs = obs.as<double2>();
-        v.xrot = nullptr; v.rot_mode = ROT_PER_FACTOR;
-        v.coeff = coeff.as<double>(); v.rowptr = rowptr.as<int>(); v.vid = vid.as<int>();
-        v.expo = expo.as<double>(); v.cons = cons.as<double>(); v.sine = sine.as<uint8_t>();
-        v.useexp = h_useexp.empty() ? nullptr : useexp.as<uint8_t>();
-        return v;
-    }
-    int64_t nslots() const { return kind == KIND_BA ? 12 * F : nnz; }
-    int arity(int f) const { return kind == KIND_BA ? 12 : h_rowptr[f + 1] - h_rowptr[f]; }
-    int var_of(int f, int k) const {
-        if (kind == KIND_BA) return k < 9 ? h_cam[f] + k : h_pt[f] + (k - 9);
-        return h_vid[h_rowptr[f] + k];
-    }
-    int slot_of(int f, int k) const { return kind == KIND_BA ? 12 * f + k : h_rowptr[f] + k; }
-};
-
-
-struct CoopItem {
-    int comp = 0, nwg = 0;
-    size_t xi_off = 0;  // where its published search direction starts in the plan's xi_glob
-    // offsets into the plan's coop_ints block (one upload for all cooperative components)
-    size_t slot_li = 0;   // [12 * m] local free index of each factor slot, -1 = constant
-    size_t lane_var = 0;  // [nwg * threads] free variable owned by a lane, -1 = none
-    size_t wave_var = 0;  // [nwg * threads / 64] free variable owned by a whole wave, -1 = none
-};
-
-struct CoopLaunch {      // cooperative groups that run side by side in one launch
-    int first = 0, count = 0, total_wg = 0;   // items [first, first + count) of the plan's list
-    DevBuf groups, wg_group;
-};
-
-struct StreamItem {
-    int comp = 0, nwg = 0, nlong = 0;
-    DevBuf long_vars;  // local indices of the variables fed by many partials
-};
-
-struct rdis_hip_plan {
-    rdis_hip_problem* prob = nullptr;
-    bool transient = false;  // lives in the problem's arena (rdis_hip_cgd_batch): one at a time
-    size_t dev_bytes = 0;    // device memory of its own (plan_alloc; rdis_hip_plan_device_bytes)
-    int64_t ncomp = 0, nfree = 0, nfac = 0, nslots = 0, ngfac = 0;
-    // one device block of int32 (order | free_ptr | free_vid | fac_ptr | fac_id | v2s_ptr |
-    // slot_base | slot_pos) and one of results (see out_layout)
-    DevBuf ints, ws, gfac, xstart, outbuf, objective, trace, vdump;
-    size_t off_order = 0, off_free_ptr = 0, off_free_vid = 0, off_fac_ptr = 0, off_fac_id = 0, off_v2s_ptr = 0,
-           off_slot_base = 0, off_slot_pos = 0;
-    // results block: xout[nfree] fret[nc] delta[nc] (f64) | nfeval[nc] ngeval[nc] (i64) | iters[nc] status[nc] trace_n[nc] (i32)
-    size_t out_bytes = 0;
-    cvec h_out;
-    ivec h_blk;   // host image of `ints` (kept alive: its upload is asynchronous)
-    ivec h_order, h_fac_ptr, h_free_ptr, h_free_vid, h_fac_id, h_v2s_ptr;
-    ivec h_slot_li;           // [nslots] per listed factor slot: index of its variable within its component, -1 = constant (may be dropped: plan_create)
-    bool have_start = false;
-    // which components go where (rebuilt when an option changes)
-    bool partition_dirty = true;
-    int coop_state_gen = -1;          // generation of the problem's exchange-state buffer this partition points into
-    std::vector<CoopItem> coop;
-    std::vector<CoopLaunch> coop_launches;
-    ivec h_coop_ints;   // host image of coop_ints (kept: the upload is asynchronous)
-    DevBuf coop_ints;
-    std::vector<std::vector<CoopGroup>> h_coop_groups;
-    std::vector<ivec> h_coop_wg;
-    std::vector<StreamItem> stream;
-    ivec h_rest;
-    DevBuf rest_order, xi_glob, queue;
-    int group_blocks4 = 0, group_blocks16 = 0;   // resident blocks of the tiny-component kernels
-    int tiny_max_blocks = 0;                     // option (tests): cap on their grid, 0 = what is resident
-    // options
-    int block_threads = 0;
-    int64_t coop_min_factors = 4096;  // cooperative solver from this many factors ...
-    int coop_max_components = 48;     // ... for at most this many components per plan (packed two or more to a launch); or ...
-    int64_t coop_group_min_factors = 256;  // ... for every component of at least this many factors when all their groups fit the device at once
-    int rest_tiny = 0;                // the first rest_tiny entries of the batch list run on the quad / wave solver
-    int rest_lds = 0;                 // the LAST rest_lds entries run on the LDS-resident solver (solver_lds.hpp)
-    int rest_ptm = 0;                 // the rest_ptm entries before them on the point-major streaming solver (solver_ptm.hpp)
-    int ptm_stream = 1;               // option "ptm_stream": 0 = never, 1 = components too large for the LDS, 2 = every component
-    int ptm_threads = 0;              // option "ptm_threads": its workgroup size, 0 = auto
-    int ptm_ncb_cap = 0, ptm_rot_mode = ROT_PER_FACTOR;
-    int64_t pm_blocks = 0, pm_entries = 0;
-    ivec h_pm_jg;
-    DevBuf pm_rec, pm_gh, pm_cbox, pm_bex, pm_cam, pm_obs;
-    int64_t pm_cptr_len = 0;          // entries of pm_cptr (a component's wave-chunks + 1)
-    // the gradient's round lists (solver_ptm.hpp), built for one workgroup size and group size at a time (ptm_build_rounds)
-    DevBuf pm_rounds, pm_rd_off, pm_rd_n, pm_grow, pm_segs, pm_sg_off;
-    int rounds_threads = 0, rounds_K = 0, rounds_slots = 1;   // (slots a round stages: ptm_round_slots_for)
-    int ptm_round_slots = 0;          // option "ptm_round_slots": 0 = two where the LDS holds their staging rows, 1, 2
-    // ... shared by several workgroups each (cgd_ptmg_kernel) when a launch has fewer components than compute units
-    int ptm_group = 0;                // option "ptm_group": 0 = auto, 1 = never, k = k workgroups per component
-    int ptm_last_group = 1;           // what the last solve used (rdis_hip_plan_debug_counters has no slot for it: get_option)
-    int ptm_last_threads = 0;        // ... and their lanes
-    int64_t ls_total_chunks = 0;      // gradient chunks of all slot tables
-    int64_t ptm_min_points = 0;       // the smallest streaming component's point blocks
-    DevBuf ptm_xch, ptm_state;
-    size_t off_pm_pt0 = 0, off_pm_ch0 = 0, off_pm_cptr = 0, off_pm_jg = 0;
-    int lds_resident = 1;             // option "lds_resident": 0 = never
-    int lds_rot = -1;                 // option "lds_rot": rotation records in that solver, -1 = auto, 0 = per factor, 1 = records
-    int lds_threads = 0;              // option "lds_threads": its workgroup size, 0 = auto
-    int lds_camera_sums = 1;          // option "lds_camera_sums": 0 = camera partials through gfac[] like the plain batch solver
-    int lds_matrix = 0;               // option "lds_matrix": 1 = line-search trials in matrix form where the cameras' trial records fit the LDS too (solver_lds.hpp);
-                                      // measured slower there (a camera's records are a lone lane's chain in front of every trial: 1000 x 2048 factors 16.6 against 10.7 ms)
-    // the dynamic LDS of the LDS-resident launch, and whether its trials run in matrix form (the records must fit behind the other arrays)
-    bool lds_matrix_on(const rdis_hip_ctx* c) const {
-        return lds_matrix != 0 && !emulate_stale && factor_rounding != 1 &&
-               lds_matrix_offset(lds_bytes_for(lds_ns_cap, lds_ncb_cap, lds_chunk_cap)) + lds_matrix_bytes(lds_ncb_cap) <= c->lds_limit;
-    }
-    size_t lds_dyn_bytes(const rdis_hip_ctx* c) const {
-        const size_t base = lds_bytes_for(lds_ns_cap, lds_ncb_cap, lds_chunk_cap);
-        return lds_matrix_on(c) ? lds_matrix_offset(base) + lds_matrix_bytes(lds_ncb_cap) : base;
-    }
-    int emulate_stale = 0;            // option "emulate_stale_cache": the reference's factor cache, emulated (solver_lds.hpp; that solver only)
-    int factor_rounding = -1;         // option "factor_rounding": -1 = auto (the cooperative solvers round like the reference's build -- it costs them 4 % --, the batch
-                                      // solvers use fused multiply-adds), 0 = fused multiply-adds everywhere, 1 = the reference's rounding (and, in the LDS-resident
-                                      // solver, its association of a trial's slope) everywhere: refround_api.hpp
-    bool coop_reference_rounding() const { return factor_rounding != 0; }
-    bool batch_reference_rounding() const { return factor_rounding == 1; }
-    DevBuf st_ev, st_val;
-    bool ptm_wide_wanted = false;     // prepare_partition: a large component joined the batch list for a wide point-major group
-    bool ptm_wide_last = false;       // the last solve ran its point-major launch as wide groups
-    // a wide group with LOCAL camera numbering (solver_ptm.hpp: a component with more cameras than the LDS holds; one such component a plan)
-    int ptm_local_cameras = -1;       // option "ptm_local_cameras": -1 = where the cameras do not fit, 0 = never, 1 = for every wide component (tests)
-    bool ptm_local = false, ptm_local_off = false;   // the plan has such a component; it was tried and did not fit (then never again)
-    int ptm_local_K = 0, ptm_local_comp = -1;
-    PtmLocalTables loc;                              // its host tables (plan_tables.hpp)
-    DevBuf lc_dev, lc_off_dev, cr_ptr_dev, cr_dev, ptm_tot;
-    DevBuf seq_val, seq_ab;           // the parity option's buffers (PlanView::seq_val, seq_ab), allocated at the first solve that needs them
-    int lds_ns_cap = 0, lds_ncb_cap = 0, lds_chunk_cap = 0, lds_rot_mode = ROT_PER_FACTOR;
-    int64_t lds_max_factors = 0;
-    DevBuf lds_ints, lds_obs;
-    ivec h_lds_ints;
-    size_t off_ls_ptr = 0, off_ls_vid = 0, off_ls_free = 0, off_ls_ncb = 0, off_ls_fidx = 0, off_ls_gperm = 0, off_ls_gptr = 0;
-    int tiny_group = 4;               // ... with this many lanes per component (4 or 16)
-    int64_t row_min_components = 4096; // option: sixteen lanes each from this many tiny components (below: a workgroup each)
-    int quad_max_vars = QUAD_MAX_VARS; // option "quad_max_vars": 0 = never use the quad solver
-    int64_t quad_min_components = 16384;  // ... and only for at least this many tiny components
-    int rest_rot_mode = ROT_PER_FACTOR; // how the factors of the batch list get their camera rotations (device_views.hpp)
-    int overlap_batch = 1;            // option: run the batched launch concurrently with cooperative launches
-    int camera_records = 1;           // option "camera_records": 0 = every factor forms its rotation itself, 1 = auto, 2 = records wherever possible
-    size_t off_cb_ptr = 0, off_cb = 0, off_cb_li = 0;
-    int coop_workgroups = 0, coop_threads = 256, coop_poll_delay = 16;
-    int coop_poll_inflight = 0;       // option: the pipelined collector keeps PIPE_POLLS polls of a value+slope slot in flight (solver_pipe.hpp: sweep_ring)
-    int coop_poll_stagger = 2;        // ... one issued every so many x64 cycles (off by default: no setting of the scan beat one poll at a time)
-    int coop_speculate = 1;           // option: guesses at the following trial steps ride along with every line-search trial
-    int coop_pipeline = 1;            // option: cooperative groups with a control wave of their own (solver_pipe.hpp); 0 = solver_coop.hpp
-    bool use_pipe = false;            // decided by prepare_partition: the plan's groups fit the pipelined layout (fewer factor lanes per workgroup)
-    bool pipelined() const { return use_pipe; }
-    int coop_lanes() const { return pipelined() ? PIPE_LANES : coop_threads; }   // factor lanes per workgroup of a cooperative group
-    bool force_stream = false;        // send large components to the streaming grid solver even if they fit the register-resident one
-    int trace_records = 0;
-    int dump_iters = 0;
-    int last_launches = 0;
-    bool timed = false;
-    // multi-start solves (rdis_hip_plan_solve_starts; solver_lds_starts.hpp, solver_wg_starts.hpp): inputs and outputs of every start of
-    // the last call, kept until fetched; the replicas of the per-solve workspace one launch needs, bounded by the option
-    // "starts_workspace_bytes" (ms_work: ws, gfac and, for the plain solver, x; ms_dir: that solver's dir, zero between launches)
-    int64_t starts_workspace_bytes = 1ll << 30;
-    DevBuf ms_in, ms_out, ms_work, ms_dir, ms_best, ms_stage;   // (ms_stage: pinned host memory the caller's starts are uploaded through)
-    hipEvent_t ms_stage_ev = nullptr;
-    bool ms_stage_busy = false;
-    int64_t ms_n = 0;                 // starts of the last multi-start solve (0: none to fetch)
-    bool ms_population = false;       // ... which was a population solve (rdis_hip_plan_solve_population: the members are the starts; no ms_best)
-    int64_t ms_per_launch = 0, ms_launches = 0;
-    int population_plain = 0;         // option "population_plain": 1 = rdis_hip_plan_solve_population takes a nonlinear-product plan on the plain batch solver (solver_wg_population.hpp)
-    int population_tiny = 0;          // option "population_tiny": 1 = ... and a bundle-adjustment plan with components on the tiny-component solver (solver_quad_population.hpp)
-    DevBuf ms_queue;                  // ... whose members of a launch have a queue counter each
-    int tiny_population_fill = 1;     // option "tiny_population_fill" (measurement): the population launch of that solver takes this many times the resident blocks
-    int ms_tiny_blocks = 0;           // ... and this many blocks each in the last such solve (plan_get_info "population_tiny_blocks")
-    int population_point_major = 0;   // option "population_point_major": 1 = ... and one with components on the point-major streaming solver, a workgroup each (solver_ptm_population.hpp)
-    DevBuf ms_ptm;                    // ... whose members of a launch have a replica each of pm_rec, pm_gh, pm_bex and pm_cbox (within "starts_workspace_bytes" too)
-    int ms_ptm_threads = 0;           // ... and the lanes of that kernel in the last population solve, 0 = it had none (plan_get_info "population_point_major_threads")
-    ~rdis_hip_plan() { if (ms_stage_ev) (void)hipEventDestroy(ms_stage_ev); }
-    // the outputs' block for n starts: xout[n][nfree] fret[n][nc] delta[n][nc] (f64) | nfeval[n][nc] ngeval[n][nc] (i64) | iters[n][nc] status[n][nc] (i32)
-    size_t ms_out_bytes(int64_t n) const { return (size_t)n * ((size_t)nfree * 8 + (size_t)ncomp * 40); }
-    StartsView starts_view(int64_t n) const {
-        StartsView s{};
-        const size_t sn = (size_t)n * (size_t)nfree, sc = (size_t)n * (size_t)ncomp;
-        s.xstart = ms_in.as<double>();
-        s.xout = ms_out.as<double>();
-        s.fret = s.xout + sn; s.delta = s.fret + sc;
-        s.nfeval = reinterpret_cast<long long*>(s.delta + sc); s.ngeval = s.nfeval + sc;
-        s.iters = reinterpret_cast<int*>(s.ngeval + sc); s.status = s.iters + sc;
-        s.ws = ms_work.as<double>(); s.gfac = nullptr;   // (gfac, x: behind the launch's replicas of ws -- the solve knows their number)
-        s.x = nullptr; s.dir = nullptr;
-        s.nfree = nfree; s.ngfac = ngfac; s.N = prob->N; s.first = 0;
-        return s;
-    }
-
-    const int* ip(size_t off) const { return ints.as<int>() + off; }
-    double* out_f64(size_t idx) const { return outbuf.as<double>() + idx; }
-    PlanView view() const {
-        PlanView v{};
-        const size_t nc = (size_t)ncomp;
-        v.ncomp = (int)ncomp;
-        v.order = rest_order.as<int>();
-        v.free_ptr = ip(off_free_ptr); v.free_vid = ip(off_free_vid);
-        v.fac_ptr = ip(off_fac_ptr); v.fac_id = ip(off_fac_id);
-        v.v2s_ptr = ip(off_v2s_ptr); v.slot_base = ip(off_slot_base); v.slot_pos = ip(off_slot_pos);
-        v.cb_ptr = ip(off_cb_ptr); v.cb = ip(off_cb); v.cb_li = ip(off_cb_li);
-        const int* li = lds_ints.as<int>();
-        v.ls_ptr = li + off_ls_ptr; v.ls_vid = li + off_ls_vid; v.ls_free = li + off_ls_free; v.ls_ncb = li + off_ls_ncb;
-        v.ls_fidx = reinterpret_cast<const unsigned*>(li + off_ls_fidx);
-        v.ls_obs = lds_obs.as<double2>();
-        v.ls_gperm = li + off_ls_gperm; v.ls_gptr = li + off_ls_gptr;
-        v.ls_cam_gfac = lds_camera_sums ? 0 : 1;
-        v.ls_matrix = lds_matrix_on(prob->ctx) ? 1 : 0;
-        v.st_ev = emulate_stale ? st_ev.as<int>() : nullptr; v.st_val = emulate_stale ? st_val.as<double>() : nullptr;
-        v.pm_pt0 = li + off_pm_pt0; v.pm_ch0 = li + off_pm_ch0; v.pm_cptr = li + off_pm_cptr;
-        v.pm_rec = pm_rec.as<double>(); v.pm_gh = pm_gh.as<double>(); v.pm_cbox = pm_cbox.as<float>(); v.pm_bex = pm_bex.as<double>(); v.pm_cam = pm_cam.as<short>(); v.pm_obs = pm_obs.as<double2>();
-        v.pm_grow = pm_grow.as<unsigned short>(); v.pm_rounds = pm_rounds.as<unsigned short>(); v.pm_rd_off = pm_rd_off.as<long long>(); v.pm_rd_n = pm_rd_n.as<int>(); v.pm_round_slots = rounds_slots;
-        v.pm_segs = pm_segs.as<int>(); v.pm_sg_off = pm_sg_off.as<long long>();
-        v.seq_val = seq_val.as<double>(); v.seq_ab = seq_ab.as<double>(); v.seq_n = (int)nfree;
-        v.timing = prob->coop_timing.as<long long>();
-        v.ws = ws.as<double>(); v.dir = prob->dir.as<double>(); v.gfac = gfac.as<double>();
-        v.xstart = xstart.as<double>();
-        v.xout = out_f64(0);
-        v.fret = out_f64((size_t)nfree); v.delta = out_f64((size_t)nfree + nc);
-        long long* i64 = reinterpret_cast<long long*>(out_f64((size_t)nfree + 2 * nc));
-        v.nfeval = i64; v.ngeval = i64 + nc;
-        int* i32 = reinterpret_cast<int*>(i64 + 2 * nc);
-        v.iters = i32; v.status = i32 + nc; v.trace_n = i32 + 2 * nc;
-        v.trace = trace_records > 0 ? trace.as<double>() : nullptr;
-        v.trace_cap = trace_records;
-        v.vdump = dump_iters > 0 ? vdump.as<double>() : nullptr;
-        v.dump_iters = dump_iters;
-        return v;
-    }
-};
 
 
 // =====================================================================================
@@ -663,7 +274,6 @@ int stage_ids(rdis_hip_problem* p, int64_t n, const int64_t* ids, int64_t limit,
     *dev = p->tmp_idx.as<int>();
     return 0;
 }
-int ensure(rdis_hip_ctx* c, DevBuf& b, size_t bytes) { return b.bytes >= bytes ? 0 : dalloc(c, b, bytes); }
 }  // namespace
 
 extern "C" int rdis_hip_set_x(rdis_hip_problem* p, int64_t n, const int64_t* vid, const double* val) {
@@ -1240,10 +850,6 @@ extern "C" int rdis_hip_grad_each_ba(rdis_hip_problem* p, int64_t nf, const int6
 // =====================================================================================
 // plans
 // =====================================================================================
-
-// =====================================================================================
-// plans
-// =====================================================================================
 namespace {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -1553,139 +1159,34 @@ extern "C" int rdis_hip_plan_set_option(rdis_hip_plan* L, const char* name, int6
     if (!L || !name) return RDIS_HIP_EINVAL;
     rdis_hip_ctx* c = L->prob->ctx;
     USE_DEVICE(c);
-    const std::string n(name);
-    if (n == "block_threads") {
-        if (value != 0 && value != 64 && value != 128 && value != 256 && value != 512 && value != 768 && value != 1024)
-            return fail(c, RDIS_HIP_EINVAL, "block_threads must be 0, 64, 128, 256, 512, 768 or 1024");
-        L->block_threads = (int)value;
-    } else if (n == "coop_min_factors") {
-        if (value < 0) return fail(c, RDIS_HIP_EINVAL, "coop_min_factors < 0");
-        L->coop_min_factors = value;
-    } else if (n == "quad_min_components") {
-        if (value < 0) return fail(c, RDIS_HIP_EINVAL, "quad_min_components < 0");
-        L->quad_min_components = value;
-    } else if (n == "coop_group_min_factors") {
-        if (value < 0) return fail(c, RDIS_HIP_EINVAL, "coop_group_min_factors < 0");
-        L->coop_group_min_factors = value;
-    } else if (n == "tiny_max_blocks") {
-        if (value < 0 || value > (1 << 20)) return fail(c, RDIS_HIP_EINVAL, "tiny_max_blocks out of range");
-        L->tiny_max_blocks = (int)value;
-    } else if (n == "overlap_batch") {
-        L->overlap_batch = value != 0;
-    } else if (n == "row_min_components") {
-        if (value < 0) return fail(c, RDIS_HIP_EINVAL, "row_min_components < 0");
-        L->row_min_components = value;
-    } else if (n == "camera_records") {
-        if (value < 0 || value > 2) return fail(c, RDIS_HIP_EINVAL, "camera_records must be 0, 1 or 2");
-        L->camera_records = (int)value;
-    } else if (n == "quad_max_vars") {
-        if (value < 0 || value > QUAD_MAX_VARS) return fail(c, RDIS_HIP_EINVAL, "quad_max_vars out of range");
-        L->quad_max_vars = (int)value;
-    } else if (n == "coop_max_components") {
-        if (value < 0 || value > 4096) return fail(c, RDIS_HIP_EINVAL, "coop_max_components out of range");
-        L->coop_max_components = (int)value;
-    } else if (n == "coop_workgroups") {
-        if (value < 0 || value > COOP_MAX_WG) return fail(c, RDIS_HIP_EINVAL, "coop_workgroups out of range");
-        L->coop_workgroups = (int)value;
-    } else if (n == "coop_threads") {
-        if (value != 128 && value != 256 && value != 512) return fail(c, RDIS_HIP_EINVAL, "coop_threads must be 128, 256 or 512");
-        L->coop_threads = (int)value;
-    } else if (n == "coop_speculate") {
-        L->coop_speculate = value != 0;
-    } else if (n == "coop_pipeline") {
-        L->coop_pipeline = value != 0;
-    } else if (n == "lds_resident") {
-        L->lds_resident = value != 0;
-    } else if (n == "ptm_stream") {
-        if (value < 0 || value > 2) return fail(c, RDIS_HIP_EINVAL, "ptm_stream must be 0 (never), 1 (components too large for the LDS) or 2 (every component its tables fit)");
-        L->ptm_stream = (int)value;
-    } else if (n == "ptm_group") {
-        if (value < 0 || value > PTM_WIDE_MAX_GROUP) return fail(c, RDIS_HIP_EINVAL, "ptm_group must be 0 (auto), 1 (never) or the number of workgroups per component (at most 16; up to 512 for the wide groups of a few large components)");
-        L->ptm_group = (int)value;
-        return 0;   // (no table depends on it)
-    } else if (n == "ptm_round_slots") {
-        if (value < 0 || value > 2) return fail(c, RDIS_HIP_EINVAL, "ptm_round_slots must be 0 (two where the LDS holds them), 1 or 2");
-        L->ptm_round_slots = (int)value;
-        L->rounds_threads = L->rounds_K = 0;   // (the round tables are built for one choice)
-        return 0;
-    } else if (n == "ptm_threads") {
-        if (value != 0 && value != 256 && value != 512 && value != 768) return fail(c, RDIS_HIP_EINVAL, "ptm_threads must be 0, 256, 512 or 768");
-        L->ptm_threads = (int)value;
-    } else if (n == "ptm_local_cameras") {
-        if (value < -1 || value > 1) return fail(c, RDIS_HIP_EINVAL, "ptm_local_cameras must be -1 (where a wide group's cameras do not fit the LDS), 0 (never) or 1 (every wide group)");
-        L->ptm_local_cameras = (int)value;
-        L->ptm_local_off = false;
-    } else if (n == "emulate_stale_cache") {
-        L->emulate_stale = value != 0;
-    } else if (n == "factor_rounding") {
-        if (value < -1 || value > 1) return fail(c, RDIS_HIP_EINVAL, "factor_rounding must be -1 (auto), 0 (fused multiply-adds) or 1 (the reference's rounding)");
-        L->factor_rounding = (int)value;
-    } else if (n == "lds_camera_sums") {
-        L->lds_camera_sums = value != 0;
-    } else if (n == "lds_matrix") {
-        L->lds_matrix = value != 0;
-        return 0;   // (no table depends on it)
-    } else if (n == "lds_rot") {
-        if (value < -1 || value > 1) return fail(c, RDIS_HIP_EINVAL, "lds_rot must be -1, 0 or 1");
-        L->lds_rot = (int)value;
-    } else if (n == "lds_threads") {
-        if (value != 0 && value != 64 && value != 128 && value != 256 && value != 512 && value != 768 && value != 1024)
-            return fail(c, RDIS_HIP_EINVAL, "lds_threads must be 0, 64, 128, 256, 512, 768 or 1024");
-        L->lds_threads = (int)value;
-    } else if (n == "force_stream") {
-        L->force_stream = value != 0;
-    } else if (n == "coop_poll_delay") {
-        if (value < 0 || value > 1024) return fail(c, RDIS_HIP_EINVAL, "coop_poll_delay out of range");
-        L->coop_poll_delay = (int)value;
-    } else if (n == "coop_poll_inflight") {
-        if (value < 0 || value > 1) return fail(c, RDIS_HIP_EINVAL, "coop_poll_inflight must be 0 (one poll at a time) or 1 (a ring of polls in flight)");
-        L->coop_poll_inflight = (int)value;
-    } else if (n == "coop_poll_stagger") {
-        if (value < 0 || value > 64) return fail(c, RDIS_HIP_EINVAL, "coop_poll_stagger out of range (0 ... 64)");
-        L->coop_poll_stagger = (int)value;
-    } else if (n == "starts_workspace_bytes") {
-        if (value < 0) return fail(c, RDIS_HIP_EINVAL, "starts_workspace_bytes < 0");
-        L->starts_workspace_bytes = value;
-        // (the bound holds from now on: replicas beyond it go; releasing device memory waits for the work that uses it)
-        if (L->ms_work.bytes + L->ms_ptm.bytes > (size_t)value) {
-            for (DevBuf* b : {&L->ms_work, &L->ms_ptm})
-                if (b->p) { L->dev_bytes -= std::min(L->dev_bytes, b->bytes); b->release(); }
-        }
-        return 0;   // (no table depends on it)
-    } else if (n == "population_point_major") {
-        L->population_point_major = value != 0;
-        return 0;   // (no table depends on it)
-    } else if (n == "population_plain") {
-        L->population_plain = value != 0;
-        return 0;   // (no table depends on it)
-    } else if (n == "population_tiny") {
-        L->population_tiny = value != 0;
-        return 0;   // (no table depends on it)
-    } else if (n == "tiny_population_fill") {
-        if (value < 1 || value > 64) return fail(c, RDIS_HIP_EINVAL, "tiny_population_fill out of range (1 ... 64)");
-        L->tiny_population_fill = (int)value;
-        return 0;   // (no table depends on it)
-    } else if (n == "trace_records") {
-        if (value < 0 || value > (1 << 22)) return fail(c, RDIS_HIP_EINVAL, "trace_records out of range");
-        if (L->transient && value) return fail(c, RDIS_HIP_EINVAL, "tracing needs a persistent plan");
-        L->trace_records = (int)value;
-        if (value > 0) {
-            int rc = dalloc(c, L->trace, (size_t)L->ncomp * (size_t)value * 4 * sizeof(double));
-            if (rc) return rc;
-        }
-    } else if (n == "dump_iters") {
-        if (value < 0 || value > 4096 || (double)value * 2.0 * (double)L->nfree > 4e9) return fail(c, RDIS_HIP_EINVAL, "dump_iters out of range");
-        if (L->transient && value) return fail(c, RDIS_HIP_EINVAL, "vector dumps need a persistent plan");
-        L->dump_iters = (int)value;
-        if (value > 0) {
-            int rc = dalloc(c, L->vdump, (size_t)value * 2 * (size_t)L->nfree * sizeof(double));
-            if (rc) return rc;
-            HIPCHK(c, hipMemsetAsync(L->vdump.p, 0, L->vdump.bytes, c->stream));
-        }
-    } else {
-        return fail(c, RDIS_HIP_EINVAL, "unknown option " + n);
+    // Every option's rule, message and effects: plan_options.hpp.  The value goes into a copy of the options first, so that
+    // what only the plan can refuse is refused before anything is written.
+    PlanOptions next = *L;
+    std::string message;
+    const PlanOptionRow* row = nullptr;
+    const int effect = plan_option_set(next, name, value, &message, &row);
+    if (effect < 0) return fail(c, RDIS_HIP_EINVAL, message);
+    if ((effect & PLAN_OPTION_DUMP) && (double)value * 2.0 * (double)L->nfree > 4e9) return fail(c, RDIS_HIP_EINVAL, row->refusal);
+    if ((effect & PLAN_OPTION_TRACE) && L->transient && value) return fail(c, RDIS_HIP_EINVAL, "tracing needs a persistent plan");
+    if ((effect & PLAN_OPTION_DUMP) && L->transient && value) return fail(c, RDIS_HIP_EINVAL, "vector dumps need a persistent plan");
+    static_cast<PlanOptions&>(*L) = next;   // the commit: every refusal is above this line, nothing of the plan is written above it
+    if (effect & PLAN_OPTION_ROUNDS) L->rounds_threads = L->rounds_K = 0;   // (the round tables are built for one choice)
+    if (effect & PLAN_OPTION_LOCAL) L->ptm_local_off = false;
+    // (the bound holds from now on: replicas beyond it go; releasing device memory waits for the work that uses it)
+    if ((effect & PLAN_OPTION_WORKSPACE) && L->ms_work.bytes + L->ms_ptm.bytes > (size_t)value) {
+        for (DevBuf* b : {&L->ms_work, &L->ms_ptm})
+            if (b->p) { L->dev_bytes -= std::min(L->dev_bytes, b->bytes); b->release(); }
     }
-    L->partition_dirty = true;
+    if ((effect & PLAN_OPTION_TRACE) && value > 0) {
+        int rc = dalloc(c, L->trace, (size_t)L->ncomp * (size_t)value * 4 * sizeof(double));
+        if (rc) return rc;
+    }
+    if ((effect & PLAN_OPTION_DUMP) && value > 0) {
+        int rc = dalloc(c, L->vdump, (size_t)value * 2 * (size_t)L->nfree * sizeof(double));
+        if (rc) return rc;
+        HIPCHK(c, hipMemsetAsync(L->vdump.p, 0, L->vdump.bytes, c->stream));
+    }
+    if (effect & PLAN_OPTION_DIRTY) L->partition_dirty = true;
     return 0;
 }
 
@@ -2202,8 +1703,10 @@ int pack_coop_launches(rdis_hip_plan* L, int cap) {
     return 0;
 }
 
-// decide which solver takes each component and build what it needs
-int prepare_partition(rdis_hip_plan* L) {
+}  // namespace
+
+// decide which solver takes each component and build what it needs (plan_query.hip calls it too)
+int rdis_hip::prepare_partition(rdis_hip_plan* L) {
     rdis_hip_ctx* c = L->prob->ctx;
     Partition S;
     for (;;) {
@@ -2231,6 +1734,9 @@ int prepare_partition(rdis_hip_plan* L) {
     L->coop_state_gen = L->prob->coop_state_gen;
     return 0;
 }
+
+// ---- the launches of a solve, and their shapes ----
+namespace {
 
 template <int KIND>
 int launch_wg(rdis_hip_plan* L, hipStream_t stream, int threads, int first, int grid, int maxiters, double ftol) {
@@ -3354,232 +2860,6 @@ extern "C" int rdis_hip_plan_fetch_population(rdis_hip_plan* L, double* x_out, d
     return fetch_many(L, true, x_out, fret, delta, iters, status, nfeval, ngeval, nullptr);
 }
 
-extern "C" int rdis_hip_plan_objective_device(rdis_hip_plan* L, void** dev_ptr) {
-    if (!L || !dev_ptr) return RDIS_HIP_EINVAL;
-    *dev_ptr = L->objective.p;
-    return 0;
-}
-
-// =====================================================================================
-// the path's one collective: the all-reduce of the top-level objective (reference src/RDISOptimizer.cpp:1491-1494 adds the
-// components' values on one host; here the components of a level are sharded over GPUs and the partial sums meet over xGMI)
-// =====================================================================================
-// RCCL is loaded at the first communicator (dlopen): a single-GPU user never maps it.
-#include <dlfcn.h>
-#include <rccl/rccl.h>
-
-struct rdis_hip_comm {
-    rdis_hip_ctx* ctx = nullptr;
-    ncclComm_t comm = nullptr;
-    int world = 1, rank = 0;
-    DevBuf scratch;            // small host-buffer reductions (rdis_hip_comm_allreduce_f64)
-};
-
-namespace {
-struct RcclApi {
-    void* h = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*CommInitAll)(ncclComm_t*, int, const int*) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*GroupStart)() = nullptr;
-    ncclResult_t (*GroupEnd)() = nullptr;
-    const char* (*GetErrorString)(ncclResult_t) = nullptr;
-    bool ok = false;
-};
-RcclApi& rccl() {
-    static RcclApi A = [] {
-        RcclApi a;
-        for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-            a.h = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-            if (a.h) break;
-        }
-        if (!a.h) return a;
-#define RDIS_RCCL_SYM(field, sym) a.field = reinterpret_cast<decltype(a.field)>(dlsym(a.h, sym))
-        RDIS_RCCL_SYM(GetUniqueId, "ncclGetUniqueId"); RDIS_RCCL_SYM(CommInitRank, "ncclCommInitRank"); RDIS_RCCL_SYM(CommInitAll, "ncclCommInitAll");
-        RDIS_RCCL_SYM(CommDestroy, "ncclCommDestroy"); RDIS_RCCL_SYM(AllReduce, "ncclAllReduce"); RDIS_RCCL_SYM(GroupStart, "ncclGroupStart");
-        RDIS_RCCL_SYM(GroupEnd, "ncclGroupEnd"); RDIS_RCCL_SYM(GetErrorString, "ncclGetErrorString");
-#undef RDIS_RCCL_SYM
-        a.ok = a.GetUniqueId && a.CommInitRank && a.CommInitAll && a.CommDestroy && a.AllReduce && a.GroupStart && a.GroupEnd;
-        return a;
-    }();
-    return A;
-}
-int rccl_fail(rdis_hip_ctx* c, ncclResult_t r, const char* what) {
-    const char* msg = rccl().GetErrorString ? rccl().GetErrorString(r) : "?";
-    if (c) return fail(c, RDIS_HIP_EDEVICE, std::string(what) + ": RCCL: " + msg);
-    return RDIS_HIP_EDEVICE;
-}
-}  // namespace
-
-extern "C" int rdis_hip_comm_unique_id(void* id128) {
-    if (!id128) return RDIS_HIP_EINVAL;
-    static_assert(sizeof(ncclUniqueId) == RDIS_HIP_COMM_ID_BYTES, "RCCL's unique id is 128 bytes");
-    if (!rccl().ok) return RDIS_HIP_EDEVICE;
-    ncclUniqueId id;
-    if (rccl().GetUniqueId(&id) != ncclSuccess) return RDIS_HIP_EDEVICE;
-    std::memcpy(id128, &id, sizeof id);
-    return 0;
-}
-
-extern "C" int rdis_hip_comm_create(rdis_hip_ctx* c, int32_t world, int32_t rank, const void* id128, rdis_hip_comm** out) {
-    if (!c || !out || world < 1 || rank < 0 || rank >= world || !id128) return RDIS_HIP_EINVAL;
-    if (!rccl().ok) return fail(c, RDIS_HIP_EDEVICE, "comm_create: librccl.so could not be loaded");
-    USE_DEVICE(c);
-    std::unique_ptr<rdis_hip_comm> m(new (std::nothrow) rdis_hip_comm);
-    if (!m) return fail(c, RDIS_HIP_ENOMEM, "comm_create: host allocation");
-    ncclUniqueId id;
-    std::memcpy(&id, id128, sizeof id);
-    const ncclResult_t r = rccl().CommInitRank(&m->comm, world, id, rank);
-    if (r != ncclSuccess) return rccl_fail(c, r, "comm_create");
-    m->ctx = c; m->world = world; m->rank = rank;
-    *out = m.release();
-    return 0;
-}
-
-extern "C" int rdis_hip_comm_create_all(int32_t n, rdis_hip_ctx* const* ctxs, rdis_hip_comm** comms) {
-    if (n < 1 || !ctxs || !comms) return RDIS_HIP_EINVAL;
-    for (int i = 0; i < n; ++i) if (!ctxs[i]) return RDIS_HIP_EINVAL;
-    rdis_hip_ctx* c0 = ctxs[0];
-    if (!rccl().ok) return fail(c0, RDIS_HIP_EDEVICE, "comm_create_all: librccl.so could not be loaded");
-    std::vector<int> devs((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        devs[(size_t)i] = ctxs[i]->phys;
-        for (int j = 0; j < i; ++j)
-            if (devs[(size_t)j] == devs[(size_t)i]) return fail(c0, RDIS_HIP_EINVAL, "comm_create_all: a device is listed twice (one rank per GPU)");
-    }
-    std::vector<ncclComm_t> cc((size_t)n, nullptr);
-    const ncclResult_t r = rccl().CommInitAll(cc.data(), n, devs.data());
-    if (r != ncclSuccess) return rccl_fail(c0, r, "comm_create_all");
-    for (int i = 0; i < n; ++i) {
-        rdis_hip_comm* m = new (std::nothrow) rdis_hip_comm;
-        if (!m) { for (int j = 0; j < i; ++j) { delete comms[j]; comms[j] = nullptr; } for (ncclComm_t q : cc) rccl().CommDestroy(q); return fail(c0, RDIS_HIP_ENOMEM, "comm_create_all: host allocation"); }
-        m->ctx = ctxs[i]; m->comm = cc[(size_t)i]; m->world = n; m->rank = i;
-        comms[i] = m;
-    }
-    return 0;
-}
-
-extern "C" void rdis_hip_comm_destroy(rdis_hip_comm* m) {
-    if (!m) return;
-    if (m->ctx) { (void)make_current(m->ctx); (void)hipStreamSynchronize(m->ctx->stream); }
-    if (m->comm && rccl().ok) rccl().CommDestroy(m->comm);
-    if (m->scratch.p) (void)hipFree(m->scratch.p);
-    m->scratch.p = nullptr;
-    delete m;
-}
-
-extern "C" int rdis_hip_allreduce_objective(rdis_hip_plan* L, rdis_hip_comm* m, double* sum_out) {
-    if (!L) return RDIS_HIP_EINVAL;
-    rdis_hip_ctx* c = L->prob->ctx;
-    USE_DEVICE(c);
-    if (m) {
-        if (m->ctx != c) return fail(c, RDIS_HIP_EINVAL, "allreduce_objective: the communicator belongs to another context");
-        // in place, on the stream the solve ran on: ordered behind objective_sum_kernel, ahead of whatever reads the sum
-        const ncclResult_t r = rccl().AllReduce(L->objective.p, L->objective.p, 1, ncclDouble, ncclSum, m->comm, c->stream);
-        if (r != ncclSuccess) return rccl_fail(c, r, "allreduce_objective");
-    }
-    if (sum_out) {
-        HIPCHK(c, hipMemcpyAsync(sum_out, L->objective.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return 0;
-}
-
-extern "C" int rdis_hip_allreduce_objective_all(int32_t n, rdis_hip_plan* const* plans, rdis_hip_comm* const* comms, double* sum_out) {
-    if (n < 1 || !plans) return RDIS_HIP_EINVAL;
-    for (int i = 0; i < n; ++i) if (!plans[i]) return RDIS_HIP_EINVAL;
-    rdis_hip_ctx* c0 = plans[0]->prob->ctx;
-    if (comms) {
-        if (!rccl().ok) return fail(c0, RDIS_HIP_EDEVICE, "allreduce_objective_all: librccl.so could not be loaded");
-        for (int i = 0; i < n; ++i) if (!comms[i] || comms[i]->ctx != plans[i]->prob->ctx) return fail(c0, RDIS_HIP_EINVAL, "allreduce_objective_all: communicator i must belong to plan i's context");
-        // one thread drives all the ranks: the calls are grouped, or the first would wait for the others
-        ncclResult_t r = rccl().GroupStart();
-        for (int i = 0; i < n && r == ncclSuccess; ++i) {
-            rdis_hip_ctx* c = plans[i]->prob->ctx;
-            USE_DEVICE(c);
-            r = rccl().AllReduce(plans[i]->objective.p, plans[i]->objective.p, 1, ncclDouble, ncclSum, comms[i]->comm, c->stream);
-        }
-        const ncclResult_t e = rccl().GroupEnd();
-        if (r != ncclSuccess || e != ncclSuccess) return rccl_fail(c0, r != ncclSuccess ? r : e, "allreduce_objective_all");
-        if (sum_out) {
-            USE_DEVICE(c0);
-            HIPCHK(c0, hipMemcpyAsync(sum_out, plans[0]->objective.p, sizeof(double), hipMemcpyDeviceToHost, c0->stream));
-            HIPCHK(c0, hipStreamSynchronize(c0->stream));
-        }
-        return 0;
-    }
-    // no communicators (the same device listed twice, or no RCCL): the partial sums meet on the host, in plan order
-    if (sum_out) {
-        double acc = 0.0;
-        for (int i = 0; i < n; ++i) {
-            rdis_hip_ctx* c = plans[i]->prob->ctx;
-            double v = 0.0;
-            USE_DEVICE(c);
-            HIPCHK(c, hipMemcpyAsync(&v, plans[i]->objective.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            acc += v;
-        }
-        *sum_out = acc;
-    }
-    return 0;
-}
-
-extern "C" int rdis_hip_comm_allreduce_f64(rdis_hip_comm* m, double* inout, int32_t n, int32_t op) {
-    if (!m || !inout || n < 1 || n > 4096 || (op != 0 && op != 1)) return RDIS_HIP_EINVAL;
-    rdis_hip_ctx* c = m->ctx;
-    USE_DEVICE(c);
-    if (m->scratch.bytes < (size_t)n * sizeof(double)) { if (int rc = dalloc(c, m->scratch, 4096 * sizeof(double))) return rc; }
-    HIPCHK(c, hipMemcpyAsync(m->scratch.p, inout, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const ncclResult_t r = rccl().AllReduce(m->scratch.p, m->scratch.p, (size_t)n, ncclDouble, op == 0 ? ncclSum : ncclMax, m->comm, c->stream);
-    if (r != ncclSuccess) return rccl_fail(c, r, "comm_allreduce_f64");
-    HIPCHK(c, hipMemcpyAsync(inout, m->scratch.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-extern "C" int rdis_hip_plan_get_info(rdis_hip_plan* L, const char* name, int64_t* value) {
-    if (!L || !name || !value) return RDIS_HIP_EINVAL;
-    rdis_hip_ctx* c = L->prob->ctx;
-    USE_DEVICE(c);
-    if (L->partition_dirty) { int rc = prepare_partition(L); if (rc) return rc; }
-    const std::string n(name);
-    const int64_t rest = (int64_t)L->h_rest.size() - L->rest_tiny - L->rest_lds - L->rest_ptm;
-    if (n == "components_cooperative") *value = (int64_t)L->coop.size();
-    else if (n == "components_grid_stream") *value = (int64_t)L->stream.size();
-    else if (n == "grid_stream_workgroups") *value = L->stream.empty() ? 0 : L->stream.front().nwg;   // (of the first such component)
-    else if (n == "components_tiny") *value = L->rest_tiny;
-    else if (n == "components_lds") *value = L->rest_lds;
-    else if (n == "components_point_major") *value = L->rest_ptm;
-    else if (n == "point_major_wide") *value = L->ptm_wide_last ? 1 : 0;
-    else if (n == "point_major_local_cameras") *value = (L->ptm_wide_last && L->ptm_local) ? L->ptm_ncb_cap : 0;
-    else if (n == "components_plain") *value = rest;
-    else if (n == "pipelined") *value = L->pipelined() ? 1 : 0;
-    else if (n == "coop_poll_delay") *value = L->coop_poll_delay;
-    else if (n == "coop_poll_inflight") *value = L->coop_poll_inflight;
-    else if (n == "coop_poll_stagger") *value = L->coop_poll_stagger;
-    else if (n == "point_major_group") *value = L->ptm_last_group;
-    else if (n == "point_major_threads") *value = L->ptm_last_threads;
-    else if (n == "point_major_round_slots") *value = L->rounds_slots;
-    else if (n == "starts_per_launch") *value = L->ms_per_launch;
-    else if (n == "starts_launches") *value = L->ms_launches;
-    else if (n == "population_tiny_blocks") *value = L->ms_tiny_blocks;
-    else if (n == "population_point_major_threads") *value = L->ms_ptm_threads;
-    else return fail(c, RDIS_HIP_EINVAL, "plan_get_info: unknown name '" + n + "'");
-    return 0;
-}
-
-extern "C" int rdis_hip_plan_device_bytes(rdis_hip_plan* L, int64_t* bytes) {
-    if (!L || !bytes) return RDIS_HIP_EINVAL;
-    USE_DEVICE(L->prob->ctx);
-    // (the solvers' tables are built on demand: counted once they exist -- built here if they do not yet; what a first
-    // solve adds for its launch shape, e.g. the streaming solver's round tables, shows in a query after that solve)
-    if (L->partition_dirty && !L->transient) { int rc = prepare_partition(L); if (rc) return rc; }
-    *bytes = (int64_t)(L->dev_bytes + L->trace.bytes + L->vdump.bytes);
-    return 0;
-}
-
 extern "C" int rdis_hip_plan_last_kernel_ms(rdis_hip_plan* L, double* ms, int32_t* launches) {
     if (!L || !ms) return RDIS_HIP_EINVAL;
     rdis_hip_problem* p = L->prob;
@@ -3592,23 +2872,6 @@ extern "C" int rdis_hip_plan_last_kernel_ms(rdis_hip_plan* L, double* ms, int32_
     float t = 0.f;
     HIPCHK(c, hipEventElapsedTime(&t, p->ev0, p->ev1));
     *ms = t;
-    return 0;
-}
-
-extern "C" int rdis_hip_plan_get_trace(rdis_hip_plan* L, int64_t comp, double* rec4, int64_t cap, int64_t* nrec) {
-    if (!L || !nrec || comp < 0 || comp >= L->ncomp) return RDIS_HIP_EINVAL;
-    rdis_hip_ctx* c = L->prob->ctx;
-    USE_DEVICE(c);
-    if (L->trace_records <= 0) { *nrec = 0; return 0; }
-    int n = 0;
-    HIPCHK(c, hipMemcpyAsync(&n, L->view().trace_n + comp, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *nrec = n;
-    const int64_t k = std::min<int64_t>(std::min<int64_t>(n, L->trace_records), cap);
-    if (rec4 && k > 0) {
-        HIPCHK(c, hipMemcpyAsync(rec4, L->trace.as<double>() + 4ll * L->trace_records * comp, (size_t)k * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
     return 0;
 }
 
@@ -3685,30 +2948,6 @@ extern "C" int rdis_hip_components_fetch(rdis_hip_problem* p, int64_t* free_ptr,
     if (fac_ptr) std::memcpy(fac_ptr, L.fac_ptr.data(), L.fac_ptr.size() * sizeof(int64_t));
     if (free_vid && !L.free_vid.empty()) std::memcpy(free_vid, L.free_vid.data(), L.free_vid.size() * sizeof(int64_t));
     if (fac_id && !L.fac_id.empty()) std::memcpy(fac_id, L.fac_id.data(), L.fac_id.size() * sizeof(int64_t));
-    return 0;
-}
-
-extern "C" int rdis_hip_plan_debug_counters(rdis_hip_plan* L, int64_t* out48) {
-    if (!L || !out48) return RDIS_HIP_EINVAL;
-    rdis_hip_ctx* c = L->prob->ctx;
-    USE_DEVICE(c);
-    HIPCHK(c, hipMemcpyAsync(out48, L->prob->coop_timing.p, PIPE_TM * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-extern "C" int rdis_hip_plan_get_vectors(rdis_hip_plan* L, int64_t comp, double* out, int64_t cap_doubles) {
-    if (!L || !out || comp < 0 || comp >= L->ncomp) return RDIS_HIP_EINVAL;
-    rdis_hip_ctx* c = L->prob->ctx;
-    USE_DEVICE(c);
-    if (L->dump_iters <= 0) return fail(c, RDIS_HIP_EINVAL, "get_vectors: dump_iters is 0");
-    const int64_t n = L->h_free_ptr[(size_t)comp + 1] - L->h_free_ptr[(size_t)comp];
-    const int64_t want = 2ll * L->dump_iters * n;
-    if (cap_doubles < want) return fail(c, RDIS_HIP_EINVAL, "get_vectors: buffer too small");
-    if (want == 0) return 0;
-    HIPCHK(c, hipMemcpyAsync(out, L->vdump.as<double>() + 2ll * L->dump_iters * L->h_free_ptr[(size_t)comp],
-                             (size_t)want * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 

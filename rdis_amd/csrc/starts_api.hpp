@@ -1,4 +1,4 @@
-// starts_api.hpp -- what rdis_hip.hip sees of the multi-start entries of the LDS-resident solver (solver_lds_starts.hpp) and of
+// starts_api.hpp -- what the C ABI's translation units (through abi_state.hpp: StartsView; rdis_hip.hip: the launches) see of the multi-start entries of the LDS-resident solver (solver_lds_starts.hpp) and of
 // the plain one-workgroup solver (solver_wg_starts.hpp), whose kernels are a translation unit of their own (starts_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>

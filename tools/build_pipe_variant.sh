@@ -3,8 +3,9 @@
 #   tools/build_pipe_variant.sh NAME [compiler flags ...]   ->  build_ab/librdis_hip_NAME.so
 # e.g.  tools/build_pipe_variant.sh polls4 -DRDIS_PIPE_POLLS=4
 #       tools/build_pipe_variant.sh timing -DRDIS_COOP_TIMING
-# Only the two sources that include solver_pipe.hpp are compiled again; the other objects are those of the
-# regular build (make -C rdis_amd/csrc first).  Probes pick a variant up through RDIS_PROBE_LIB.
+# Only the two sources that include solver_pipe.hpp are compiled again; the other objects -- the kernels' translation
+# units and the ABI's host-only ones (comm, plan_query) -- are those of the regular build
+# (make -C rdis_amd/csrc first).  Probes pick a variant up through RDIS_PROBE_LIB.
 set -euo pipefail
 root="$(cd "$(dirname "$0")/.." && pwd)"
 name="$1"; shift
