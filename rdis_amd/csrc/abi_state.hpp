@@ -18,6 +18,7 @@
 #include "host_blocks.hpp"
 #include "plan_tables.hpp"
 #include "plan_options.hpp"
+#include "plan_index.hpp"
 #include "components.hpp"
 #include "lm_solver.hpp"
 #include "grad_fused.hpp"
@@ -138,8 +139,6 @@ inline int grid_for(const rdis_hip_ctx* c, long long work, int threads) {
 
 }  // namespace rdis_hip
 
-struct VarMark { int stamp, owner, gidx, pad; };
-
 // the fused gradient pass's tables for one factor list (grad_fused.hpp), kept by the problem
 struct GradPlan {
     unsigned long long key0 = 0, key1 = 0, used = 0;   // two hashes of the id list (0, 0: all factors); last use
@@ -233,26 +232,20 @@ struct StreamItem {
     DevBuf long_vars;  // local indices of the variables fed by many partials
 };
 
-// The options (plan_options.hpp: what rdis_hip_plan_set_option writes) are the base; below them what plan_create lays out,
-// what prepare_partition decides, the device buffers, and what the last solve and the last many-solve call left.
-struct rdis_hip_plan : PlanOptions {
+// The options (plan_options.hpp: what rdis_hip_plan_set_option writes) and the index plan_create lays out (plan_index.hpp: the
+// host lists, the int32 block `ints` with its offsets) are the bases; below them what prepare_partition decides, the device
+// buffers, and what the last solve and the last many-solve call left.
+struct rdis_hip_plan : PlanOptions, PlanIndex {
     rdis_hip_problem* prob = nullptr;
     bool transient = false;  // lives in the problem's arena (rdis_hip_cgd_batch): one at a time
     size_t dev_bytes = 0;    // device memory of its own (plan_alloc; rdis_hip_plan_device_bytes)
 
     // ---- the lists (plan_create) ----
-    int64_t ncomp = 0, nfree = 0, nfac = 0, nslots = 0, ngfac = 0;
-    // one device block of int32, `ints` (order | free_ptr | free_vid | fac_ptr | fac_id | v2s_ptr | slot_base | slot_pos |
-    // cb_ptr | cb | cb_li), and one of results, `outbuf`
-    size_t off_order = 0, off_free_ptr = 0, off_free_vid = 0, off_fac_ptr = 0, off_fac_id = 0, off_v2s_ptr = 0,
-           off_slot_base = 0, off_slot_pos = 0;
-    size_t off_cb_ptr = 0, off_cb = 0, off_cb_li = 0;
+    int64_t ncomp = 0, nfree = 0, nfac = 0;
+    // one device block of int32, `ints` (PlanIndex), and one of results, `outbuf`
     // results block: xout[nfree] fret[nc] delta[nc] (f64) | nfeval[nc] ngeval[nc] (i64) | iters[nc] status[nc] trace_n[nc] (i32)
     size_t out_bytes = 0;
     cvec h_out;
-    ivec h_blk;   // host image of `ints` (kept alive: its upload is asynchronous)
-    ivec h_order, h_fac_ptr, h_free_ptr, h_free_vid, h_fac_id, h_v2s_ptr;
-    ivec h_slot_li;           // [nslots] per listed factor slot: index of its variable within its component, -1 = constant (may be dropped: plan_create)
     bool have_start = false;
 
     // ---- what prepare_partition decides: which components go where (rebuilt when an option changes) ----

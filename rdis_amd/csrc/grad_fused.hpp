@@ -39,7 +39,7 @@ constexpr int GRAD_REC = 14;           // doubles of a camera's record: [v0 v1 v
 constexpr int GRAD_MAX_TILE_CHUNKS = 8;
 constexpr unsigned short GRAD_NO_ENTRY = 0xFFFF;
 
-// a factor list's tables on the device (all built on the host once per list, rdis_hip.hip: build_grad_plan)
+// a factor list's tables on the device (all built on the host once per list: grad_tables.hpp, uploaded by rdis_hip.hip's build_grad_plan)
 struct GradTables {
     int nf, nchunks, ntiles, ncam_cap;        // list entries; chunks of GRAD_LANES; tiles; the largest number of distinct cameras in a tile
     const int* fac;                           // [nf] factor ids, or null = 0 .. nf-1

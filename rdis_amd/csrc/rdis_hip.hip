@@ -12,6 +12,7 @@
 #include <numeric>
 
 #include "eval_kernels.hpp"
+#include "grad_tables.hpp"
 #include "refround_api.hpp"
 #include "solver_coop.hpp"
 #include "solver_lds.hpp"
@@ -24,6 +25,11 @@
 using namespace rdis_hip;
 
 // what abi_state.hpp and plan_options.hpp restate of the headers above for the translation units that do not see them
+static_assert(PLAN_INDEX_EINVAL == RDIS_HIP_EINVAL && PLAN_INDEX_EOVERLAP == RDIS_HIP_EOVERLAP && PLAN_INDEX_ERANGE == RDIS_HIP_ERANGE &&
+              PLAN_INDEX_KIND_BA == KIND_BA && GRAD_TABLES_NO_ENTRY == GRAD_NO_ENTRY, "a restated constant differs from its original");
+// grad_tables.hpp's pairs are uploaded as the int2 that grad_fused.hpp's tables name
+static_assert(sizeof(IntPair) == sizeof(int2) && offsetof(IntPair, x) == offsetof(int2, x) && offsetof(IntPair, y) == offsetof(int2, y),
+              "IntPair is not laid out as int2");
 static_assert(ABI_LDS_MAX_BYTES == LDS_MAX_BYTES && ABI_PIPE_TM == PIPE_TM && OPTION_QUAD_MAX_VARS == QUAD_MAX_VARS &&
               OPTION_COOP_MAX_WG == COOP_MAX_WG && OPTION_PTM_MAX_GROUP == PTM_WIDE_MAX_GROUP, "a restated constant differs from its original");
 
@@ -386,10 +392,8 @@ constexpr size_t GRAD_PLAN_BYTES = (size_t)1 << 30;
 
 bool fused_path(const rdis_hip_problem* p) { return p->kind == KIND_BA && p->ncam_blocks > 0; }
 
-// The tables of grad_fused.hpp for one factor list, built once per list.  Everything here is index work over the list:
-// cut it into chunks and tiles, number a tile's cameras, rank a chunk's entries by camera and by point block (list order
-// within a block: the order of the sums), decide per block whether one chunk / tile holds all its listed factors (straight to
-// g) or several do (a staging slot each, a block's slots consecutive in chunk / tile order).
+// The tables of grad_fused.hpp for one factor list, built once per list: the index work is grad_tables.hpp's; here the tile
+// size is chosen, the tables uploaded and the staging arrays allocated.
 int build_grad_plan(rdis_hip_problem* p, int64_t nf64, const int64_t* fac, GradPlan& G) {
     rdis_hip_ctx* c = p->ctx;
     const int nf = (int)nf64, GW = GRAD_LANES;
@@ -402,158 +406,23 @@ int build_grad_plan(rdis_hip_problem* p, int64_t nf64, const int64_t* fac, GradP
         blocks.erase(std::unique(blocks.begin(), blocks.end()), blocks.end());
         for (size_t i = 0; i < blocks.size(); ++i) p->h_cam_ord[(size_t)blocks[i]] = (int)i;
     }
-    auto fid_of = [&](int j) { return fac ? (int)fac[j] : j; };
-    // how many listed factors read each block
-    ivec cnt_cam(ncb, 0), cnt_pt(N, 0);
-    for (int j = 0; j < nf; ++j) { const int f = fid_of(j); ++cnt_cam[(size_t)p->h_cam_ord[(size_t)p->h_cam[(size_t)f]]]; ++cnt_pt[(size_t)p->h_pt[(size_t)f]]; }
     // tiles: up to tile_chunks chunks, fewer where their cameras would not fit (a chunk alone always does)
     const int want_tiles = 8 * std::max(1, c->num_cus);
     int tile_chunks = std::max(1, std::min(GRAD_MAX_TILE_CHUNKS, nchunks / want_tiles));
     if (const char* ev = std::getenv("RDIS_HIP_GRAD_TILE_CHUNKS")) tile_chunks = std::max(1, std::min(64, std::atoi(ev)));   // (tuning)
     const int cam_soft = 192;
-    const size_t npad = (size_t)nchunks * GW;
-    std::vector<unsigned short> sh(3 * npad, GRAD_NO_ENTRY);   // cl | rc | rp
-    unsigned short* const cl = sh.data();
-    unsigned short* const rc = cl + npad;
-    unsigned short* const rp = rc + npad;
-    ivec ptv(npad, 0), tile_chunk0, tile_cam0, chunk_cseg0((size_t)nchunks + 1, 0), chunk_pseg0((size_t)nchunks + 1, 0);
-    std::vector<int2> tile_cam, cseg, pseg;
-    ivec cam_tile(ncb, -1), cam_local(ncb, 0);           // camera ordinal -> tile it was last numbered in, its number there
-    ivec tcnt;                                            // listed factors of a tile's camera inside the tile
-    std::vector<std::pair<int, int>> cstaged, pstaged;    // (block, index of the table entry to patch), in tile / chunk order
-    ivec pt_chunk(N, -1), pt_seg(N, 0);                   // point block -> chunk it was last seen in, its segment there
-    ivec segcnt, segrow, seg_of((size_t)GW), cam_seg_chunk, cam_seg;
-    int ncam_cap = 1;
-    tile_chunk0.push_back(0); tile_cam0.push_back(0);
-    for (int ch0 = 0; ch0 < nchunks;) {
-        const int tile = (int)tile_chunk0.size() - 1;
-        const size_t tc0 = tile_cam.size();
-        int ch1 = ch0;
-        while (ch1 < nchunks && ch1 - ch0 < tile_chunks) {
-            // the cameras this chunk would add
-            const size_t before = tile_cam.size();
-            const int j0 = ch1 * GW, j1 = std::min(nf, j0 + GW);
-            for (int j = j0; j < j1; ++j) {
-                const int o = p->h_cam_ord[(size_t)p->h_cam[(size_t)fid_of(j)]];
-                if (cam_tile[(size_t)o] != tile) { cam_tile[(size_t)o] = tile; cam_local[(size_t)o] = (int)(tile_cam.size() - tc0); tile_cam.push_back(int2{o, 0}); }
-            }
-            if (ch1 > ch0 && tile_cam.size() - tc0 > (size_t)cam_soft) {   // too many: the chunk starts the next tile
-                for (size_t k = before; k < tile_cam.size(); ++k) cam_tile[(size_t)tile_cam[k].x] = -1;
-                tile_cam.resize(before);
-                break;
-            }
-            ++ch1;
-        }
-        const int nc = (int)(tile_cam.size() - tc0);
-        ncam_cap = std::max(ncam_cap, nc);
-        tcnt.assign((size_t)nc, 0);
-        cam_seg_chunk.assign((size_t)nc, -1); cam_seg.assign((size_t)nc, 0);
-        for (int ch = ch0; ch < ch1; ++ch) {
-            const int j0 = ch * GW, j1 = std::min(nf, j0 + GW);
-            // segments by camera, in order of first appearance; list order within a segment
-            segcnt.clear();
-            for (int j = j0; j < j1; ++j) {
-                const int f = fid_of(j);
-                const int l = cam_local[(size_t)p->h_cam_ord[(size_t)p->h_cam[(size_t)f]]];
-                cl[j] = (unsigned short)l;
-                ptv[(size_t)j] = p->h_pt[(size_t)f];
-                ++tcnt[(size_t)l];
-                if (cam_seg_chunk[(size_t)l] != ch) { cam_seg_chunk[(size_t)l] = ch; cam_seg[(size_t)l] = (int)segcnt.size(); segcnt.push_back(0); cseg.push_back(int2{l, 0}); }
-                seg_of[(size_t)(j - j0)] = cam_seg[(size_t)l];
-                ++segcnt[(size_t)cam_seg[(size_t)l]];
-            }
-            {
-                const size_t s0 = cseg.size() - segcnt.size();
-                segrow.assign(segcnt.size() + 1, 0);
-                for (size_t k = 0; k < segcnt.size(); ++k) { segrow[k + 1] = segrow[k] + segcnt[k]; cseg[s0 + k].y = segrow[k]; }
-                for (int j = j0; j < j1; ++j) rc[j] = (unsigned short)segrow[(size_t)seg_of[(size_t)(j - j0)]]++;
-                cseg.push_back(int2{0, j1 - j0});
-                chunk_cseg0[(size_t)ch + 1] = (int)cseg.size();
-            }
-            // ... and by point block
-            segcnt.clear();
-            for (int j = j0; j < j1; ++j) {
-                const int q = ptv[(size_t)j];
-                if (pt_chunk[(size_t)q] != ch) { pt_chunk[(size_t)q] = ch; pt_seg[(size_t)q] = (int)segcnt.size(); segcnt.push_back(0); pseg.push_back(int2{q, 0}); }
-                seg_of[(size_t)(j - j0)] = pt_seg[(size_t)q];
-                ++segcnt[(size_t)pt_seg[(size_t)q]];
-            }
-            {
-                const size_t s0 = pseg.size() - segcnt.size();
-                segrow.assign(segcnt.size() + 1, 0);
-                for (size_t k = 0; k < segcnt.size(); ++k) {
-                    segrow[k + 1] = segrow[k] + segcnt[k];
-                    pseg[s0 + k].y = segrow[k];
-                    // all the block's listed factors in this chunk: its sum goes straight to g (destination = its id, as set)
-                    if (segcnt[k] != cnt_pt[(size_t)pseg[s0 + k].x]) pstaged.emplace_back(pseg[s0 + k].x, (int)(s0 + k));
-                }
-                for (int j = j0; j < j1; ++j) rp[j] = (unsigned short)segrow[(size_t)seg_of[(size_t)(j - j0)]]++;
-                pseg.push_back(int2{0, j1 - j0});
-                chunk_pseg0[(size_t)ch + 1] = (int)pseg.size();
-            }
-        }
-        for (int l = 0; l < nc; ++l) {
-            int2& e = tile_cam[tc0 + (size_t)l];
-            const int o = e.x;
-            if (tcnt[(size_t)l] == cnt_cam[(size_t)o]) e.y = -1;   // (patched below: the block's first variable id)
-            else { e.y = -2; cstaged.emplace_back(o, (int)(tc0 + (size_t)l)); }
-        }
-        tile_chunk0.push_back(ch1);
-        tile_cam0.push_back((int)tile_cam.size());
-        ch0 = ch1;
-    }
-    // camera ordinal -> first variable id
-    ivec cam_first(ncb, 0);
-    for (size_t v = 0; v < N; ++v) if (p->h_cam_ord[v] >= 0) cam_first[(size_t)p->h_cam_ord[v]] = (int)v;
-    for (int2& e : tile_cam) if (e.y == -1) e.y = cam_first[(size_t)e.x];
-    // staging slots: a block's partial sums consecutive, in the order they were made
-    ivec cs_var, cs_ptr(1, 0), ps_var, ps_ptr(1, 0);
-    {
-        ivec n_of(ncb, 0), base(ncb, 0);
-        for (const auto& e : cstaged) ++n_of[(size_t)e.first];
-        for (size_t o = 0; o < ncb; ++o)
-            if (n_of[o] > 0) { base[o] = cs_ptr.back(); cs_var.push_back(cam_first[o]); cs_ptr.push_back(cs_ptr.back() + n_of[o]); }
-        for (const auto& e : cstaged) tile_cam[(size_t)e.second].y = ~(base[(size_t)e.first]++);
-    }
-    {
-        ivec& n_of = pt_seg;    // (scratch: the per-chunk segment numbers are not needed any more)
-        ivec& base = pt_chunk;
-        for (const auto& e : pstaged) n_of[(size_t)e.first] = 0;
-        for (const auto& e : pstaged) ++n_of[(size_t)e.first];
-        ivec blocks;
-        for (const auto& e : pstaged) if (n_of[(size_t)e.first] > 0) { blocks.push_back(e.first); n_of[(size_t)e.first] = -n_of[(size_t)e.first]; }
-        std::sort(blocks.begin(), blocks.end());
-        for (int q : blocks) { base[(size_t)q] = ps_ptr.back(); ps_var.push_back(q); ps_ptr.push_back(ps_ptr.back() - n_of[(size_t)q]); }
-        for (const auto& e : pstaged) pseg[(size_t)e.second].x = ~(base[(size_t)e.first]++);
-    }
-    // variables no listed factor reads
-    ivec zvar;
-    {
-        cvec touched(N, 0);
-        for (size_t o = 0; o < ncb; ++o) if (cnt_cam[o] > 0) for (int k = 0; k < 9; ++k) touched[(size_t)cam_first[o] + k] = 1;
-        for (size_t v = 0; v < N; ++v) if (cnt_pt[v] > 0) for (int k = 0; k < 3; ++k) touched[v + k] = 1;
-        for (size_t v = 0; v < N; ++v) if (!touched[v]) zvar.push_back((int)v);
-    }
-    // one int32 block, one 16-bit block
-    ivec blk;
-    auto put = [&](const int* v, size_t n) { const size_t off = blk.size(); blk.insert(blk.end(), v, v + n); if (blk.size() & 1) blk.push_back(0); return off; };
-    const size_t o_ptv = put(ptv.data(), ptv.size()), o_tc0 = put(tile_chunk0.data(), tile_chunk0.size()), o_tm0 = put(tile_cam0.data(), tile_cam0.size());
-    const size_t o_tcam = put(reinterpret_cast<const int*>(tile_cam.data()), 2 * tile_cam.size());
-    const size_t o_cs0 = put(chunk_cseg0.data(), chunk_cseg0.size()), o_cseg = put(reinterpret_cast<const int*>(cseg.data()), 2 * cseg.size());
-    const size_t o_ps0 = put(chunk_pseg0.data(), chunk_pseg0.size()), o_pseg = put(reinterpret_cast<const int*>(pseg.data()), 2 * pseg.size());
-    const size_t o_csv = put(cs_var.data(), cs_var.size()), o_csp = put(cs_ptr.data(), cs_ptr.size());
-    const size_t o_psv = put(ps_var.data(), ps_var.size()), o_psp = put(ps_ptr.data(), ps_ptr.size());
-    const size_t o_z = put(zvar.data(), zvar.size());
-    int rc_ = upload(c, G.ints, blk);
-    if (!rc_) rc_ = upload(c, G.shorts, sh.data(), sh.size());
+    GradIndex X;
+    grad_tables_build(N, ncb, p->h_cam.data(), p->h_pt.data(), p->h_cam_ord.data(), nf, fac, GW, tile_chunks, cam_soft, X);
+    int rc_ = upload(c, G.ints, X.blk);
+    if (!rc_) rc_ = upload(c, G.shorts, X.sh.data(), X.sh.size());
     if (!rc_ && fac) {
         ivec f32((size_t)nf);
         for (int j = 0; j < nf; ++j) f32[(size_t)j] = (int)fac[j];
         rc_ = upload(c, G.fac, f32);
         if (!rc_) HIPCHK(c, hipStreamSynchronize(c->stream));   // (f32 goes out of scope)
     }
-    if (!rc_) rc_ = dalloc(c, G.cstage, (size_t)std::max(cs_ptr.back(), 1) * 9 * sizeof(double));
-    if (!rc_) rc_ = dalloc(c, G.pstage, (size_t)std::max(ps_ptr.back(), 1) * 3 * sizeof(double));
+    if (!rc_) rc_ = dalloc(c, G.cstage, (size_t)std::max(X.cstage_slots, 1) * 9 * sizeof(double));
+    if (!rc_) rc_ = dalloc(c, G.pstage, (size_t)std::max(X.pstage_slots, 1) * 3 * sizeof(double));
     if (!rc_) rc_ = dalloc(c, G.partial, (size_t)std::max(nchunks, 1) * sizeof(double));
     if (rc_) {   // (the uploads above are asynchronous copies out of host vectors that go out of scope with this call)
         (void)hipStreamSynchronize(c->stream);
@@ -563,14 +432,15 @@ int build_grad_plan(rdis_hip_problem* p, int64_t nf64, const int64_t* fac, GradP
     const int* I = G.ints.as<int>();
     const unsigned short* S = G.shorts.as<unsigned short>();
     GradTables& T = G.T;
-    T.nf = nf; T.nchunks = nchunks; T.ntiles = (int)tile_chunk0.size() - 1; T.ncam_cap = ncam_cap;
+    const size_t npad = X.npad;
+    T.nf = nf; T.nchunks = nchunks; T.ntiles = X.ntiles; T.ncam_cap = X.ncam_cap;
     T.fac = fac ? G.fac.as<int>() : nullptr;
     T.cl = S; T.rc = S + npad; T.rp = S + 2 * npad;
-    T.ptv = I + o_ptv; T.tile_chunk0 = I + o_tc0; T.tile_cam0 = I + o_tm0; T.tile_cam = reinterpret_cast<const int2*>(I + o_tcam);
-    T.chunk_cseg0 = I + o_cs0; T.cseg = reinterpret_cast<const int2*>(I + o_cseg);
-    T.chunk_pseg0 = I + o_ps0; T.pseg = reinterpret_cast<const int2*>(I + o_pseg);
-    T.ncs = (int)cs_var.size(); T.nps = (int)ps_var.size(); T.nz = (int)zvar.size();
-    T.cs_var = I + o_csv; T.cs_ptr = I + o_csp; T.ps_var = I + o_psv; T.ps_ptr = I + o_psp; T.zvar = I + o_z;
+    T.ptv = I + X.o_ptv; T.tile_chunk0 = I + X.o_tc0; T.tile_cam0 = I + X.o_tm0; T.tile_cam = reinterpret_cast<const int2*>(I + X.o_tcam);
+    T.chunk_cseg0 = I + X.o_cs0; T.cseg = reinterpret_cast<const int2*>(I + X.o_cseg);
+    T.chunk_pseg0 = I + X.o_ps0; T.pseg = reinterpret_cast<const int2*>(I + X.o_pseg);
+    T.ncs = X.ncs; T.nps = X.nps; T.nz = X.nz;
+    T.cs_var = I + X.o_csv; T.cs_ptr = I + X.o_csp; T.ps_var = I + X.o_psv; T.ps_ptr = I + X.o_psp; T.zvar = I + X.o_z;
     G.nf = nf64;
     return 0;
 }
@@ -906,9 +776,8 @@ static int plan_create_impl(rdis_hip_problem* p, bool transient, int64_t ncomp, 
     rdis_hip_ctx* c = p->ctx;
     *out = nullptr;
     const int64_t nfree = free_ptr[ncomp], nfac = fac_ptr[ncomp];
-    if (free_ptr[0] != 0 || fac_ptr[0] != 0 || nfree < 0 || nfac < 0 || (nfree && !free_vid) || (nfac && !fac_id))
-        return fail(c, RDIS_HIP_EINVAL, "plan_create: bad CSR");
-    if (nfree >= (1ll << 31) / 5 || nfac >= ((1ll << 31) - 16) / 12) return fail(c, RDIS_HIP_ERANGE, "plan_create: too large");
+    std::string why;
+    if (int rc = plan_index_check(ncomp, free_ptr, free_vid, fac_ptr, fac_id, &why)) return fail(c, rc, why);
     if (int rc = refuse_exponential(p, nfac, fac_id, "plan_create")) return rc;
     USE_DEVICE(c);
     int rc = ensure_problem_scratch(p);
@@ -921,158 +790,11 @@ static int plan_create_impl(rdis_hip_problem* p, bool transient, int64_t ncomp, 
     // (A/B runs of callers that cannot reach the plan's options, e.g. rdis_hip_cgd_batch: RDIS_HIP_COOP_PIPELINE=0 / 1)
     if (const char* ev = std::getenv("RDIS_HIP_COOP_PIPELINE")) L->coop_pipeline = std::atoi(ev) != 0;
 
-    // --- validate independence (free sets disjoint, factors owned once, no factor of one
-    // component reading a free variable of another); the marks are a persistent per-problem
-    // array validated by a stamp, so a call costs O(its own size), not O(N)
-    const int stamp = ++p->stamp;
-    VarMark* const mark = p->h_mark.data();
-    L->h_free_ptr.resize((size_t)ncomp + 1); L->h_fac_ptr.resize((size_t)ncomp + 1);
-    L->h_free_vid.resize((size_t)nfree); L->h_fac_id.resize((size_t)nfac);
-    for (int64_t cc = 0; cc <= ncomp; ++cc) {
-        if (cc && (free_ptr[cc] < free_ptr[cc - 1] || fac_ptr[cc] < fac_ptr[cc - 1]))
-            return fail(c, RDIS_HIP_EINVAL, "plan_create: ptr not monotone");
-        L->h_free_ptr[(size_t)cc] = (int)free_ptr[cc];
-        L->h_fac_ptr[(size_t)cc] = (int)fac_ptr[cc];
-    }
-    for (int64_t cc = 0; cc < ncomp; ++cc)
-        for (int64_t i = free_ptr[cc]; i < free_ptr[cc + 1]; ++i) {
-            const int64_t v = free_vid[i];
-            if (v < 0 || v >= p->N) return fail(c, RDIS_HIP_EINVAL, "plan_create: free variable id out of range");
-            VarMark& mk = mark[(size_t)v];
-            if (mk.stamp == stamp) return fail(c, RDIS_HIP_EOVERLAP, "plan_create: variable " + std::to_string(v) + " is free in two components (or listed twice)");
-            mk.stamp = stamp; mk.owner = (int)cc; mk.gidx = (int)i;
-            L->h_free_vid[(size_t)i] = (int)v;
-        }
-    // One pass over the listed factors' slots leaves, per slot, the position of its variable in the
-    // plan's free list (-1: a constant for this solve) and counts the slots per variable; a second,
-    // sequential one turns that into the variable-major position of the slot's partial (slot_pos) and
-    // the variable's index within its component (h_slot_li: what the cooperative layouts address by).
-    ivec& v2s_ptr = L->h_v2s_ptr;
-    v2s_ptr.assign((size_t)nfree + 1, 0);
-    ivec slot_base((size_t)nfac + 1);
-    slot_base[0] = 0;
-    int* const fid32 = L->h_fac_id.data();
-    int* const cnt = v2s_ptr.data() + 1;
-    const bool ba = p->kind == KIND_BA;
-    if (ba) L->nslots = 12 * nfac;
-    else {
-        int64_t ns = 0;
-        for (int64_t j = 0; j < nfac; ++j) {
-            const int64_t f = fac_id[j];
-            if (f < 0 || f >= p->F) return fail(c, RDIS_HIP_EINVAL, "plan_create: factor id out of range");
-            ns += p->arity((int)f);
-        }
-        if (ns >= (1ll << 31) - 16) return fail(c, RDIS_HIP_ERANGE, "plan_create: too large");
-        L->nslots = ns;
-    }
-    ivec& sli = L->h_slot_li;
-    sli.resize((size_t)L->nslots);
-    int* const gi = sli.data();
-    auto other_owner = [&](int64_t f, int64_t cc, int o) {
-        return fail(c, RDIS_HIP_EOVERLAP, "plan_create: factor " + std::to_string(f) + " of component " + std::to_string(cc) + " reads a free variable of component " + std::to_string(o));
-    };
-    for (int64_t cc = 0; cc < ncomp; ++cc) {
-        const int icc = (int)cc;
-        for (int64_t j = fac_ptr[cc]; j < fac_ptr[cc + 1]; ++j) {
-            const int64_t f = fac_id[j];
-            if (f < 0 || f >= p->F) return fail(c, RDIS_HIP_EINVAL, "plan_create: factor id out of range");
-            if (p->h_fac_stamp[(size_t)f] == stamp) return fail(c, RDIS_HIP_EOVERLAP, "plan_create: factor " + std::to_string(f) + " listed twice");
-            p->h_fac_stamp[(size_t)f] = stamp;
-            fid32[j] = (int)f;
-            if (ba) {
-                slot_base[(size_t)j + 1] = 12 * (int)(j + 1);
-                int* g = gi + 12 * j;
-                const VarMark* mc = mark + p->h_cam[(size_t)f];
-                const VarMark* mp = mark + p->h_pt[(size_t)f];
-#pragma unroll
-                for (int k = 0; k < 12; ++k) {
-                    const VarMark& mk = k < 9 ? mc[k] : mp[k - 9];
-                    int pos = -1;
-                    if (mk.stamp == stamp) {
-                        if (mk.owner != icc) return other_owner(f, cc, mk.owner);
-                        pos = mk.gidx;
-                        ++cnt[pos];
-                    }
-                    g[k] = pos;
-                }
-            } else {
-                const int a = p->arity((int)f), sb = slot_base[(size_t)j];
-                slot_base[(size_t)j + 1] = sb + a;
-                for (int k = 0; k < a; ++k) {
-                    const VarMark& mk = mark[(size_t)p->var_of((int)f, k)];
-                    int pos = -1;
-                    if (mk.stamp == stamp) {
-                        if (mk.owner != icc) return other_owner(f, cc, mk.owner);
-                        pos = mk.gidx;
-                        ++cnt[pos];
-                    }
-                    gi[sb + k] = pos;
-                }
-            }
-        }
-    }
-    for (int64_t i = 0; i < nfree; ++i) v2s_ptr[(size_t)i + 1] += v2s_ptr[(size_t)i];
-    L->ngfac = v2s_ptr[(size_t)nfree];
-    // heaviest components first (longest-processing-time order for the launch)
-    L->h_order.resize((size_t)ncomp);
-    std::iota(L->h_order.begin(), L->h_order.end(), 0);
-    std::stable_sort(L->h_order.begin(), L->h_order.end(), [&](int a, int b) {
-        return (fac_ptr[a + 1] - fac_ptr[a]) > (fac_ptr[b + 1] - fac_ptr[b]);
-    });
-
-    // --- one int32 block, one H2D copy
-    ivec& blk = L->h_blk;
-    blk.reserve((size_t)(4 * ncomp + 3 * nfree + 2 * nfac + L->nslots) + 64);
-    auto put = [&](const ivec& v) { const size_t off = blk.size(); blk.insert(blk.end(), v.begin(), v.end()); return off; };
-    L->off_order = put(L->h_order);
-    L->off_free_ptr = put(L->h_free_ptr); L->off_free_vid = put(L->h_free_vid);
-    L->off_fac_ptr = put(L->h_fac_ptr); L->off_fac_id = put(L->h_fac_id);
-    L->off_v2s_ptr = put(v2s_ptr); L->off_slot_base = put(slot_base);
-    {   // gfac is variable-major: slot_pos[s] = where listed factor slot s lands in it (-1: not free here),
-        // the slots of a variable in listed order; the positions above become component-local indices
-        L->off_slot_pos = blk.size();
-        blk.resize(blk.size() + (size_t)L->nslots);
-        int* const slot_pos = blk.data() + L->off_slot_pos;
-        ivec fill(v2s_ptr.begin(), v2s_ptr.end() - 1);
-        int* const fl = fill.data();
-        for (int64_t cc = 0; cc < ncomp; ++cc) {
-            const int f0 = (int)free_ptr[cc];
-            const int64_t s0 = slot_base[(size_t)fac_ptr[cc]], s1 = slot_base[(size_t)fac_ptr[cc + 1]];
-            for (int64_t s = s0; s < s1; ++s) {
-                const int g = gi[s];
-                slot_pos[s] = g >= 0 ? fl[g]++ : -1;
-                gi[s] = g >= 0 ? g - f0 : -1;
-            }
-        }
-    }
-    // (the per-slot local indices serve prepare_partition's cooperative groups, bundle adjustment only; a plan
-    // too large for them to matter does not keep them: prepare_partition then forms a group's indices itself)
-    if (!ba || L->nslots > (64ll << 20)) { ivec().swap(L->h_slot_li); }
-    {   // per component: the camera blocks with a free rotation variable (their records follow the trial
-        // point) and where in the component's vectors their three rotation variables are (-1: constant)
-        ivec cb_ptr((size_t)ncomp + 1, 0), cb, cb_li;
-        if (p->kind == KIND_BA && p->ncam_blocks > 0) {
-            std::vector<std::array<int, 3>> ent;   // (block, which of the three, local index)
-            for (int64_t cc = 0; cc < ncomp; ++cc) {
-                ent.clear();
-                for (int64_t i = free_ptr[cc]; i < free_ptr[cc + 1]; ++i) {
-                    const int v = L->h_free_vid[(size_t)i], b = p->h_block_of[(size_t)v];
-                    if (b >= 0 && v - b < 3) ent.push_back({b, v - b, (int)(i - free_ptr[cc])});
-                }
-                std::sort(ent.begin(), ent.end());
-                for (const auto& e : ent) {
-                    if (cb.size() == (size_t)cb_ptr[(size_t)cc] || cb.back() != e[0]) {
-                        cb.push_back(e[0]);
-                        cb_li.insert(cb_li.end(), {-1, -1, -1});
-                    }
-                    cb_li[cb_li.size() - 3 + (size_t)e[1]] = e[2];
-                }
-                cb_ptr[(size_t)cc + 1] = (int)cb.size();
-            }
-        }
-        for (int64_t cc = 0; cc < ncomp; ++cc) cb_ptr[(size_t)cc + 1] = std::max(cb_ptr[(size_t)cc + 1], cb_ptr[(size_t)cc]);
-        L->off_cb_ptr = put(cb_ptr); L->off_cb = put(cb); L->off_cb_li = put(cb_li);
-    }
+    // the lists checked for independence and laid out as the plan's tables (plan_index.hpp)
+    const IndexArrays P{p->kind, p->N, p->F, p->h_cam.data(), p->h_pt.data(), p->h_rowptr.data(), p->h_vid.data(),
+                        p->h_block_of.data(), p->ncam_blocks, p->h_mark.data(), p->h_fac_stamp.data(), ++p->stamp};
+    if ((rc = plan_index_build(P, ncomp, free_ptr, free_vid, fac_ptr, fac_id, *L, &why))) return fail(c, rc, why);
+    const ivec& blk = L->h_blk;
 
     const size_t nc = (size_t)ncomp;
     L->out_bytes = ((size_t)nfree + 2 * nc) * 8 + 2 * nc * 8 + 3 * nc * 4;
