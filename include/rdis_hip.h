@@ -311,9 +311,11 @@ int rdis_hip_plan_fetch_starts(rdis_hip_plan *plan, double *x_out, double *fret,
  *                       population_assign, _get_x and evaluations do not invalidate.
  *   population_set_option   "eval_workspace_bytes" (default 2^30, the default of "starts_workspace_bytes"; >= 0; lowering it
  *                       releases scratch beyond it), "eval_batched" (default 1; 0 = the evaluation member by member through
- *                       the problem's scratch, two or three launches a member: the yardstick of the batched path).
+ *                       the problem's scratch, two or three launches a member: the yardstick of the batched path),
+ *                       "grad_workspace_bytes" (population_eval_grad below; default 2^30; >= 0; lowering it releases scratch).
  *   population_get_info     "eval_members_per_launch" (R of the last evaluation), "eval_launches" (kernels it launched),
- *                       "eval_valid" (1: best / assign_best are served).  Unknown names: RDIS_HIP_EINVAL.
+ *                       "eval_valid" (1: best / assign_best are served); "grad_members_per_launch", "grad_launches" and
+ *                       "grad_branch" of the last gradient call (population_eval_grad below).  Unknown names: RDIS_HIP_EINVAL.
  *   plan_solve_population   asynchronous on the context's stream.  For every member s and component c exactly what
  *                       plan_set_start(plan, NULL) + plan_solve would do on a problem whose assigned x is X[s] -- the same
  *                       bits in fret, delta, x, iters, status, nfeval, ngeval: the start is X[s][free_vid], clamped at
@@ -400,7 +402,37 @@ int rdis_hip_plan_fetch_starts(rdis_hip_plan *plan, double *x_out, double *fret,
  *                       RDIS_HIP_EINVAL.  plan_fetch_population afterwards returns [count][...] arrays, row i belonging to
  *                       member first + i.  The splitting by "starts_workspace_bytes" ("starts_per_launch" /
  *                       "starts_launches" of count members), plan_last_kernel_ms and every refusal are the whole-population
- *                       entry's. */
+ *                       entry's.
+ *
+ * The members' gradients, the member a grid dimension (computeGradient(facs, pg) on every member at once):
+ *   population_eval_grad   f[count] and g[count][N], row-major, for members first .. first + count - 1; nf / fac as in
+ *                       rdis_hip_eval_grad (fac == NULL: all factors).  Row k holds, bit for bit, what rdis_hip_eval_grad(p, nf,
+ *                       fac, ...) returns on a problem whose assigned x is X[first + k], exact zeros where no listed factor
+ *                       reads included.  The range is checked like population_set_x's; count == 0 succeeds and does nothing;
+ *                       count N beyond what population_create accepts: RDIS_HIP_ERANGE.  nf == 0: zeros in both, no kernel.
+ *                       Refusals are rdis_hip_eval_grad's (the list's form; an exponential factor; a tile's cameras that do
+ *                       not fit the LDS), each with a message.  The form is rdis_hip_eval_grad's for the list
+ *                       (population_get_info "grad_branch": 0 none, 1 the fused pass, 2 a list of one chunk, 3 two passes);
+ *                       the list's tables are shared by the members (and cached with the problem, as rdis_hip_eval_grad's
+ *                       are), every member of a launch has scratch of its own, the population's -- camera records, staging
+ *                       arrays and chunk sums (fused), the per-factor partials and value partials (the others): rdis_amd/csrc/
+ *                       population_grid.hpp, grad_member_bytes -- within the option "grad_workspace_bytes" (default 2^30;
+ *                       negative: RDIS_HIP_EINVAL; lowering it releases scratch beyond it): R = min(count, 65535, max(1,
+ *                       bound / bytes per member)) members a round ("grad_members_per_launch"), ceil(count / R) rounds of
+ *                       three or four kernels ("grad_launches" counts them).  No bit depends on R.  Not written: X, the
+ *                       values, "eval_valid" and the best member of the last population_eval; the problem's x and the
+ *                       scratch and results of its own evaluation entries (the pointers rdis_hip_eval_grad_device handed
+ *                       out keep their contents).
+ *   population_eval_grad_device   the same, left on the device: *f_dev -> f[count], *g_dev -> g[count][N], buffers of the
+ *                       population, grown on demand, valid until the next gradient call on this population or its
+ *                       destruction.  Enqueued on the context's stream; nothing is waited for but what a list's first use
+ *                       waits for (its tables; the staging of an explicit list).  population_eval_grad is this entry, two
+ *                       copies and one synchronisation.
+ *   population_grad_max   gmax[k] = max_i |g[k][i]| for every row k of the last gradient call (NaN if an entry of the row is
+ *                       one), exact: its bits do not depend on the reduction.  gmax (host, [rows]) and gmax_dev (the address
+ *                       of the population's buffer; enqueued, no wait) may each be NULL.  It describes the rows as that call
+ *                       left them -- a later population_set_x, _sort, _sample or solve does not change it.  Before any
+ *                       gradient call: RDIS_HIP_EINVAL ("evaluate the gradient first"). */
 typedef struct rdis_hip_population rdis_hip_population;
 int rdis_hip_population_create(rdis_hip_problem *p, int64_t nmembers, const double *x, rdis_hip_population **out);
 void rdis_hip_population_destroy(rdis_hip_population *pop);
@@ -419,6 +451,11 @@ int rdis_hip_population_set_sampling(rdis_hip_population *pop, const double *lo,
 int rdis_hip_population_sample(rdis_hip_population *pop, int64_t first, int64_t count, int64_t n, const int64_t *vid,
                                uint64_t seed, int64_t stream);
 int rdis_hip_population_sort(rdis_hip_population *pop, int64_t *order_out);
+int rdis_hip_population_eval_grad(rdis_hip_population *pop, int64_t first, int64_t count, int64_t nf, const int64_t *fac,
+                                  double *f, double *g);
+int rdis_hip_population_eval_grad_device(rdis_hip_population *pop, int64_t first, int64_t count, int64_t nf,
+                                         const int64_t *fac, void **f_dev, void **g_dev);
+int rdis_hip_population_grad_max(rdis_hip_population *pop, double *gmax, void **gmax_dev);
 int rdis_hip_plan_solve_population(rdis_hip_plan *plan, rdis_hip_population *pop, int32_t maxiters, double ftol);
 int rdis_hip_plan_solve_population_range(rdis_hip_plan *plan, rdis_hip_population *pop, int64_t first, int64_t count,
                                          int32_t maxiters, double ftol);

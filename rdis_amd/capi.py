@@ -94,6 +94,9 @@ SYMBOLS = {
     "rdis_hip_population_set_sampling": (C.c_int, [_vp, _vp, _vp]),
     "rdis_hip_population_sample": (C.c_int, [_vp, _i64, _i64, _i64, _vp, C.c_uint64, _i64]),
     "rdis_hip_population_sort": (C.c_int, [_vp, _vp]),
+    "rdis_hip_population_eval_grad": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "rdis_hip_population_eval_grad_device": (C.c_int, [_vp, _i64, _i64, _i64, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "rdis_hip_population_grad_max": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "rdis_hip_plan_solve_population": (C.c_int, [_vp, _vp, C.c_int32, C.c_double]),
     "rdis_hip_plan_solve_population_range": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int32, C.c_double]),
     "rdis_hip_plan_fetch_population": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -540,12 +543,43 @@ class Population:
         self.ctx.check(self.ctx.lib.rdis_hip_population_sort(self.h, _ptr(order)))
         return order
 
+    def eval_grad(self, fac=None, first=0, count=None):
+        """(f[count], g[count, nvars]) of members first .. first + count - 1 (default: to the last): row k is, bit for bit, what
+        Problem.eval_grad(fac) returns with member first + k's x assigned -- all members in one round of three or four kernels
+        (info("grad_launches")), the member a grid dimension.  X, the last eval()'s values and the problem are not written"""
+        first, count = self._range(first, count)
+        fac, nf = self.prob._nf(fac)
+        f, g = np.empty(max(count, 0)), np.empty((max(count, 0), self.nvars))
+        self.ctx.check(self.ctx.lib.rdis_hip_population_eval_grad(self.h, first, count, nf, _ptr(fac), _ptr(f), _ptr(g)))
+        if count > 0:
+            self._grad_rows = count
+        return f, g
+
+    def eval_grad_device(self, fac=None, first=0, count=None):
+        """the same left on the device: the addresses of f[count] and g[count, nvars] (Context.copy_to_host reads them), valid
+        until the next gradient call on this population.  Enqueued; fac=None: nothing is waited for once the tables exist"""
+        first, count = self._range(first, count)
+        fac, nf = self.prob._nf(fac)
+        fd, gd = _vp(), _vp()
+        self.ctx.check(self.ctx.lib.rdis_hip_population_eval_grad_device(self.h, first, count, nf, _ptr(fac), C.byref(fd), C.byref(gd)))
+        if count > 0:
+            self._grad_rows = count
+        return fd.value, gd.value
+
+    def grad_max(self) -> np.ndarray:
+        """[rows]: max |g[k, :]| of every row of the last gradient call (NaN where the row holds one), reduced on the device"""
+        out = np.empty(getattr(self, "_grad_rows", 0))     # (no gradient call yet: the library refuses)
+        self.ctx.check(self.ctx.lib.rdis_hip_population_grad_max(self.h, _ptr(out), None))
+        return out
+
     def set_option(self, name: str, value: int):
-        """eval_workspace_bytes (scratch of a launch of the evaluation; default 2^30), eval_batched (default 1; 0: member by member)"""
+        """eval_workspace_bytes (scratch of a launch of the evaluation; default 2^30), eval_batched (default 1; 0: member by member),
+        grad_workspace_bytes (scratch of a round of eval_grad; default 2^30)"""
         self.ctx.check(self.ctx.lib.rdis_hip_population_set_option(self.h, name.encode(), int(value)))
 
     def info(self, name: str) -> int:
-        """eval_members_per_launch, eval_launches (kernels of the last evaluation), eval_valid"""
+        """eval_members_per_launch, eval_launches (kernels of the last evaluation), eval_valid; grad_members_per_launch,
+        grad_launches (kernels of the last gradient call), grad_branch (0 none, 1 fused, 2 short, 3 two-pass)"""
         v = _i64()
         self.ctx.check(self.ctx.lib.rdis_hip_population_get_info(self.h, name.encode(), C.byref(v)))
         return int(v.value)

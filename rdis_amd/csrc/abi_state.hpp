@@ -145,6 +145,7 @@ struct GradPlan {
     int64_t nf = 0;
     DevBuf ints, shorts, fac;      // one int32 block, one 16-bit block, the list as int32 (explicit lists)
     DevBuf cstage, pstage, partial;
+    int cstage_slots = 0, pstage_slots = 0;   // slots of the staging arrays (a population's gradient sizes its replicas by them)
     std::vector<int64_t> ids;      // the list itself (explicit lists): compared on a hash hit -- two lists with the same hashes must not share tables
     size_t device_bytes() const { return ints.bytes + shorts.bytes + fac.bytes + cstage.bytes + pstage.bytes + partial.bytes; }
     rdis_hip::GradTables T{};

@@ -200,6 +200,88 @@ gather_grad_kernel(int nvars, const int* __restrict__ v2s_ptr, const int* __rest
     }
 }
 
+// ---- value and gradient of a population on the short and the two-pass branch (rdis_hip.hip: population_grad_enqueue) ----
+// Block (., r) is member first + r of X[members][N]: the view's x becomes the member's row, gfac replica r of the launch's
+// [members of the launch][nslots] (wave-uniform: scalar registers); the statements, and so the bits, are the single-x kernels'.
+
+// partials_kernel<KIND_BA> per member: grid (blocks, members of the launch)
+__global__ void __launch_bounds__(256)
+population_partials_kernel(ProblemView P, double* __restrict__ X, long long first, int nf, const int* __restrict__ fac, double* __restrict__ gfac,
+                           long long nslots) {
+    const long long r = blockIdx.y;
+    P.x = X + (first + r) * (long long)P.N;
+    gfac += r * nslots;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nf; i += gridDim.x * blockDim.x)
+        factor_partials<KIND_BA>(P, gfac, nullptr, fac ? fac[i] : i);
+}
+
+// eval_sum_kernel<KIND, true> per member: grid (nb, members of the launch), nb the block count rdis_hip_eval_grad takes for nf;
+// partial: [members of the launch][nb]
+template <int KIND>
+__global__ void __launch_bounds__(256)
+population_eval_sum_grad_kernel(ProblemView P, double* __restrict__ X, long long first, int nf, const int* __restrict__ fac, double* __restrict__ gfac,
+                                long long nslots, double* __restrict__ partial) {
+    __shared__ double red[MAX_WAVES];
+    const long long r = blockIdx.y;
+    P.x = X + (first + r) * (long long)P.N;
+    const double acc = eval_sum_of<KIND, true>(P, nf, fac, gfac + r * nslots, (int)blockIdx.x, (int)gridDim.x, red);
+    if (threadIdx.x == 0) partial[r * gridDim.x + blockIdx.x] = acc;
+}
+
+// gather_grad_kernel per member: grid (blocks, members of the launch); the gather lists are the members' common ones, member
+// first + r's row of the result is G[row0 + r].  The loop is gather_grad_kernel's, RESTATED line by line (moving it into a
+// function the two kernels share changes that kernel's registers: 58 scalar / 44 vector become 57 / 45): the slots' positions,
+// their values, the additions strictly in order -- a change to either loop is a change to both.
+__global__ void __launch_bounds__(256)
+population_gather_grad_kernel(int nvars, const int* __restrict__ v2s_ptr, const int* __restrict__ v2s_idx, const double* __restrict__ gfac, long long nslots,
+                              double* __restrict__ G, long long row0) {
+    const long long r = blockIdx.y;
+    gfac += r * nslots;
+    double* __restrict__ g = G + (row0 + r) * (long long)nvars;
+    for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < nvars; v += gridDim.x * blockDim.x) {
+        const int b = v2s_ptr[v], e = v2s_ptr[v + 1];
+        double s = 0.0;
+        for (int k0 = b; k0 < e; k0 += 16) {
+            int id[16];
+            double t[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) id[j] = (k0 + j < e) ? v2s_idx[k0 + j] : 0;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) t[j] = (k0 + j < e) ? gfac[id[j]] : 0.0;
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                if (k0 + j < e) s = (k0 + j == b) ? t[j] : s + t[j];
+        }
+        g[v] = s;
+    }
+}
+
+// gmax[k] = max_i |G[k][i]|, NaN if any entry of the row is one: one workgroup per row, lanes stride over the row.  A maximum
+// is exact, so no bit depends on the shape of the reduction.
+__global__ void __launch_bounds__(256)
+population_grad_max_kernel(long long N, const double* __restrict__ G, double* __restrict__ gmax) {
+    __shared__ double wm[MAX_WAVES];
+    __shared__ int wn[MAX_WAVES];
+    const double* row = G + (long long)blockIdx.x * N;
+    double m = 0.0;
+    int isnan_ = 0;
+    for (long long i = threadIdx.x; i < N; i += blockDim.x) {
+        const double a = __builtin_fabs(row[i]);
+        if (a != a) isnan_ = 1; else m = a > m ? a : m;
+    }
+    for (int k = 1; k < 64; k <<= 1) {
+        const double om = __shfl_xor(m, k, 64);
+        isnan_ |= __shfl_xor(isnan_, k, 64);
+        m = om > m ? om : m;
+    }
+    if ((threadIdx.x & 63) == 0) { wm[threadIdx.x >> 6] = m; wn[threadIdx.x >> 6] = isnan_; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) { m = wm[w] > m ? wm[w] : m; isnan_ |= wn[w]; }
+        gmax[blockIdx.x] = isnan_ ? __builtin_nan("") : m;
+    }
+}
+
 __global__ void scatter_x_kernel(int n, const int* __restrict__ vid, const double* __restrict__ val,
                                  double* __restrict__ x) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)

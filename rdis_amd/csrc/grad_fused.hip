@@ -151,9 +151,10 @@ __device__ __forceinline__ void grad_stage2(const double* __restrict__ x, const 
     }
 }
 
-__global__ void __launch_bounds__(GRAD_LANES)
-grad_fused_kernel(GradTables T, const double* __restrict__ x, const double2* __restrict__ obs, const double* __restrict__ camrec,
-                  double* __restrict__ cstage, double* __restrict__ pstage, double* __restrict__ partial, double* __restrict__ g) {
+// the tiles of a launch's first grid dimension: the one definition of grad_fused_kernel's pass and of its population form's
+__device__ __forceinline__ void grad_fused_tiles(const GradTables& T, const double* __restrict__ x, const double2* __restrict__ obs,
+                                                 const double* __restrict__ camrec, double* __restrict__ cstage, double* __restrict__ pstage,
+                                                 double* __restrict__ partial, double* __restrict__ g) {
     extern __shared__ __align__(16) double smem[];
     double* const rec = smem;                                   // [ncam_cap][GRAD_REC]
     double* const acc = rec + (size_t)T.ncam_cap * GRAD_REC;    // [ncam_cap][9]
@@ -277,9 +278,16 @@ grad_fused_kernel(GradTables T, const double* __restrict__ x, const double2* __r
     }
 }
 
-// what more than one chunk / tile contributed to, in chunk / tile order; zero where no listed factor reads
-__global__ void __launch_bounds__(256)
-grad_combine_kernel(GradTables T, const double* __restrict__ cstage, const double* __restrict__ pstage, double* __restrict__ g) {
+__global__ void __launch_bounds__(GRAD_LANES)
+grad_fused_kernel(GradTables T, const double* __restrict__ x, const double2* __restrict__ obs, const double* __restrict__ camrec,
+                  double* __restrict__ cstage, double* __restrict__ pstage, double* __restrict__ partial, double* __restrict__ g) {
+    grad_fused_tiles(T, x, obs, camrec, cstage, pstage, partial, g);
+}
+
+// what more than one chunk / tile contributed to, in chunk / tile order; zero where no listed factor reads: the one definition of
+// grad_combine_kernel's sums and of its population form's
+__device__ __forceinline__ void grad_combine_items(const GradTables& T, const double* __restrict__ cstage, const double* __restrict__ pstage,
+                                                   double* __restrict__ g) {
     const long long nc9 = 9ll * T.ncs, np3 = 3ll * T.nps, total = nc9 + np3 + T.nz;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         if (i < nc9) {
@@ -293,6 +301,48 @@ grad_combine_kernel(GradTables T, const double* __restrict__ cstage, const doubl
             g[T.zvar[i - nc9 - np3]] = 0.0;
         }
     }
+}
+
+__global__ void __launch_bounds__(256)
+grad_combine_kernel(GradTables T, const double* __restrict__ cstage, const double* __restrict__ pstage, double* __restrict__ g) {
+    grad_combine_items(T, cstage, pstage, g);
+}
+
+// ---- value and gradient of a population X[members][N], the member a grid dimension (rdis_hip.hip: population_grad_enqueue) ----
+// Block (., r) is member first + r: its x is the member's row, its camera records, staging arrays and chunk sums replica r of
+// the launch's (W: GradReplicas, the population's scratch), its gradient row `row0 + r` of G[rows][N].  All of these are
+// wave-uniform: scalar registers.  The statements, and so the bits, are those of the single-x kernels above.
+
+// grad_camera_records_kernel per member: grid (camera blocks / 256, members of the launch)
+__global__ void __launch_bounds__(256)
+population_grad_camera_records_kernel(const double* __restrict__ X, long long N, long long first, const int* __restrict__ cam_blocks, int nblocks,
+                                      double* __restrict__ camrec, long long camrec_stride) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nblocks) return;
+    const long long m = blockIdx.y;
+    const double* x = X + (first + m) * N;
+    const int c = cam_blocks[i];
+    double* r = camrec + m * camrec_stride + (size_t)i * GRAD_REC;
+    store_rotation(x[c], x[c + 1], x[c + 2], r);   // (grad_camera_records_kernel's record)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) r[7 + k] = x[c + 3 + k];
+    r[13] = 0.0;
+}
+
+// grad_fused_kernel per member: grid (tiles, members of the launch), the same dynamic LDS
+__global__ void __launch_bounds__(GRAD_LANES)
+population_grad_fused_kernel(GradTables T, const double* __restrict__ X, long long N, long long first, const double2* __restrict__ obs, GradReplicas W,
+                             double* __restrict__ G, long long row0) {
+    const long long r = blockIdx.y;
+    grad_fused_tiles(T, X + (first + r) * N, obs, W.camrec + r * W.camrec_stride, W.cstage + r * W.cstage_stride, W.pstage + r * W.pstage_stride,
+                     W.partial + r * W.partial_stride, G + (row0 + r) * N);
+}
+
+// grad_combine_kernel per member: grid (item blocks, members of the launch)
+__global__ void __launch_bounds__(256)
+population_grad_combine_kernel(GradTables T, GradReplicas W, double* __restrict__ G, long long N, long long row0) {
+    const long long r = blockIdx.y;
+    grad_combine_items(T, W.cstage + r * W.cstage_stride, W.pstage + r * W.pstage_stride, G + (row0 + r) * N);
 }
 
 #ifdef RDIS_GRAD_STAMPS
@@ -314,6 +364,21 @@ hipError_t grad_fused_launch(hipStream_t s, int grid, size_t dyn, const GradTabl
 }
 hipError_t grad_combine_launch(hipStream_t s, int grid, const GradTables& T, const double* cstage, const double* pstage, double* g) {
     grad_combine_kernel<<<grid, 256, 0, s>>>(T, cstage, pstage, g);
+    return hipGetLastError();
+}
+hipError_t population_grad_camera_records_launch(hipStream_t s, int members_of_launch, const double* X, long long N, long long first, const int* cam_blocks,
+                                                 int nblocks, double* camrec, long long camrec_stride) {
+    const dim3 g((unsigned)((nblocks + 255) / 256), (unsigned)members_of_launch);
+    population_grad_camera_records_kernel<<<g, 256, 0, s>>>(X, N, first, cam_blocks, nblocks, camrec, camrec_stride);
+    return hipGetLastError();
+}
+hipError_t population_grad_fused_launch(hipStream_t s, int members_of_launch, size_t dyn, const GradTables& T, const double* X, long long N, long long first,
+                                        const double2* obs, const GradReplicas& W, double* G, long long row0) {
+    return launch_dyn(population_grad_fused_kernel, dim3((unsigned)T.ntiles, (unsigned)members_of_launch), GRAD_LANES, dyn, s, T, X, N, first, obs, W, G, row0);
+}
+hipError_t population_grad_combine_launch(hipStream_t s, int grid, int members_of_launch, const GradTables& T, const GradReplicas& W, double* G, long long N,
+                                          long long row0) {
+    population_grad_combine_kernel<<<dim3((unsigned)grid, (unsigned)members_of_launch), 256, 0, s>>>(T, W, G, N, row0);
     return hipGetLastError();
 }
 hipError_t population_eval_chunks_launch(hipStream_t s, int grid, int members_of_launch, const ProblemView& P, double* X, long long first, double* XR,

@@ -88,4 +88,22 @@ hipError_t eval_chunks_launch(hipStream_t s, int grid, const ProblemView& P, int
 hipError_t population_eval_chunks_launch(hipStream_t s, int grid, int members_of_launch, const ProblemView& P, double* X, long long first, double* XR,
                                          int nf, const int* fac, double* partial);
 
+// Value and gradient of a population X[members][N] (rdis_hip_population_eval_grad, the fused branch): the member is the grid's
+// second dimension; member first + r of a launch has replica r of the per-call arrays, the list's tables are shared.
+struct GradReplicas {
+    double* camrec;              // [members of the launch][camrec_stride]: the members' camera records
+    double* cstage;              // [...][cstage_stride], pstage: [...][pstage_stride]: the staging arrays
+    double* pstage;
+    double* partial;             // [...][partial_stride]: the chunks' value sums
+    long long camrec_stride, cstage_stride, pstage_stride, partial_stride;   // doubles per replica
+};
+// grad_camera_records_kernel / grad_fused_kernel / grad_combine_kernel with grid (., members_of_launch); G: [rows][N], member
+// first + r writes row row0 + r
+hipError_t population_grad_camera_records_launch(hipStream_t s, int members_of_launch, const double* X, long long N, long long first, const int* cam_blocks,
+                                                 int nblocks, double* camrec, long long camrec_stride);
+hipError_t population_grad_fused_launch(hipStream_t s, int members_of_launch, size_t dyn, const GradTables& T, const double* X, long long N, long long first,
+                                        const double2* obs, const GradReplicas& W, double* G, long long row0);
+hipError_t population_grad_combine_launch(hipStream_t s, int grid, int members_of_launch, const GradTables& T, const GradReplicas& W, double* G, long long N,
+                                          long long row0);
+
 }  // namespace rdis_hip

@@ -1,8 +1,9 @@
 // population_grid.hpp -- the grid of the tiny-component solver's population launch (solver_quad_population.hpp), the members
 // of a launch of the population's evaluation, and the replica of a population launch with point-major components
-// (solver_ptm_population.hpp) with the members of a launch it allows, pure host functions: no HIP call, no plan
-// (tests/cpp/population_tiny_grid_test.cpp, tests/cpp/population_eval_members_test.cpp and
-// tests/cpp/population_ptm_replica_test.cpp run them without a device).
+// (solver_ptm_population.hpp) with the members of a launch it allows, and a member's scratch in a launch of the population's
+// value + gradient, pure host functions: no HIP call, no plan (tests/cpp/population_tiny_grid_test.cpp,
+// tests/cpp/population_eval_members_test.cpp, tests/cpp/population_ptm_replica_test.cpp and
+// tests/cpp/population_grad_members_test.cpp run them without a device).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -46,6 +47,36 @@ inline int64_t ptm_population_replica_bytes(int64_t pm_blocks, int64_t pm_cptr_l
 inline int64_t population_members_per_launch(int64_t members, int64_t budget_bytes, int64_t replica_bytes) {
     const int64_t fit = replica_bytes > 0 ? std::max<int64_t>(1, budget_bytes / replica_bytes) : members;
     return std::min(std::min(fit, members), (int64_t)65535);
+}
+
+// Bytes of one member's scratch in a launch of the population's value + gradient (rdis_hip_population_eval_grad), by the branch
+// rdis_hip_eval_grad takes for the list (grad_branch; the info name of the same name reports it):
+//   fused:    the member's camera records (GRAD_MEMBER_REC doubles a camera block), the list's camera and point staging arrays
+//             (9 and 3 doubles a slot) and its chunk sums -- a count of zero allocates one, as the list's own arrays do;
+//   short:    the per-factor partials gfac[nslots] and the one chunk's sum;
+//   two-pass: gfac[nslots] and the blocks' sums.
+enum GradBranch { GRAD_BRANCH_NONE = 0, GRAD_BRANCH_FUSED = 1, GRAD_BRANCH_SHORT = 2, GRAD_BRANCH_TWO_PASS = 3 };
+constexpr int64_t GRAD_MEMBER_REC = 14;   // grad_fused.hpp: GRAD_REC (rdis_hip.hip asserts them equal)
+struct GradMemberShape {
+    int64_t ncam_blocks = 0, cstage_slots = 0, pstage_slots = 0, nchunks = 0;   // fused
+    int64_t nslots = 0, blocks = 0;                                             // short (blocks not used), two-pass
+};
+inline int64_t grad_member_bytes(int branch, const GradMemberShape& s) {
+    const auto pos = [](int64_t v) { return std::max<int64_t>(v, 0); };
+    const auto one = [](int64_t v) { return std::max<int64_t>(v, 1); };
+    switch (branch) {
+    case GRAD_BRANCH_FUSED: return 8 * (GRAD_MEMBER_REC * pos(s.ncam_blocks) + 9 * one(s.cstage_slots) + 3 * one(s.pstage_slots) + one(s.nchunks));
+    case GRAD_BRANCH_SHORT: return 8 * (pos(s.nslots) + 1);
+    case GRAD_BRANCH_TWO_PASS: return 8 * (pos(s.nslots) + one(s.blocks));
+    default: return 0;
+    }
+}
+// Members of one launch of it: the member is the grid's second dimension (at most 65535) and every member of a launch has
+// `member_bytes` of scratch within `budget_bytes` (the population option grad_workspace_bytes) -- at least one member a launch,
+// whatever the budget.  No bit of a result depends on it.
+inline int64_t grad_members_per_launch(int64_t count, int64_t budget_bytes, int64_t member_bytes) {
+    const int64_t fit = std::max<int64_t>(1, budget_bytes / std::max<int64_t>(member_bytes, 1));
+    return std::max<int64_t>(1, std::min(std::min<int64_t>(count, 65535), fit));
 }
 
 }  // namespace rdis_hip

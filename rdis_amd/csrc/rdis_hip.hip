@@ -31,7 +31,8 @@ static_assert(PLAN_INDEX_EINVAL == RDIS_HIP_EINVAL && PLAN_INDEX_EOVERLAP == RDI
 static_assert(sizeof(IntPair) == sizeof(int2) && offsetof(IntPair, x) == offsetof(int2, x) && offsetof(IntPair, y) == offsetof(int2, y),
               "IntPair is not laid out as int2");
 static_assert(ABI_LDS_MAX_BYTES == LDS_MAX_BYTES && ABI_PIPE_TM == PIPE_TM && OPTION_QUAD_MAX_VARS == QUAD_MAX_VARS &&
-              OPTION_COOP_MAX_WG == COOP_MAX_WG && OPTION_PTM_MAX_GROUP == PTM_WIDE_MAX_GROUP, "a restated constant differs from its original");
+              OPTION_COOP_MAX_WG == COOP_MAX_WG && OPTION_PTM_MAX_GROUP == PTM_WIDE_MAX_GROUP && GRAD_MEMBER_REC == GRAD_REC,
+              "a restated constant differs from its original");
 
 // The one place that knows there are two roundings: a solver's launches in the default rounding (fused multiply-adds), and
 // the set to use (refround_api.hpp).  A plan asks with coop_reference_rounding() or batch_reference_rounding().
@@ -442,6 +443,7 @@ int build_grad_plan(rdis_hip_problem* p, int64_t nf64, const int64_t* fac, GradP
     T.ncs = X.ncs; T.nps = X.nps; T.nz = X.nz;
     T.cs_var = I + X.o_csv; T.cs_ptr = I + X.o_csp; T.ps_var = I + X.o_psv; T.ps_ptr = I + X.o_psp; T.zvar = I + X.o_z;
     G.nf = nf64;
+    G.cstage_slots = X.cstage_slots; G.pstage_slots = X.pstage_slots;
     return 0;
 }
 
@@ -505,6 +507,22 @@ int eval_grad_fused(rdis_hip_problem* p, int64_t nf, const int64_t* fac) {
     return 0;
 }
 
+// the gather lists of all factors, built at their first use and kept by the problem
+int all_factors_v2s(rdis_hip_problem* p, const int** dptr, const int** didx) {
+    rdis_hip_ctx* c = p->ctx;
+    if (!p->have_all_v2s) {
+        int rc;
+        ivec ptr, idx;
+        build_v2s(p, p->F, nullptr, ptr, idx);
+        if ((rc = upload(c, p->all_v2s_ptr, ptr))) return rc;
+        if ((rc = upload(c, p->all_v2s_idx, idx))) return rc;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        p->have_all_v2s = true;
+    }
+    *dptr = p->all_v2s_ptr.as<int>(); *didx = p->all_v2s_idx.as<int>();
+    return 0;
+}
+
 // the two-pass form (nonlinear-product functions; bundle adjustment whose blocks overlap): per-factor partials, then one
 // lane per variable adds its slots in factor-list order
 int eval_grad_two_pass(rdis_hip_problem* p, int64_t nf, const int64_t* fac) {
@@ -516,15 +534,7 @@ int eval_grad_two_pass(rdis_hip_problem* p, int64_t nf, const int64_t* fac) {
     const int *dptr, *didx;
     DevBuf lptr, lidx;
     if (!fac) {
-        if (!p->have_all_v2s) {
-            ivec ptr, idx;
-            build_v2s(p, nf, nullptr, ptr, idx);
-            if ((rc = upload(c, p->all_v2s_ptr, ptr))) return rc;
-            if ((rc = upload(c, p->all_v2s_idx, idx))) return rc;
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            p->have_all_v2s = true;
-        }
-        dptr = p->all_v2s_ptr.as<int>(); didx = p->all_v2s_idx.as<int>();
+        if ((rc = all_factors_v2s(p, &dptr, &didx))) return rc;
     } else {
         ivec ptr, idx;
         build_v2s(p, nf, fac, ptr, idx);
@@ -575,9 +585,18 @@ int eval_grad_short(rdis_hip_problem* p, int64_t nf, const int64_t* fac) {
     return 0;
 }
 
+// the form a list's value + gradient takes (population_grid.hpp: GradBranch): the one rule of rdis_hip_eval_grad and of
+// rdis_hip_population_eval_grad
+int grad_branch_of(const rdis_hip_problem* p, int64_t nf, const int64_t* fac) {
+    if (nf == 0) return GRAD_BRANCH_NONE;
+    if (fused_path(p) && fac && nf <= GRAD_LANES) return GRAD_BRANCH_SHORT;
+    return fused_path(p) ? GRAD_BRANCH_FUSED : GRAD_BRANCH_TWO_PASS;
+}
+
 int eval_grad_on_device(rdis_hip_problem* p, int64_t nf, const int64_t* fac) {
     if (int rc = refuse_exponential(p, nf, fac, "eval_grad")) return rc;
-    if (nf == 0) {
+    const int branch = grad_branch_of(p, nf, fac);
+    if (branch == GRAD_BRANCH_NONE) {
         rdis_hip_ctx* c = p->ctx;
         int rc = ensure(c, p->g_all, (size_t)p->N * sizeof(double));
         if (rc) return rc;
@@ -585,8 +604,8 @@ int eval_grad_on_device(rdis_hip_problem* p, int64_t nf, const int64_t* fac) {
         HIPCHK(c, hipMemsetAsync(p->scalar.p, 0, sizeof(double), c->stream));
         return 0;
     }
-    if (fused_path(p) && fac && nf <= GRAD_LANES) return eval_grad_short(p, nf, fac);
-    return fused_path(p) ? eval_grad_fused(p, nf, fac) : eval_grad_two_pass(p, nf, fac);
+    if (branch == GRAD_BRANCH_SHORT) return eval_grad_short(p, nf, fac);
+    return branch == GRAD_BRANCH_FUSED ? eval_grad_fused(p, nf, fac) : eval_grad_two_pass(p, nf, fac);
 }
 
 }  // namespace
@@ -2092,6 +2111,15 @@ struct rdis_hip_population {
     DevBuf slo, shi;           // [N] each: the sampling intervals of population_sample (population_set_sampling) ...
     bool sampling_set = false; // ... false: the problem's domains
     DevBuf X2, f2, order;      // population_sort: the other buffer of X's size (X and X2 swap roles), the permuted values, order[nmembers] (int64)
+    // value + gradient of a member range (population_grad_enqueue): results and scratch of the population's own
+    DevBuf grad_f, grad_g;     // [rows], [rows][N]: what the last gradient call handed out
+    DevBuf grad_gmax;          // [rows]: population_grad_max of those rows
+    DevBuf grad_ws;            // the replicas of a launch's members (population_grid.hpp: grad_member_bytes each)
+    DevBuf grad_v2s_ptr, grad_v2s_idx;   // the gather lists of the call's explicit list (short and two-pass branch)
+    int64_t grad_workspace_bytes = (int64_t)1 << 30;   // option "grad_workspace_bytes": bounds grad_ws
+    int64_t grad_rows = -1;    // rows of the last gradient call; -1: none yet
+    int64_t grad_per_launch = 0, grad_launches = 0;    // of the last gradient call: members of a launch, kernels launched
+    int grad_branch = 0;       // ... and its form (GradBranch)
     double* row(int64_t s) const { return X.as<double>() + (size_t)s * (size_t)prob->N; }
 };
 
@@ -2315,6 +2343,162 @@ extern "C" int rdis_hip_population_assign_best(rdis_hip_population* pop) {
     return 0;
 }
 
+namespace {
+// Value and gradient of members first0 .. first0 + count - 1 (count >= 1), enqueued on the context's stream: pop->grad_f[count]
+// and pop->grad_g[count][N] on the device.  Nothing is waited for but what grad_plan_for / stage_ids / the upload of an explicit
+// list's gather lists wait for.  The member is the grid's second dimension; the branch is rdis_hip_eval_grad's (grad_branch_of),
+// the kernels its kernels with the member's row for x, so row k has the bits of rdis_hip_eval_grad at X[first0 + k].
+// Per round of R members (population_grid.hpp) every member has a replica of the per-call arrays in pop->grad_ws.  A replica
+// serves another member in the next round, and every entry a round reads it has written itself:
+//   fused:    the camera records are rebuilt before EVERY round; the fused kernel writes every cstage / pstage slot and every
+//             chunk's sum before the combine kernel and the final sum read them (each slot belongs to one (block, chunk / tile));
+//   short, two-pass: the gather lists name only slots of listed factors, which the round's partials have written.
+// The scratch is the population's: X, f, eval_valid and best, the problem's x, scalar, g_all, camrec, partial, gfac and xrot and
+// the cached GradPlan's own staging arrays are not written (its tables are read).
+int population_grad_enqueue(rdis_hip_population* pop, int64_t first0, int64_t count, int64_t nf, const int64_t* fac) {
+    rdis_hip_problem* p = pop->prob;
+    rdis_hip_ctx* c = p->ctx;
+    const int64_t N = p->N;
+    int rc;
+    if ((rc = refuse_exponential(p, nf, fac, "population_eval_grad"))) return rc;
+    const int branch = grad_branch_of(p, nf, fac);
+    // what the branch needs of the list, before anything of the last call is overwritten
+    GradPlan* G = nullptr;
+    GradMemberShape shape;
+    size_t dyn = 0;
+    const int *dfac = nullptr, *dptr = nullptr, *didx = nullptr;
+    int blocks = 0;
+    if (branch == GRAD_BRANCH_FUSED) {
+        if ((rc = grad_plan_for(p, nf, fac, &G))) return rc;
+        dyn = grad_lds_bytes(G->T.ncam_cap);
+        if (dyn > (size_t)160 * 1024) return fail(c, RDIS_HIP_EINVAL, "population_eval_grad: a tile's cameras do not fit the LDS");
+        shape.ncam_blocks = p->ncam_blocks; shape.cstage_slots = G->cstage_slots; shape.pstage_slots = G->pstage_slots; shape.nchunks = G->T.nchunks;
+    } else if (branch != GRAD_BRANCH_NONE) {
+        if ((rc = stage_ids(p, nf, fac, p->F, &dfac))) return rc;
+        blocks = branch == GRAD_BRANCH_SHORT ? 1 : grid_for(c, nf, 256);   // a member's value partials: the one chunk's, or eval_grad_two_pass's blocks
+        shape.nslots = p->nslots(); shape.blocks = blocks;
+        if (!fac) {
+            if ((rc = all_factors_v2s(p, &dptr, &didx))) return rc;
+        } else {   // built once per call, kept by the population: the launches below read them after this call has returned
+            ivec ptr, idx;
+            build_v2s(p, nf, fac, ptr, idx);
+            if ((rc = ensure(c, pop->grad_v2s_ptr, ptr.size() * sizeof(int))) || (rc = ensure(c, pop->grad_v2s_idx, idx.size() * sizeof(int)))) return rc;
+            HIPCHK(c, hipMemcpyAsync(pop->grad_v2s_ptr.p, ptr.data(), ptr.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+            if (!idx.empty()) HIPCHK(c, hipMemcpyAsync(pop->grad_v2s_idx.p, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));   // (the host images go out of scope)
+            dptr = pop->grad_v2s_ptr.as<int>(); didx = pop->grad_v2s_idx.as<int>();
+        }
+    }
+    const int64_t mbytes = grad_member_bytes(branch, shape);
+    const int64_t R = branch == GRAD_BRANCH_NONE ? count : grad_members_per_launch(count, pop->grad_workspace_bytes, mbytes);
+    if ((rc = ensure(c, pop->grad_f, (size_t)count * sizeof(double)))) return rc;
+    if ((rc = ensure(c, pop->grad_g, (size_t)count * (size_t)N * sizeof(double)))) return rc;
+    if (branch != GRAD_BRANCH_NONE && (rc = ensure(c, pop->grad_ws, (size_t)R * (size_t)mbytes))) return rc;
+    pop->grad_rows = count; pop->grad_per_launch = R; pop->grad_launches = 0; pop->grad_branch = branch;
+    double *X = pop->X.as<double>(), *F_out = pop->grad_f.as<double>(), *G_out = pop->grad_g.as<double>(), *W = pop->grad_ws.as<double>();
+    if (branch == GRAD_BRANCH_NONE) {
+        HIPCHK(c, hipMemsetAsync(F_out, 0, (size_t)count * sizeof(double), c->stream));
+        if (N > 0) HIPCHK(c, hipMemsetAsync(G_out, 0, (size_t)count * (size_t)N * sizeof(double), c->stream));
+        return 0;
+    }
+    const ProblemView V = p->view();
+    int64_t launches = 0;
+    if (branch == GRAD_BRANCH_FUSED) {
+        const GradTables& T = G->T;
+        GradReplicas rep;
+        rep.camrec_stride = GRAD_REC * p->ncam_blocks; rep.cstage_stride = 9ll * std::max(G->cstage_slots, 1);
+        rep.pstage_stride = 3ll * std::max(G->pstage_slots, 1); rep.partial_stride = T.nchunks;
+        rep.camrec = W; rep.cstage = rep.camrec + R * rep.camrec_stride; rep.pstage = rep.cstage + R * rep.cstage_stride;
+        rep.partial = rep.pstage + R * rep.pstage_stride;
+        const long long items = 9ll * T.ncs + 3ll * T.nps + T.nz;
+        for (int64_t k = 0; k < count; k += R) {   // (rounds on one stream: the next takes the replicas when this one is done)
+            const int ns = (int)std::min<int64_t>(R, count - k);
+            const int64_t first = first0 + k;
+            // the records of THIS round's members: the replicas held another round's until now
+            HIPCHK(c, population_grad_camera_records_launch(c->stream, ns, X, N, first, p->cam_blocks.as<int>(), (int)p->ncam_blocks, rep.camrec, rep.camrec_stride));
+            HIPCHK(c, population_grad_fused_launch(c->stream, ns, dyn, T, X, N, first, p->obs.as<double2>(), rep, G_out, k));
+            if (items > 0) HIPCHK(c, population_grad_combine_launch(c->stream, grid_for(c, items, 256), ns, T, rep, G_out, N, k));
+            // (population_final_sum_kernel adds a member's nchunks partials by final_sum_of, final_sum_kernel's own sum: the same order)
+            population_final_sum_kernel<<<ns, 256, 0, c->stream>>>(T.nchunks, rep.partial, k, F_out);
+            HIPCHK(c, hipGetLastError());
+            launches += items > 0 ? 4 : 3;
+        }
+    } else {
+        const long long nslots = p->nslots();
+        double *gfac = W, *part = W + R * nslots;   // [R][nslots], [R][blocks]
+        for (int64_t k = 0; k < count; k += R) {
+            const int ns = (int)std::min<int64_t>(R, count - k);
+            const int64_t first = first0 + k;
+            if (branch == GRAD_BRANCH_SHORT) {
+                population_partials_kernel<<<dim3((unsigned)grid_for(c, nf, 256), (unsigned)ns), 256, 0, c->stream>>>(V, X, first, (int)nf, dfac, gfac, nslots);
+                HIPCHK(c, hipGetLastError());
+            } else {
+                const dim3 grid((unsigned)blocks, (unsigned)ns);
+                if (p->kind == KIND_BA) population_eval_sum_grad_kernel<KIND_BA><<<grid, 256, 0, c->stream>>>(V, X, first, (int)nf, dfac, gfac, nslots, part);
+                else population_eval_sum_grad_kernel<KIND_NLP><<<grid, 256, 0, c->stream>>>(V, X, first, (int)nf, dfac, gfac, nslots, part);
+                HIPCHK(c, hipGetLastError());
+            }
+            population_gather_grad_kernel<<<dim3((unsigned)grid_for(c, N, 256), (unsigned)ns), 256, 0, c->stream>>>((int)N, dptr, didx, gfac, nslots, G_out, k);
+            HIPCHK(c, hipGetLastError());
+            if (branch == GRAD_BRANCH_SHORT) {   // the value by the chunk kernel, as eval_grad_short takes it
+                HIPCHK(c, population_eval_chunks_launch(c->stream, 1, ns, V, X, first, nullptr, (int)nf, dfac, part));
+                ++launches;
+            }
+            population_final_sum_kernel<<<ns, 256, 0, c->stream>>>(blocks, part, k, F_out);
+            HIPCHK(c, hipGetLastError());
+            launches += 3;
+        }
+    }
+    pop->grad_launches = launches;
+    return 0;
+}
+}  // namespace
+
+extern "C" int rdis_hip_population_eval_grad_device(rdis_hip_population* pop, int64_t first, int64_t count, int64_t nf, const int64_t* fac, void** f_dev,
+                                                    void** g_dev) {
+    if (!pop || !f_dev || !g_dev) return RDIS_HIP_EINVAL;
+    rdis_hip_problem* p = pop->prob;
+    rdis_hip_ctx* c = p->ctx;
+    int rc = population_range(pop, "population_eval_grad", first, count, p->N, nullptr);
+    if (!rc) rc = check_list(p, nf, fac);
+    if (rc) return rc;
+    USE_DEVICE(c);
+    if (count > 0 && (rc = population_grad_enqueue(pop, first, count, nf, fac))) return rc;   // (count == 0: nothing happens)
+    *f_dev = pop->grad_f.p;
+    *g_dev = pop->grad_g.p;
+    return 0;
+}
+
+extern "C" int rdis_hip_population_eval_grad(rdis_hip_population* pop, int64_t first, int64_t count, int64_t nf, const int64_t* fac, double* f, double* g) {
+    if (!pop || (count > 0 && (!f || !g))) return RDIS_HIP_EINVAL;
+    void *fd, *gd;
+    int rc = rdis_hip_population_eval_grad_device(pop, first, count, nf, fac, &fd, &gd);
+    if (rc || count == 0) return rc;
+    rdis_hip_ctx* c = pop->prob->ctx;
+    HIPCHK(c, hipMemcpyAsync(f, fd, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (pop->prob->N > 0) HIPCHK(c, hipMemcpyAsync(g, gd, (size_t)count * (size_t)pop->prob->N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int rdis_hip_population_grad_max(rdis_hip_population* pop, double* gmax, void** gmax_dev) {
+    if (!pop) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = pop->prob->ctx;
+    if (pop->grad_rows < 0)
+        return fail(c, RDIS_HIP_EINVAL, "population_grad_max: evaluate the gradient first (rdis_hip_population_eval_grad or _eval_grad_device)");
+    USE_DEVICE(c);
+    const int64_t rows = pop->grad_rows;
+    if (int rc = ensure(c, pop->grad_gmax, (size_t)rows * sizeof(double))) return rc;
+    population_grad_max_kernel<<<(unsigned)rows, 256, 0, c->stream>>>((long long)pop->prob->N, pop->grad_g.as<double>(), pop->grad_gmax.as<double>());
+    HIPCHK(c, hipGetLastError());
+    if (gmax_dev) *gmax_dev = pop->grad_gmax.p;
+    if (gmax) {
+        HIPCHK(c, hipMemcpyAsync(gmax, pop->grad_gmax.p, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
 extern "C" int rdis_hip_population_set_option(rdis_hip_population* pop, const char* name, int64_t value) {
     if (!pop || !name) return RDIS_HIP_EINVAL;
     rdis_hip_ctx* c = pop->prob->ctx;
@@ -2329,8 +2513,16 @@ extern "C" int rdis_hip_population_set_option(rdis_hip_population* pop, const ch
         }
     } else if (n == "eval_batched") {
         pop->eval_batched = value != 0;
+    } else if (n == "grad_workspace_bytes") {
+        if (value < 0) return fail(c, RDIS_HIP_EINVAL, "population_set_option: grad_workspace_bytes must not be negative");
+        USE_DEVICE(c);
+        pop->grad_workspace_bytes = value;
+        if (pop->grad_ws.bytes > (size_t)value) {   // scratch beyond the new bound goes (the next gradient call takes what it needs)
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            pop->grad_ws.release();
+        }
     } else {
-        return fail(c, RDIS_HIP_EINVAL, "population_set_option: unknown option '" + n + "' (eval_workspace_bytes, eval_batched)");
+        return fail(c, RDIS_HIP_EINVAL, "population_set_option: unknown option '" + n + "' (eval_workspace_bytes, eval_batched, grad_workspace_bytes)");
     }
     return 0;
 }
@@ -2341,7 +2533,11 @@ extern "C" int rdis_hip_population_get_info(rdis_hip_population* pop, const char
     if (n == "eval_members_per_launch") *value = pop->eval_per_launch;
     else if (n == "eval_launches") *value = pop->eval_launches;
     else if (n == "eval_valid") *value = pop->eval_valid ? 1 : 0;
-    else return fail(pop->prob->ctx, RDIS_HIP_EINVAL, "population_get_info: unknown name '" + n + "' (eval_members_per_launch, eval_launches, eval_valid)");
+    else if (n == "grad_members_per_launch") *value = pop->grad_per_launch;
+    else if (n == "grad_launches") *value = pop->grad_launches;
+    else if (n == "grad_branch") *value = pop->grad_branch;
+    else return fail(pop->prob->ctx, RDIS_HIP_EINVAL, "population_get_info: unknown name '" + n + "' (eval_members_per_launch, eval_launches, eval_valid, "
+                                                     "grad_members_per_launch, grad_launches, grad_branch)");
     return 0;
 }
 

@@ -2,7 +2,7 @@
 """Multi-start solves measured: rdis_hip_plan_solve_starts against the same starts solved one by one.
 
   python tools/bench_multistart.py            # both steps, one JSON line
-  python tools/bench_multistart.py --step config3|config5s|config2|population|population-nlp|population-tiny|population-eval|population-point-major|population-halving   # one step, in this process
+  python tools/bench_multistart.py --step config3|config5s|config2|population|population-nlp|population-tiny|population-eval|population-point-major|population-halving|population-grad   # one step, in this process
 
 config3   BASELINE config 3 (ladybug 5 cameras / 30 points, one component): 320 one-ulp starts -- those of the end-value fixture,
           tests/golden/end_values.json -- in one call, and the same 320 by set_start / solve / fetch on the same plan.
@@ -41,6 +41,11 @@ population-halving  ladybug 5 / 30, 256 members DRAWN ON THE DEVICE from the sam
           whether (a) and (b) end with the same order and the same bytes in the surviving rows, the best value of (a) and (c).  Then the
           wall time of sort alone (between two synchronisations) at 256, 4096 and 65535 members, and of sample of 256 whole members of
           full ladybug against the host's draw + set_x of the same 48.7 MB.  Asked for by name, like population-point-major.
+population-grad  the members' gradients: 256 members of ladybug 5 / 30 and 64 members of full ladybug from the sampling intervals, after one
+          camera step.  The wall time of rdis_hip_population_eval_grad_device + one synchronisation (the member a grid dimension: three
+          or four launches), of the member-by-member route -- population_assign(s) + rdis_hip_eval_grad_device for every s, then one
+          synchronisation: code the batched path does not touch -- and of one member's rdis_hip_eval_grad_device; the launches; whether
+          f and g have the same bytes both ways.  Asked for by name, like population-point-major.
 Every step runs in a child process under a time limit of its own; a step that fails ends the run.  Wall times are the median of
 `--repeats` calls after one warm-up call; kernel_ms is rdis_hip_plan_last_kernel_ms of the last call."""
 import argparse
@@ -56,7 +61,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 STEP_LIMIT_S = {"config3": 240, "config5s": 240, "config2": 240, "population": 240, "population-nlp": 240, "population-tiny": 240, "population-eval": 240,
-                "population-point-major": 420, "population-halving": 420}
+                "population-point-major": 420, "population-halving": 420, "population-grad": 240}
 STEPS = ("config3", "config5s", "config2", "population", "population-nlp", "population-tiny", "population-eval")
 
 
@@ -478,6 +483,66 @@ def measure_population_eval(repeats):
             "ladybug_full": shape(P.load_bal(), 64, lds, {"population_tiny": 1})}
 
 
+def measure_population_grad(repeats):
+    """every member's value and gradient in one call (rdis_hip_population_eval_grad_device) against the member-by-member route
+    (population_assign(s) + rdis_hip_eval_grad_device for every s -- code the batched path does not touch), device forms
+    followed by one synchronisation"""
+    from rdis_amd import capi, problems as P
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    from ba_multistart import sampling_intervals
+    ctx = capi.Context(0)
+
+    def median_ms(call):
+        call()                                             # (warm-up; a list's tables are built at its first use)
+        tt = []
+        for _ in range(repeats):
+            t = time.perf_counter()
+            call()
+            ctx.synchronize()
+            tt.append(time.perf_counter() - t)
+        return 1e3 * float(np.median(tt))
+
+    def shape(pp, members, cam_opts):
+        cams, pts = P.ba_alternation_plans(pp)
+        lo, hi = sampling_intervals(pp)
+        g = capi.Problem(ctx, pp)
+        plan = capi.Plan(g, *cams)
+        for k, v in cam_opts.items():
+            plan.set_option(k, v)
+        pop = capi.Population(g, x=np.random.default_rng(0).uniform(lo, hi, size=(members, pp.nvars)))
+        plan.solve_population(pop, 25, 3e-8)               # one camera step: every member its own cameras
+        ctx.synchronize()
+
+        def one_by_one():
+            for s in range(members):
+                pop.assign(s)
+                g.eval_grad_device()
+
+        out = {"members": members, "factors": int(pp.nfac), "variables": int(pp.nvars)}
+        out["batched_wall_ms"] = median_ms(pop.eval_grad_device)
+        out["batched_launches"] = pop.info("grad_launches")
+        out["members_per_launch"] = pop.info("grad_members_per_launch")
+        out["grad_branch"] = pop.info("grad_branch")
+        out["member_by_member_wall_ms"] = median_ms(one_by_one)
+        pop.assign(0)
+        out["one_member_wall_ms"] = median_ms(g.eval_grad_device)
+        out["speedup"] = out["member_by_member_wall_ms"] / out["batched_wall_ms"]
+        out["batched_in_single_calls"] = out["batched_wall_ms"] / out["one_member_wall_ms"]
+        f, gr = pop.eval_grad()
+        same = True
+        for s in range(members):
+            pop.assign(s)
+            fs, gs = g.eval_grad()
+            same = same and np.float64(fs).tobytes() == f[s].tobytes() and gs.tobytes() == gr[s].tobytes()
+        out["f_and_g_bytes_equal"] = bool(same)
+        for o in (plan, pop, g):
+            o.close()
+        return out
+
+    return {"ladybug_5_30": shape(P.load_bal(ncams=5, npts=30), 256, {}),
+            "ladybug_full": shape(P.load_bal(), 64, {"coop_min_factors": 0, "coop_group_min_factors": 0})}
+
+
 def measure_population_halving(repeats, members=256, rounds=4):
     """successive halving on the device against the way without sample / sort / a member range, and the three pieces alone"""
     from rdis_amd import capi, problems as P
@@ -617,6 +682,8 @@ def step(name, repeats):
         return measure_population_halving(repeats)
     if name == "population-eval":
         return measure_population_eval(repeats)
+    if name == "population-grad":
+        return measure_population_grad(repeats)
     if name == "population-tiny":
         return measure_population_tiny(repeats)
     if name == "population-point-major":
