@@ -120,6 +120,134 @@ def test_lm_pixel_residual_model_full_ladybug(gctx):
     assert abs(o.eval() - r.fret) <= 1e-12 * r.fret and abs(accepted[-1, 2] - r.fret) <= 1e-12 * r.fret
 
 
+# ---- reduced systems beyond ladybug's: more than 512 unknowns --------------------------------------------------------
+# ladybug has at most 49 cameras: a padded reduced system Mp of 64 or 448.  The tests below reach what lm_solver.hip
+# does only for larger ones, on make_synthetic_ba blocks in which every point is seen by a cyclic window of K cameras
+# (the reduced matrix couples different cameras: the off-block sums of k_trail, k_trsv and k_trsv_left multiply
+# non-zeros).  Against the parent commit's run of this file (5 s on an MI355X host) they add 13 s, nearly all of it the
+# CPU oracle: 3.5 s a case at 120 cameras, 1.3 s at 58 and 64, 0.4 s for the sub-block, 0.01 s for a boundary solve.
+def _converged_at(ro):
+    """index of the first history entry whose trial objective equals the current one to 1e-11 (where _compare stops
+    comparing histories), or len(history)"""
+    fcur = ro.finit
+    for i, (_, _, ft, ok) in enumerate(ro.history):
+        if abs(ft - fcur) <= 1e-11 * abs(fcur):
+            return i
+        if ok:
+            fcur = ft
+    return len(ro.history)
+
+
+def _deviations(r, ro):
+    n = min(len(r.history), len(ro.history))
+    h, oh = np.asarray(r.history, dtype=np.float64)[:n, :3], np.array(ro.history, dtype=np.float64)[:n, :3]
+    return (float(np.max(np.abs(h - oh) / np.abs(oh))), float(np.max(np.abs(r.x - ro.x)) / (1.0 + np.max(np.abs(ro.x)))),
+            abs(r.fret - ro.fret) / abs(ro.fret))
+
+
+@pytest.mark.parametrize("model", [1, 2])
+@pytest.mark.parametrize("nc,npt,k,iters", [(58, 400, 6, 8), (64, 400, 6, 8), (120, 700, 6, 4)])
+def test_lm_steps_beyond_512_unknowns(nc, npt, k, iters, model, gctx):
+    """Step by step against the dense oracle, dense (schur 1) and block-sparse (schur 2) Schur product, and the two
+    against each other (the criteria of test_sparse_and_dense_schur_products_agree).
+    58 cameras: M = 522, Mp = 576 -- 54 padding rows (unit diagonal from k_sfinish / k_sinit, the padding reset of k_rhs),
+        and k_trsv's strided loop "more unknowns than threads" (Mp > TRSV_THREADS = 512) runs, one stride.
+    64 cameras: M = Mp = 576 -- no padding at all (9 * 64 is a multiple of 64): no row takes the `else` of k_sfinish /
+        k_sinit, and k_panel's right-hand-side row Mp directly follows the last real row.
+    120 cameras: M = 1080, Mp = 1088 -- k_trsv's strided loop takes two strides (Mp >= 1088); 17 tiles: SK =
+        2048 / 153 = 13 (ladybug's 49 cameras: 64), a k_syrk grid of 17 x 17 tile pairs by 13 slices.
+    The comparison is of the whole history (the oracle never converges within the iteration limit) and includes
+    re-damped solves (the oracle rejects at least one step); tests/test_lm_oracle_cpu.py pins that the oracle's
+    own sensitivity to rounding is 100 times below _compare's tolerances on these problems.
+    Observed on an MI355X, largest deviation from the oracle over both Schur paths (history, x, fret):
+     58 cameras: model 1  8.8e-13, 1.2e-16, 7.7e-14;  model 2  2.1e-12, 3.1e-14, 2.8e-14
+     64 cameras: model 1  1.3e-12, 3.4e-16, 2.1e-13;  model 2  3.7e-12, 2.9e-14, 9.4e-14
+    120 cameras: model 1  1.0e-13, 2.0e-16, 1.1e-14;  model 2  8.0e-13, 3.7e-14, 7.8e-14
+    With k_trsv's strided loop made to skip its second stride the two 120-camera cases fail and the others pass.
+    Time: with the other tests of this section the file takes 18 s on an MI355X host where the parent commit's took 5 s."""
+    pp = P.make_synthetic_ba(1, nc, npt, obs_per_pt=k, first_comp=7)
+    ro = LM.lm_optimize(O.OracleProblem(pp, emulate_stale_cache=False), maxiters=iters, model=model)
+    assert _converged_at(ro) == len(ro.history) and ro.stop == 3      # nothing truncated: _compare sees every solve
+    assert any(not h[3] for h in ro.history)                           # a rejected step: the re-damped solve is compared
+    res = {}
+    for schur in (1, 2):
+        r = res[schur] = capi.Problem(gctx, pp).lm_optimize(maxiters=iters, model=model, schur=schur)
+        print("LM %d cameras (Mp %d), model %d, schur %d against the oracle: history %.1e, x %.1e, fret %.1e" % (
+            (nc, (9 * nc + 63) // 64 * 64, model, schur) + _deviations(r, ro)))
+        _compare(r, ro)
+        assert r.camera_blocks == nc and r.point_blocks == npt
+    a, b = res[1], res[2]
+    assert len(a.history) == len(b.history) and np.array_equal(a.history[:, 3], b.history[:, 3])
+    assert np.max(np.abs(a.history[:, 2] - b.history[:, 2]) / np.abs(a.history[:, 2])) <= 1e-9
+
+
+@pytest.mark.parametrize("schur", [1, 2])
+@pytest.mark.parametrize("nc", [455, 456])
+def test_lm_linear_solve_at_the_trsv_boundary(nc, schur, gctx):
+    """The first damped solve on 455 and 456 cameras x 700 points, 8 cameras a point (5600 factors): the residual of the
+    damped normal equations (J^T J + mu I) dp + grad, formed without a matrix on the CPU as in
+    test_lm_full_ladybug_properties, within that test's 1e-9 |grad|.
+    455 cameras: M = 4095, Mp = 4096 = TRSV_MAX -- the last size k_trsv takes (`D.Mp <= TRSV_MAX`), zs[4096] full.
+    456 cameras: M = 4104, Mp = 4160 -- the first size of k_trsv_left, which no other test runs.
+    Both: 65 tiles, so SK = 2048 / 2145 = 0 clamped to 1 and k_syrk's grid is 4225 x 1; two or three of the
+    cameras have 1 to 3 factors (the fewest: 1): k_cam with fewer rows than one MFMA step of four.
+    Observed on an MI355X, |res| / |grad|: 455 cameras (mu 511.968) dense 2.02e-15, sparse 1.99e-15; 456 cameras
+    (mu 286.447) dense 1.72e-15, sparse 1.72e-15.  With one row block left out of k_trsv_left's sums, or the second
+    stride out of k_trsv's loop, the cases of that kernel fail."""
+    pp = P.make_synthetic_ba(1, nc, 700, obs_per_pt=8, first_comp=11)
+    pp.lo[:], pp.hi[:] = -np.inf, np.inf                          # (the final clamp is not part of the linear step)
+    assert 1 <= np.min(np.bincount(pp.cam_vid0 // 9, minlength=nc)) < 4    # a camera of fewer rows than one MFMA step
+    r1 = capi.Problem(gctx, pp).lm_optimize(maxiters=1, model=1, schur=schur)
+    assert r1.camera_blocks == nc and r1.point_blocks == 700
+    assert r1.history[-1, 3] == 1
+    mu = r1.history[-1, 0]                                        # the damping of the accepted solve
+    o = O.OracleProblem(pp, emulate_stale_cache=False)
+    grad = o.gradient()
+    dp = r1.x - pp.x0
+    E, G = o.eval_each(np.arange(pp.nfac)), o.grad_each_ba(np.arange(pp.nfac))
+    Jd = np.zeros(pp.nvars)
+    vids = np.concatenate([pp.cam_vid0[:, None] + np.arange(9), pp.pt_vid0[:, None] + np.arange(3)], axis=1)
+    rows = G / np.sqrt(2.0 * E)[:, None]
+    np.add.at(Jd, vids.reshape(-1), (rows * np.sum(rows * dp[vids], axis=1)[:, None]).reshape(-1))
+    res = Jd + mu * dp + grad
+    print("LM %d cameras (Mp %d, %s), schur %d: mu %.6g, |res| / |grad| = %.2e" % (
+        nc, (9 * nc + 63) // 64 * 64, "k_trsv" if nc == 455 else "k_trsv_left", schur, mu, np.linalg.norm(res) / np.linalg.norm(grad)))
+    assert np.linalg.norm(res) <= 1e-9 * np.linalg.norm(grad)
+
+
+@pytest.mark.parametrize("model", [1, 2])
+def test_lm_sub_block_at_64_cameras(model, gctx):
+    """test_lm_sub_block_with_constants beyond 512 unknowns: of 64 cameras x 400 points (6 cameras a point) all cameras
+    but two and the first 200 points are free, the factors of those points listed, and of one free camera's listed
+    factors all but one dropped.  62 active cameras: M = 558, Mp = 576 (k_trsv's strided loop, 18 padding rows), active
+    blocks numbered differently from the problem's (cam_id / fci skip the constant cameras; the listed factors of the
+    constant cameras have fci = -1, so k_z stops after T_j and k_back skips them), and k_cam on a camera of a single
+    Jacobian row (model 1) or two (model 2).
+    Observed on an MI355X, largest deviation from the oracle (history, x, fret):
+    model 1  8.5e-11, 2.1e-13, 7.3e-11 (11 solves, 3 rejected);  model 2  4.4e-12, 5.8e-13, 4.5e-13 (10 solves, 2 rejected);
+    the oracle's own sensitivity to one-ulp changes of the start here: 3.7e-11, 8.2e-14, 3.6e-11 and 9.4e-12, 5.1e-13, 2.8e-13."""
+    nc, npt = 64, 400
+    pp = P.make_synthetic_ba(1, nc, npt, obs_per_pt=6, first_comp=7)
+    const_cams, lone = (5, 40), 17
+    free = np.concatenate([np.setdiff1d(np.arange(9 * nc), np.concatenate([9 * c + np.arange(9) for c in const_cams])),
+                           9 * nc + np.arange(3 * (npt // 2))]).astype(np.int64)
+    fac = np.where(pp.pt_vid0 < 9 * nc + 3 * (npt // 2))[0].astype(np.int64)
+    of_lone = fac[pp.cam_vid0[fac] == 9 * lone]
+    assert len(of_lone) > 1
+    fac = np.setdiff1d(fac, of_lone[1:])                          # camera `lone` keeps exactly one listed factor
+    assert np.sum(pp.cam_vid0[fac] == 9 * lone) == 1
+    g = capi.Problem(gctx, pp)
+    r = g.lm_optimize(free, fac, maxiters=8, model=model)
+    ro = LM.lm_optimize(O.OracleProblem(pp, emulate_stale_cache=False), free, fac, maxiters=8, model=model)
+    print("LM sub-block of 64 cameras, model %d against the oracle: history %.1e, x %.1e, fret %.1e (%d of %d solves compared)" % (
+        (model,) + _deviations(r, ro) + (_converged_at(ro), len(ro.history))))
+    _compare(r, ro)
+    assert r.camera_blocks == nc - 2 and r.point_blocks == npt // 2
+    x_all = g.get_x()
+    rest = np.setdiff1d(np.arange(pp.nvars), free)
+    assert np.array_equal(x_all[rest], pp.x0[rest]) and np.array_equal(x_all[free], r.x)   # constants untouched, block left assigned
+
+
 def test_lm_argument_errors(gctx):
     q = P.load_poly()
     with pytest.raises(capi.RdisHipError):
