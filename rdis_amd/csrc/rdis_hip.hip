@@ -31,8 +31,8 @@ static_assert(PLAN_INDEX_EINVAL == RDIS_HIP_EINVAL && PLAN_INDEX_EOVERLAP == RDI
 static_assert(sizeof(IntPair) == sizeof(int2) && offsetof(IntPair, x) == offsetof(int2, x) && offsetof(IntPair, y) == offsetof(int2, y),
               "IntPair is not laid out as int2");
 static_assert(ABI_LDS_MAX_BYTES == LDS_MAX_BYTES && ABI_PIPE_TM == PIPE_TM && OPTION_QUAD_MAX_VARS == QUAD_MAX_VARS &&
-              OPTION_COOP_MAX_WG == COOP_MAX_WG && OPTION_PTM_MAX_GROUP == PTM_WIDE_MAX_GROUP && GRAD_MEMBER_REC == GRAD_REC,
-              "a restated constant differs from its original");
+              OPTION_COOP_MAX_WG == COOP_MAX_WG && OPTION_PTM_MAX_GROUP == PTM_WIDE_MAX_GROUP && GRAD_MEMBER_REC == GRAD_REC &&
+              REPLICA_PT_REC == PT_REC, "a restated constant differs from its original");
 
 // The one place that knows there are two roundings: a solver's launches in the default rounding (fused multiply-adds), and
 // the set to use (refround_api.hpp).  A plan asks with coop_reference_rounding() or batch_reference_rounding().
@@ -1918,7 +1918,6 @@ extern "C" int rdis_hip_plan_fetch(rdis_hip_plan* L, double* x_out, double* fret
 // =====================================================================================
 namespace {
 constexpr size_t STARTS_STAGE_MAX_BYTES = 64u << 20;   // the caller's starts go through pinned memory up to this size
-constexpr int64_t STARTS_MAX_PER_LAUNCH = 65535;       // (the start is the grid's second dimension)
 
 // why a plan cannot be solved from many starts yet.  Two kinds of plan can: every component on the LDS-resident solver (bundle
 // adjustment), or a nonlinear-product problem with every component on the plain batch solver -- *plain_solver says which
@@ -1997,6 +1996,47 @@ int fetch_many(rdis_hip_plan* L, bool population, double* x_out, double* fret, d
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
+
+// The per-call buffers of both solve entries, grown where an earlier call left them too small, in this order: the launch's
+// replicas (ms_work; ms_dir, which is zeroed here once -- the kernel leaves what it wrote zero again), the tiny-component launch's
+// queue counters (0 bytes: it does not run), the start rows and the outputs of the call's n starts or members.
+int grow_solve_buffers(rdis_hip_plan* L, size_t work_bytes, size_t dir_bytes, size_t queue_bytes, int64_t n) {
+    rdis_hip_ctx* c = L->prob->ctx;
+    int rc = 0;
+    if (L->ms_work.bytes < work_bytes) rc = plan_alloc(L, L->ms_work, work_bytes);
+    if (!rc && L->ms_dir.bytes < dir_bytes) {
+        rc = plan_alloc(L, L->ms_dir, dir_bytes);
+        if (!rc) HIPCHK(c, hipMemsetAsync(L->ms_dir.p, 0, L->ms_dir.bytes, c->stream));
+    }
+    if (!rc && L->ms_queue.bytes < queue_bytes) rc = plan_alloc(L, L->ms_queue, queue_bytes);
+    const size_t in_bytes = (size_t)n * (size_t)L->nfree * sizeof(double);
+    if (!rc && L->ms_in.bytes < in_bytes) rc = plan_alloc(L, L->ms_in, in_bytes);
+    if (!rc && L->ms_out.bytes < L->ms_out_bytes(n)) rc = plan_alloc(L, L->ms_out, L->ms_out_bytes(n));
+    return rc;
+}
+
+// behind the last launch of either entry: the end of the stretch rdis_hip_plan_last_kernel_ms reports ...
+int end_timed_launches(rdis_hip_plan* L) {
+    rdis_hip_problem* p = L->prob;
+    rdis_hip_ctx* c = p->ctx;
+    HIPCHK(c, hipEventRecord(p->ev1, c->stream));
+    L->timed = true;
+    p->last_timed_plan = L;
+    return 0;
+}
+// ... and what fetch_many and plan_get_info read of the call: n rows, R of them a launch, the launches counted in last_launches
+void note_many_solve(rdis_hip_plan* L, bool population, int64_t n, int64_t R) {
+    L->ms_population = population;
+    L->ms_n = n;
+    L->ms_per_launch = R;
+    L->ms_launches = L->last_launches;
+}
+// a plan without components: nothing is launched, and n rows of nothing can be fetched
+void note_empty_solve(rdis_hip_plan* L, bool population, int64_t n) {
+    L->last_launches = 0;
+    L->timed = false;
+    note_many_solve(L, population, n, n);
+}
 }  // namespace
 
 extern "C" int rdis_hip_plan_solve_starts(rdis_hip_plan* L, int64_t nstarts, const double* x_starts, int32_t maxiters, double ftol) {
@@ -2012,22 +2052,13 @@ extern "C" int rdis_hip_plan_solve_starts(rdis_hip_plan* L, int64_t nstarts, con
     if (int rc = refuse_late_exponential(L, "plan_solve_starts")) return rc;
     bool plain = false;
     if (int rc = starts_refusal(L, "plan_solve_starts", &plain)) return rc;
-    if (L->ncomp == 0) { L->ms_population = false; L->ms_n = nstarts; L->ms_per_launch = nstarts; L->ms_launches = 0; L->last_launches = 0; L->timed = false; return 0; }
+    if (L->ncomp == 0) { note_empty_solve(L, false, nstarts); return 0; }
 
     // replicas of the per-solve workspace (ws, gfac; the plain solver's x and dir too) a launch may hold within the budget: at least one
-    const size_t work_doubles = 5 * (size_t)L->nfree + (size_t)L->ngfac + (plain ? (size_t)p->N : 0), dir_doubles = plain ? (size_t)p->N : 0;
-    const size_t rep_bytes = (work_doubles + dir_doubles) * sizeof(double);
-    int64_t R = rep_bytes ? std::max<int64_t>(1, L->starts_workspace_bytes / (int64_t)rep_bytes) : nstarts;
-    R = std::min(std::min(R, nstarts), STARTS_MAX_PER_LAUNCH);
-    int rc = 0;
-    if (L->ms_work.bytes < (size_t)R * work_doubles * sizeof(double)) rc = plan_alloc(L, L->ms_work, (size_t)R * work_doubles * sizeof(double));
-    if (!rc && plain && L->ms_dir.bytes < (size_t)R * dir_doubles * sizeof(double)) {
-        rc = plan_alloc(L, L->ms_dir, (size_t)R * dir_doubles * sizeof(double));
-        if (!rc) HIPCHK(c, hipMemsetAsync(L->ms_dir.p, 0, L->ms_dir.bytes, c->stream));   // (the kernel leaves what it wrote zero again)
-    }
+    const ReplicaLayout work = starts_work_layout(L->nfree, L->ngfac, plain, p->N), dir = solve_dir_layout(plain, p->N);
+    const int64_t R = members_per_launch(nstarts, L->starts_workspace_bytes, work.member_bytes() + dir.member_bytes());
+    int rc = grow_solve_buffers(L, (size_t)work.total_bytes(R), (size_t)dir.total_bytes(R), 0, nstarts);
     const size_t in_bytes = (size_t)nstarts * (size_t)L->nfree * sizeof(double);
-    if (!rc && L->ms_in.bytes < in_bytes) rc = plan_alloc(L, L->ms_in, in_bytes);
-    if (!rc && L->ms_out.bytes < L->ms_out_bytes(nstarts)) rc = plan_alloc(L, L->ms_out, L->ms_out_bytes(nstarts));
     if (!rc && !L->ms_best.p) rc = plan_alloc(L, L->ms_best, (size_t)L->ncomp * sizeof(int));
     if (rc) return rc;
     L->ms_n = 0;   // (what an earlier call left is overwritten from here on)
@@ -2050,11 +2081,11 @@ extern "C" int rdis_hip_plan_solve_starts(rdis_hip_plan* L, int64_t nstarts, con
     const ProblemView P = p->view();
     PlanView V = L->view();   // (order: the whole batch list -- empty components and those of the plan's one solver, heaviest first)
     StartsView S = L->starts_view(nstarts);
-    S.gfac = S.ws + (size_t)R * 5 * (size_t)L->nfree;
+    S.gfac = work.at<double>(S.ws, STARTS_GFAC, R);
     const int threads = plain ? wg_launch_threads(L) : L->rest_lds > 0 ? lds_launch_threads(L) : 64;
     const size_t dyn = L->lds_dyn_bytes(c);
     if (plain) {   // every replica's x: the problem's, for the constants (solver_wg_starts.hpp; once per call)
-        S.x = S.gfac + (size_t)R * (size_t)L->ngfac;
+        S.x = work.at<double>(S.ws, STARTS_X, R);
         S.dir = L->ms_dir.as<double>();
         HIPCHK(c, starts_fill_x_launch(c->stream, P, S, R));
     }
@@ -2069,17 +2100,13 @@ extern "C" int rdis_hip_plan_solve_starts(rdis_hip_plan* L, int64_t nstarts, con
                                      maxiters, ftol, L->lds_ns_cap, L->lds_ncb_cap, L->lds_chunk_cap));
         ++L->last_launches;
     }
-    HIPCHK(c, hipEventRecord(p->ev1, c->stream));
-    L->timed = true;
-    p->last_timed_plan = L;
+    if ((rc = end_timed_launches(L))) return rc;
     // what the node keeps: the best start per component, as the plan's ordinary outputs and the assignment of its variables
     S.first = 0;
     HIPCHK(c, starts_select_launch(c->stream, P, V, S, nstarts, L->ms_best.as<int>()));
     objective_sum_kernel<<<1, 256, 0, c->stream>>>((int)L->ncomp, V.fret, L->objective.as<double>());
     HIPCHK(c, hipGetLastError());
-    L->ms_n = nstarts;
-    L->ms_per_launch = R;
-    L->ms_launches = L->last_launches;
+    note_many_solve(L, false, nstarts, R);
     return 0;
 }
 
@@ -2249,9 +2276,10 @@ int population_eval_enqueue(rdis_hip_population* pop, int64_t nf, const int* dfa
         return 0;
     }
     const int64_t per = fused ? (nf + GRAD_LANES - 1) / GRAD_LANES : grid_for(c, nf, 256);   // a member's partials: chunks, or enqueue_eval's blocks
-    const int64_t R = eval_members_per_launch(S_n, pop->eval_workspace_bytes, per, p->N, records);
-    if ((rc = ensure(c, pop->eval_partial, (size_t)R * (size_t)per * sizeof(double)))) return rc;
-    if (records && (rc = ensure(c, pop->eval_xr, (size_t)R * (size_t)p->N * sizeof(double)))) return rc;
+    const ReplicaLayout partials = population_eval_partial_layout(per), xr = population_eval_xr_layout(records, p->N);
+    const int64_t R = members_per_launch(S_n, pop->eval_workspace_bytes, partials.member_bytes() + xr.member_bytes());
+    if ((rc = ensure(c, pop->eval_partial, (size_t)partials.total_bytes(R)))) return rc;
+    if (records && (rc = ensure(c, pop->eval_xr, (size_t)xr.total_bytes(R)))) return rc;
     const ProblemView V = p->view();
     double *X = pop->X.as<double>(), *part = pop->eval_partial.as<double>(), *XR = records ? pop->eval_xr.as<double>() : nullptr;
     int64_t launches = 0;
@@ -2389,11 +2417,11 @@ int population_grad_enqueue(rdis_hip_population* pop, int64_t first0, int64_t co
             dptr = pop->grad_v2s_ptr.as<int>(); didx = pop->grad_v2s_idx.as<int>();
         }
     }
-    const int64_t mbytes = grad_member_bytes(branch, shape);
-    const int64_t R = branch == GRAD_BRANCH_NONE ? count : grad_members_per_launch(count, pop->grad_workspace_bytes, mbytes);
+    const ReplicaLayout ws = grad_member_layout(branch, shape);
+    const int64_t R = branch == GRAD_BRANCH_NONE ? count : members_per_launch(count, pop->grad_workspace_bytes, ws.member_bytes());
     if ((rc = ensure(c, pop->grad_f, (size_t)count * sizeof(double)))) return rc;
     if ((rc = ensure(c, pop->grad_g, (size_t)count * (size_t)N * sizeof(double)))) return rc;
-    if (branch != GRAD_BRANCH_NONE && (rc = ensure(c, pop->grad_ws, (size_t)R * (size_t)mbytes))) return rc;
+    if (branch != GRAD_BRANCH_NONE && (rc = ensure(c, pop->grad_ws, (size_t)ws.total_bytes(R)))) return rc;
     pop->grad_rows = count; pop->grad_per_launch = R; pop->grad_launches = 0; pop->grad_branch = branch;
     double *X = pop->X.as<double>(), *F_out = pop->grad_f.as<double>(), *G_out = pop->grad_g.as<double>(), *W = pop->grad_ws.as<double>();
     if (branch == GRAD_BRANCH_NONE) {
@@ -2406,10 +2434,10 @@ int population_grad_enqueue(rdis_hip_population* pop, int64_t first0, int64_t co
     if (branch == GRAD_BRANCH_FUSED) {
         const GradTables& T = G->T;
         GradReplicas rep;
-        rep.camrec_stride = GRAD_REC * p->ncam_blocks; rep.cstage_stride = 9ll * std::max(G->cstage_slots, 1);
-        rep.pstage_stride = 3ll * std::max(G->pstage_slots, 1); rep.partial_stride = T.nchunks;
-        rep.camrec = W; rep.cstage = rep.camrec + R * rep.camrec_stride; rep.pstage = rep.cstage + R * rep.cstage_stride;
-        rep.partial = rep.pstage + R * rep.pstage_stride;
+        rep.camrec = ws.at<double>(W, GRAD_FUSED_CAMREC, R); rep.camrec_stride = ws.doubles(GRAD_FUSED_CAMREC);
+        rep.cstage = ws.at<double>(W, GRAD_FUSED_CSTAGE, R); rep.cstage_stride = ws.doubles(GRAD_FUSED_CSTAGE);
+        rep.pstage = ws.at<double>(W, GRAD_FUSED_PSTAGE, R); rep.pstage_stride = ws.doubles(GRAD_FUSED_PSTAGE);
+        rep.partial = ws.at<double>(W, GRAD_FUSED_PARTIAL, R); rep.partial_stride = ws.doubles(GRAD_FUSED_PARTIAL);   // (T.nchunks: at least one)
         const long long items = 9ll * T.ncs + 3ll * T.nps + T.nz;
         for (int64_t k = 0; k < count; k += R) {   // (rounds on one stream: the next takes the replicas when this one is done)
             const int ns = (int)std::min<int64_t>(R, count - k);
@@ -2424,8 +2452,8 @@ int population_grad_enqueue(rdis_hip_population* pop, int64_t first0, int64_t co
             launches += items > 0 ? 4 : 3;
         }
     } else {
-        const long long nslots = p->nslots();
-        double *gfac = W, *part = W + R * nslots;   // [R][nslots], [R][blocks]
+        const long long nslots = ws.doubles(GRAD_LIST_GFAC);
+        double *gfac = ws.at<double>(W, GRAD_LIST_GFAC, R), *part = ws.at<double>(W, GRAD_LIST_PARTIAL, R);   // [R][nslots], [R][blocks]
         for (int64_t k = 0; k < count; k += R) {
             const int ns = (int)std::min<int64_t>(R, count - k);
             const int64_t first = first0 + k;
@@ -2650,7 +2678,7 @@ int solve_population_range(rdis_hip_plan* L, rdis_hip_population* pop, int64_t f
                                             " workgroups (other sums, other bits): set the plan option ptm_group = 1");
     }
     pop->eval_valid = false; pop->best_current = false;   // X is written: the values of the last evaluation are stale
-    if (L->ncomp == 0) { L->ms_population = true; L->ms_n = S_n; L->ms_per_launch = S_n; L->ms_launches = 0; L->last_launches = 0; L->timed = false; return 0; }
+    if (L->ncomp == 0) { note_empty_solve(L, true, S_n); return 0; }
 
     // what a launch runs: the tiny-component solver on the first rest_tiny entries of the batch list (option population_tiny: the
     // refusal above let them pass), the LDS-resident or the plain solver on the entries behind them, where there are any
@@ -2664,29 +2692,18 @@ int solve_population_range(rdis_hip_plan* L, rdis_hip_population* pop, int64_t f
     // replicas a launch may hold within the budget, the multi-start entry's rule.  A replica holds only what the launch's kernels
     // read: ws and gfac where the LDS-resident or the plain solver runs (the plain solver's dir too -- its x is the member's row),
     // the cameras' rotation records [N] where the tiny-component solver reads records
-    const size_t work_doubles = nlisted > 0 ? 5 * (size_t)L->nfree + (size_t)L->ngfac : 0, rot_doubles = tiny_records ? (size_t)p->N : 0;
-    const size_t dir_doubles = plain ? (size_t)p->N : 0;
-    // ... and the four per-solve arrays of the point-major solver (population_grid.hpp: ptm_population_replica_bytes)
-    const size_t ptm_bytes = nptm > 0 ? (size_t)ptm_population_replica_bytes(L->pm_blocks, L->pm_cptr_len, false, 0, 0) : 0;
-    const size_t rep_bytes = (work_doubles + rot_doubles + dir_doubles) * sizeof(double) + ptm_bytes;
-    const int64_t R = population_members_per_launch(S_n, L->starts_workspace_bytes, (int64_t)rep_bytes);
+    const ReplicaLayout work = population_work_layout(nlisted > 0, L->nfree, L->ngfac, tiny_records, p->N), dir = solve_dir_layout(plain, p->N);
+    // ... and the four per-solve arrays of the point-major solver
+    const ReplicaLayout ptm = population_ptm_layout(nptm > 0 ? L->pm_blocks : 0, L->pm_cptr_len);
+    const int64_t R = members_per_launch(S_n, L->starts_workspace_bytes, work.member_bytes() + dir.member_bytes() + ptm.member_bytes());
     int rc = 0;
     if (nptm > 0) {
         // the round tables of that workgroup size, one workgroup a component, before the first launch (launch_ptm's)
         rc = ptm_build_rounds(L, ptm_threads, 1);
-        if (!rc && L->ms_ptm.bytes < (size_t)R * ptm_bytes) rc = plan_alloc(L, L->ms_ptm, (size_t)R * ptm_bytes);
+        if (!rc && L->ms_ptm.bytes < (size_t)ptm.total_bytes(R)) rc = plan_alloc(L, L->ms_ptm, (size_t)ptm.total_bytes(R));
         if (rc) return rc;
     }
-    const size_t work_bytes = (size_t)R * (work_doubles + rot_doubles) * sizeof(double);
-    if (L->ms_work.bytes < work_bytes) rc = plan_alloc(L, L->ms_work, work_bytes);
-    if (!rc && plain && L->ms_dir.bytes < (size_t)R * dir_doubles * sizeof(double)) {
-        rc = plan_alloc(L, L->ms_dir, (size_t)R * dir_doubles * sizeof(double));
-        if (!rc) HIPCHK(c, hipMemsetAsync(L->ms_dir.p, 0, L->ms_dir.bytes, c->stream));   // (the kernel leaves what it wrote zero again)
-    }
-    if (!rc && ntiny > 0 && L->ms_queue.bytes < (size_t)R * sizeof(int)) rc = plan_alloc(L, L->ms_queue, (size_t)R * sizeof(int));
-    const size_t in_bytes = (size_t)S_n * (size_t)L->nfree * sizeof(double);
-    if (!rc && L->ms_in.bytes < in_bytes) rc = plan_alloc(L, L->ms_in, in_bytes);
-    if (!rc && L->ms_out.bytes < L->ms_out_bytes(S_n)) rc = plan_alloc(L, L->ms_out, L->ms_out_bytes(S_n));
+    rc = grow_solve_buffers(L, (size_t)work.total_bytes(R), (size_t)dir.total_bytes(R), ntiny > 0 ? (size_t)R * sizeof(int) : 0, S_n);
     if (rc) return rc;
     L->ms_n = 0;   // (what an earlier call left is overwritten from here on)
 
@@ -2694,8 +2711,8 @@ int solve_population_range(rdis_hip_plan* L, rdis_hip_population* pop, int64_t f
     const ProblemView P = p->view();
     PlanView V = L->view();   // (order: the whole batch list -- tiny components first, then empty ones and those of the plan's other solver, heaviest first)
     StartsView S = L->starts_view(S_n);
-    S.gfac = S.ws + (size_t)R * (work_doubles ? 5 * (size_t)L->nfree : 0);
-    double* const XR = tiny_records ? S.ws + (size_t)R * work_doubles : nullptr;   // [R][N], behind the launch's replicas of ws and gfac
+    S.gfac = work.at<double>(S.ws, POPULATION_GFAC, R);
+    double* const XR = tiny_records ? work.at<double>(S.ws, POPULATION_ROT, R) : nullptr;   // [R][N], behind the launch's replicas of ws and gfac
     if (plain) S.dir = L->ms_dir.as<double>();   // (no replica of x: the member's row serves, solver_wg_population.hpp)
     // every member's start row: its own x at the plan's free variables (plan_set_start(plan, NULL) on that x)
     HIPCHK(c, population_gather_launch(c->stream, Xb, p->N, V.free_vid, L->nfree, S_n, L->ms_in.as<double>()));
@@ -2710,9 +2727,9 @@ int solve_population_range(rdis_hip_plan* L, rdis_hip_population* pop, int64_t f
     // the launch's replicas of pm_rec, pm_gh, pm_bex (six doubles a point block each) and, behind them, of pm_cbox
     PtmReplicas RP{nullptr, nullptr, nullptr, nullptr, L->pm_blocks, L->pm_cptr_len};
     if (nptm > 0) {
-        const size_t plane = (size_t)R * PT_REC * (size_t)L->pm_blocks;
-        RP.rec = L->ms_ptm.as<double>(); RP.gh = RP.rec + plane; RP.bex = RP.gh + plane;
-        RP.cbox = reinterpret_cast<float*>(RP.bex + plane);
+        void* const base = L->ms_ptm.p;
+        RP.rec = ptm.at<double>(base, PTM_REPLICA_REC, R); RP.gh = ptm.at<double>(base, PTM_REPLICA_GH, R);
+        RP.bex = ptm.at<double>(base, PTM_REPLICA_BEX, R); RP.cbox = ptm.at<float>(base, PTM_REPLICA_CBOX, R);
     }
     const size_t ptm_dyn = nptm > 0 ? ptm_bytes_for(L->ptm_ncb_cap, ptm_threads, L->rounds_slots) : 0;
     L->last_launches = 0;
@@ -2745,13 +2762,8 @@ int solve_population_range(rdis_hip_plan* L, rdis_hip_population* pop, int64_t f
             ++L->last_launches;
         }
     }
-    HIPCHK(c, hipEventRecord(p->ev1, c->stream));
-    L->timed = true;
-    p->last_timed_plan = L;
-    L->ms_population = true;
-    L->ms_n = S_n;
-    L->ms_per_launch = R;
-    L->ms_launches = L->last_launches;
+    if ((rc = end_timed_launches(L))) return rc;
+    note_many_solve(L, true, S_n, R);
     return 0;
 }
 }  // namespace
