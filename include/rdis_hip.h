@@ -170,6 +170,29 @@ int rdis_hip_lm_optimize(rdis_hip_problem *p, int64_t nfree, const int64_t *free
                          int32_t residual_model, double *fret, double *delta, double *info8, double *hist4, int64_t hist_cap,
                          int64_t *nhist);
 
+/* ---- the same solver for a batch of small independent components, in one launch per class -----
+ * Component c is free_vid[free_ptr[c] .. free_ptr[c+1]) over fac_id[fac_ptr[c] .. fac_ptr[c+1]): the calling convention
+ * of rdis_hip_cgd_batch (components must be independent, otherwise RDIS_HIP_EOVERLAP; x_inout concatenated in
+ * free-variable order, NULL = start at the assigned x; the variables are left assigned to every component's clamped
+ * result).  Each component is solved as rdis_hip_lm_optimize would solve it -- one run of oracle/lm_oracle.py's
+ * lm_optimize -- by one workgroup that runs the whole iteration on the device (rdis_amd/csrc/lm_batch.hip): the number of
+ * launches and stream waits of a call depends neither on ncomp nor on the iterations or rejected steps.
+ * residual_model is 1 or 2 (bits 4-5 are ignored).  Bundle adjustment only.
+ * Per component: fret[c], delta[c] (fret minus the listed factors' value at the start), info8[c][8], hist4[c][hist_cap][4]
+ * and nhist[c] with the meaning they have for rdis_hip_lm_optimize; any output pointer may be NULL.  A component's results
+ * do not depend, bit for bit, on the other components of the call or on its position among them.
+ * Unlike rdis_hip_lm_optimize a component may have an empty factor list (rdis_hip_components produces them): it ends
+ * with stop code 6, 0 iterations, fret 0 and x = clamp(start).
+ * A component with more than RDIS_HIP_LM_BATCH_MAX_CAMERAS camera blocks that hold a free variable makes the whole call
+ * fail with RDIS_HIP_ERANGE before anything is solved (the message names it): such a component belongs on
+ * rdis_hip_lm_optimize.  Points and factors per component are not limited.  Two listed factors of a component that join the
+ * same camera and point: RDIS_HIP_EINVAL.  Returns 0 also when components stop with codes 4, 5 or 7. */
+#define RDIS_HIP_LM_BATCH_MAX_CAMERAS 16
+int rdis_hip_lm_batch(rdis_hip_problem *p, int64_t ncomp, const int64_t *free_ptr, const int64_t *free_vid,
+                      const int64_t *fac_ptr, const int64_t *fac_id, double *x_inout, int32_t maxiters, double ftol,
+                      int32_t residual_model, double *fret, double *delta, double *info8, double *hist4,
+                      int64_t hist_cap, int64_t *nhist);
+
 /* ---- the step before the path: which independent sub-problems are there? -----
  * Connected components of the factor graph once the variables with assigned[v] != 0 are fixed:
  * what Component::createChildren (src/Component.cpp:508-549) obtains from the reference's dynamic

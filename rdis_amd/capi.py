@@ -117,6 +117,8 @@ SYMBOLS = {
     "rdis_hip_plan_debug_counters": (C.c_int, [_vp, _vp]),
     "rdis_hip_lm_optimize": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, _vp, C.c_int32, C.c_double, C.c_int32, _vp, _vp, _vp, _vp,
                                        C.c_int64, _vp]),
+    "rdis_hip_lm_batch": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32, _vp, _vp, _vp, _vp,
+                                    C.c_int64, _vp]),
     "rdis_hip_components": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "rdis_hip_components_fetch": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
 }
@@ -357,6 +359,25 @@ class Problem:
         return LmResult(x=self.get_x(fv), fret=float(out[0]), delta=float(out[1]), iters=int(info[0]), stop=int(info[1]),
                         nfev=int(info[2]), njev=int(info[3]), nsolve=int(info[4]), mu=float(info[5]),
                         camera_blocks=int(info[6]), point_blocks=int(info[7]), history=hist[:min(int(nh[0]), hist.shape[0])].copy())
+
+    def lm_batch(self, free_ptr, free_vid, fac_ptr, fac_id, x=None, maxiters=25, ftol=3e-8, history=64, model=1):
+        """Levenberg-Marquardt for a batch of small independent components (the lists of cgd_batch / components), one
+        workgroup per component, one call.  x: start values concatenated in free-variable order (None: the assigned x).
+        Returns a list of LmResult, one per component; the variables are left assigned to the results."""
+        free_ptr, free_vid, fac_ptr, fac_id = _i(free_ptr), _i(free_vid), _i(fac_ptr), _i(fac_id)
+        nc = free_ptr.shape[0] - 1
+        xin = None if x is None else _f(x).copy()
+        cap = max(int(history), 1)
+        fret, delta, info = np.zeros(max(nc, 1)), np.zeros(max(nc, 1)), np.zeros((max(nc, 1), 8))
+        hist = np.zeros((max(nc, 1), cap, 4))
+        nh = np.zeros(max(nc, 1), dtype=np.int64)
+        self.ctx.check(self.ctx.lib.rdis_hip_lm_batch(self.h, nc, _ptr(free_ptr), _ptr(free_vid), _ptr(fac_ptr), _ptr(fac_id), _ptr(xin),
+                                                      maxiters, ftol, model, _ptr(fret), _ptr(delta), _ptr(info), _ptr(hist), cap, _ptr(nh)))
+        xs = self.get_x(free_vid) if free_vid.shape[0] else np.zeros(0)
+        return [LmResult(x=xs[free_ptr[c]:free_ptr[c + 1]].copy(), fret=float(fret[c]), delta=float(delta[c]), iters=int(info[c, 0]),
+                         stop=int(info[c, 1]), nfev=int(info[c, 2]), njev=int(info[c, 3]), nsolve=int(info[c, 4]), mu=float(info[c, 5]),
+                         camera_blocks=int(info[c, 6]), point_blocks=int(info[c, 7]), history=hist[c, :min(int(nh[c]), cap)].copy())
+                for c in range(nc)]
 
     def components(self, assigned):
         """(free_ptr, free_vid, fac_ptr, fac_id) of the connected components left when the variables

@@ -21,6 +21,7 @@
 #include "plan_index.hpp"
 #include "components.hpp"
 #include "lm_solver.hpp"
+#include "lm_batch.hpp"
 #include "grad_fused.hpp"
 #include "starts_api.hpp"
 
@@ -187,6 +188,7 @@ struct rdis_hip_problem {
     ivec h_local, h_owner_stamp, h_fac_stamp;  // validity by stamp: no O(N) clears per call
     std::vector<VarMark> h_mark;           // [N] plan_create's view of a variable: free in which component, where in the free list
     LmWorkspace lm_ws;                     // scratch of rdis_hip_lm_optimize, kept between calls
+    LmBatchWorkspace lm_batch_ws;          // ... and of rdis_hip_lm_batch
     CcWorkspace cc_ws;                     // ... and of rdis_hip_components
     ComponentLists comps;                  // result of the last rdis_hip_components call
     DevBuf assigned;

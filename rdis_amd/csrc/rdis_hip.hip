@@ -2852,6 +2852,71 @@ extern "C" int rdis_hip_lm_optimize(rdis_hip_problem* p, int64_t nfree, const in
     return 0;
 }
 
+// Levenberg-Marquardt for a batch of small components, one workgroup each (lm_batch.hip).  Everything that can be refused
+// is refused on the host, before x is touched or anything is launched: the lists by the plan index's checks, the
+// components' sizes and factor pairs by lm_batch_prepare.
+static_assert(LM_BATCH_EINVAL == RDIS_HIP_EINVAL && LM_BATCH_ERANGE == RDIS_HIP_ERANGE && LM_BATCH_MAX_CAMERAS == RDIS_HIP_LM_BATCH_MAX_CAMERAS,
+              "lm_batch.hpp restates include/rdis_hip.h");
+extern "C" int rdis_hip_lm_batch(rdis_hip_problem* p, int64_t ncomp, const int64_t* free_ptr, const int64_t* free_vid,
+                                 const int64_t* fac_ptr, const int64_t* fac_id, double* x_inout, int32_t maxiters, double ftol,
+                                 int32_t model, double* fret, double* delta, double* info8, double* hist4, int64_t hist_cap,
+                                 int64_t* nhist) {
+    if (!p) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = p->ctx;
+    if (p->kind != KIND_BA) return fail(c, RDIS_HIP_EINVAL, "lm_batch: bundle adjustment problems only");
+    if (ncomp < 0 || !free_ptr || !fac_ptr || maxiters < 1 || hist_cap < 0) return fail(c, RDIS_HIP_EINVAL, "lm_batch: bad arguments");
+    const int R = model & 15;   // (the Schur bits of rdis_hip_lm_optimize are ignored)
+    if (R != 1 && R != 2) return fail(c, RDIS_HIP_EINVAL, "lm_batch: residual model must be 1 or 2");
+    if (p->ncam_blocks <= 0 && p->F > 0) return fail(c, RDIS_HIP_EINVAL, "lm_batch: the factors' camera and point blocks overlap");
+    auto relabel = [](std::string m) { return m.rfind("plan_create", 0) == 0 ? "lm_batch" + m.substr(11) : m; };
+    std::string why;
+    if (int rc = plan_index_check(ncomp, free_ptr, free_vid, fac_ptr, fac_id, &why)) return fail(c, rc, relabel(why));
+    USE_DEVICE(c);
+    int rc = ensure_problem_scratch(p);
+    if (rc) return rc;
+    {   // independence, by the plan index's check (its tables are not kept)
+        PlanIndex X;
+        const IndexArrays A{p->kind, p->N, p->F, p->h_cam.data(), p->h_pt.data(), p->h_rowptr.data(), p->h_vid.data(),
+                            p->h_block_of.data(), p->ncam_blocks, p->h_mark.data(), p->h_fac_stamp.data(), ++p->stamp};
+        if ((rc = plan_index_build(A, ncomp, free_ptr, free_vid, fac_ptr, fac_id, X, &why))) return fail(c, rc, relabel(why));
+    }
+    // cameras below the first point block, blocks of 9 then blocks of 3: what rdis_hip_lm_optimize requires; where it holds,
+    // a variable no factor reads belongs to the layout's block, like there
+    int minpt = INT32_MAX;
+    for (int64_t f = 0; f < p->F; ++f) minpt = std::min(minpt, p->h_pt[(size_t)f]);
+    const int ncams = p->F > 0 ? minpt / 9 : 0;
+    bool layout = p->F > 0 && (p->N - 9ll * ncams) % 3 == 0;
+    for (int64_t f = 0; f < p->F && layout; ++f)
+        layout = p->h_cam[(size_t)f] % 9 == 0 && p->h_cam[(size_t)f] < 9 * ncams && (p->h_pt[(size_t)f] - 9 * ncams) % 3 == 0;
+    const LmBatchBlocks blocks{p->N, p->F, p->h_cam.data(), p->h_pt.data(), p->h_block_of.data(), p->h_ptblock_of.data(), layout, ncams};
+    LmBatchTables T;
+    if ((rc = lm_batch_prepare(blocks, ncomp, free_ptr, free_vid, fac_ptr, fac_id, R, T, &why))) return fail(c, rc, why);
+    const int64_t nfree = free_ptr[ncomp];
+    if (x_inout && nfree > 0 && (rc = rdis_hip_set_x(p, nfree, free_vid, x_inout))) return rc;
+    const LmBatchProblem P{p->x.as<double>(), p->lo.as<double>(), p->hi.as<double>(), p->cam.as<int>(), p->pt.as<int>(), p->obs.as<double2>()};
+    const LmBatchOptions o{maxiters, R, 1e-3, 1e-15, 1e-15, ftol};
+    std::vector<double> res, hist;
+    const int64_t cap = hist4 ? hist_cap : 0;
+    const int e = device_lm_batch(c->stream, P, T, o, cap, &p->lm_batch_ws, &res, &hist);
+    if (e != 0) return fail(c, RDIS_HIP_EDEVICE, std::string("lm_batch: ") + hipGetErrorString((hipError_t)e));
+    if (x_inout && nfree > 0 && (rc = rdis_hip_get_x(p, nfree, free_vid, x_inout))) return rc;
+    for (int64_t cc = 0; cc < ncomp; ++cc) {
+        const double* r = res.data() + (size_t)cc * LM_BATCH_RES;
+        if (fret) fret[cc] = r[0];
+        if (delta) delta[cc] = r[0] - r[1];
+        if (info8) {
+            double* i8 = info8 + 8 * cc;
+            i8[0] = r[2]; i8[1] = r[3]; i8[2] = r[4]; i8[3] = r[5]; i8[4] = r[6]; i8[5] = r[7]; i8[6] = r[8]; i8[7] = r[9];
+        }
+        if (nhist) nhist[cc] = (int64_t)r[10];
+        if (cap > 0) {
+            const int64_t n = std::min<int64_t>((int64_t)r[10], cap);
+            std::memcpy(hist4 + (size_t)cc * (size_t)cap * 4, hist.data() + (size_t)cc * (size_t)cap * 4, (size_t)n * 32);
+        }
+    }
+    return 0;
+}
+
 extern "C" int rdis_hip_components(rdis_hip_problem* p, const uint8_t* assigned, int64_t* ncomp, int64_t* nfree, int64_t* nfac) {
     if (!p) return RDIS_HIP_EINVAL;
     rdis_hip_ctx* c = p->ctx;
