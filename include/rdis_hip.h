@@ -489,6 +489,52 @@ int rdis_hip_plan_fetch_population(rdis_hip_plan *plan, double *x_out, double *f
  * returns a device pointer to one double valid until the next plan_solve. */
 int rdis_hip_plan_objective_device(rdis_hip_plan *plan, void **dev_ptr);
 
+/* ---- Levenberg-Marquardt plans: rdis_hip_lm_batch's tables built once, solves that stay on the stream -----
+ * rdis_hip_lm_batch does a plan's work in every call: it checks the lists, builds and uploads the components' tables,
+ * downloads the results and waits.  A rdis_hip_lm_plan does the first two once (the tables do not depend on x) and leaves
+ * the last two to a fetch: between create and fetch nothing is copied, allocated (after the first solve) or waited for, so
+ * an alternation of camera and point plans runs on the stream from end to end.
+ *   rdis_hip_lm_plan_create   everything rdis_hip_lm_batch checks before it assigns x, with its codes (messages are
+ *                             labelled lm_plan_create): bundle adjustment only, residual_model 1 or 2, RDIS_HIP_EOVERLAP,
+ *                             ids in range, more than RDIS_HIP_LM_BATCH_MAX_CAMERAS active camera blocks RDIS_HIP_ERANGE,
+ *                             two listed factors joining one camera and point RDIS_HIP_EINVAL.  hist_cap: history records
+ *                             kept per component (0: none)
+ *   rdis_hip_lm_plan_solve    every component from the problem's currently assigned x, the clamped results left assigned:
+ *                             at most three launches (one per class that occurs); bit for bit rdis_hip_lm_batch with
+ *                             x_inout = NULL
+ *   rdis_hip_lm_plan_fetch    waits, then the last solve's outputs with the shapes and meaning of rdis_hip_lm_batch's
+ *                             (hist4[c][hist_cap][4] with the plan's hist_cap); x_out: the solve's clamped results,
+ *                             concatenated in free-variable order, kept by the plan beside the other outputs -- what the
+ *                             solve left assigned, whatever was assigned since.  Any pointer may be NULL
+ *   rdis_hip_lm_plan_solve_population   members first .. first + count - 1 of a population of the same problem, the member
+ *                             the grid's second dimension: member s starts from X[s], reads its constants there and is
+ *                             left at its clamped result -- what rdis_hip_lm_batch leaves on a problem whose x is X[s], bit
+ *                             for bit.  Other rows and the problem's x are untouched; the population's values become stale
+ *                             (rdis_hip_population_best: evaluate first).  RDIS_HIP_EINVAL: another problem's population,
+ *                             count < 1, a range out of bounds.  No wait
+ *   rdis_hip_lm_plan_fetch_population   the same outputs, [count][ncomp]...; row i is member first + i; x_out [count][nfree]
+ *                             comes from the plan's own outputs too: the population may have been written or destroyed since
+ *   A fetch that does not match the kind of the last solve, or before any solve: RDIS_HIP_EINVAL, nothing changed.
+ *   rdis_hip_lm_plan_set_option   "workspace_bytes" (default 2^30, >= 0): bounds the workspace replicas of one population
+ *                             launch; a solve of more members than fit is split into launches (at least one member
+ *                             each), the same bits whatever the split
+ *   rdis_hip_lm_plan_get_info "members_per_launch", "launches" (of the last solve), "device_bytes", "workspace_bytes",
+ *                             "member_workspace_bytes" (one member's workspace replica) */
+typedef struct rdis_hip_lm_plan rdis_hip_lm_plan;
+int rdis_hip_lm_plan_create(rdis_hip_problem *p, int64_t ncomp, const int64_t *free_ptr, const int64_t *free_vid,
+                            const int64_t *fac_ptr, const int64_t *fac_id, int32_t residual_model, int64_t hist_cap,
+                            rdis_hip_lm_plan **out);
+void rdis_hip_lm_plan_destroy(rdis_hip_lm_plan *plan);
+int rdis_hip_lm_plan_solve(rdis_hip_lm_plan *plan, int32_t maxiters, double ftol);
+int rdis_hip_lm_plan_fetch(rdis_hip_lm_plan *plan, double *x_out, double *fret, double *delta, double *info8,
+                           double *hist4, int64_t *nhist);
+int rdis_hip_lm_plan_solve_population(rdis_hip_lm_plan *plan, rdis_hip_population *pop, int64_t first, int64_t count,
+                                      int32_t maxiters, double ftol);
+int rdis_hip_lm_plan_fetch_population(rdis_hip_lm_plan *plan, double *x_out, double *fret, double *delta, double *info8,
+                                      double *hist4, int64_t *nhist);
+int rdis_hip_lm_plan_set_option(rdis_hip_lm_plan *plan, const char *name, int64_t value);
+int rdis_hip_lm_plan_get_info(rdis_hip_lm_plan *plan, const char *name, int64_t *value);
+
 /* ---- the path's one collective --------------------------------------------------------
  * Independent components of a recursion level are sharded over the GPUs of a node (rdis_amd/dist.py, DESIGN.md section 5:
  * no data-path collective); what the ranks exchange is the top-level objective -- the sum the reference forms on one host

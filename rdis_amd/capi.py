@@ -119,6 +119,14 @@ SYMBOLS = {
                                        C.c_int64, _vp]),
     "rdis_hip_lm_batch": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32, _vp, _vp, _vp, _vp,
                                     C.c_int64, _vp]),
+    "rdis_hip_lm_plan_create": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, C.c_int32, _i64, C.POINTER(_vp)]),
+    "rdis_hip_lm_plan_destroy": (None, [_vp]),
+    "rdis_hip_lm_plan_solve": (C.c_int, [_vp, C.c_int32, C.c_double]),
+    "rdis_hip_lm_plan_fetch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rdis_hip_lm_plan_solve_population": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int32, C.c_double]),
+    "rdis_hip_lm_plan_fetch_population": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rdis_hip_lm_plan_set_option": (C.c_int, [_vp, C.c_char_p, _i64]),
+    "rdis_hip_lm_plan_get_info": (C.c_int, [_vp, C.c_char_p, C.POINTER(_i64)]),
     "rdis_hip_components": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "rdis_hip_components_fetch": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
 }
@@ -156,7 +164,7 @@ class _Cell:
 def _close_all():
     # the HIP runtime must still be loaded when device memory and streams are released
     objs = [r() for r in _live]
-    for cls in ("Comm", "Plan", "Population", "Problem", "Context"):
+    for cls in ("Comm", "Plan", "LmPlan", "Population", "Problem", "Context"):
         for o in objs:
             if o is not None and type(o).__name__ == cls:
                 try:
@@ -603,6 +611,84 @@ class Population:
         grad_launches (kernels of the last gradient call), grad_branch (0 none, 1 fused, 2 short, 3 two-pass)"""
         v = _i64()
         self.ctx.check(self.ctx.lib.rdis_hip_population_get_info(self.h, name.encode(), C.byref(v)))
+        return int(v.value)
+
+
+class LmPlan:
+    """rdis_hip_lm_plan: the tables of Problem.lm_batch for a list of small independent components, built and uploaded once.
+    solve() / solve_population() only enqueue launches; fetch() / fetch_population() wait and download.  model: residual model
+    1 or 2; history: records kept per component."""
+
+    def __init__(self, prob: Problem, free_ptr, free_vid, fac_ptr, fac_id, model=1, history=64):
+        self.prob, self.ctx = prob, prob.ctx
+        self.free_ptr, self.free_vid = _i(free_ptr), _i(free_vid)
+        self.fac_ptr, self.fac_id = _i(fac_ptr), _i(fac_id)
+        self.ncomp = self.free_ptr.shape[0] - 1
+        self.nfree = int(self.free_ptr[-1])
+        self.cap = max(int(history), 1)
+        self._nmembers = 0
+        h = _vp()
+        self.ctx.check(self.ctx.lib.rdis_hip_lm_plan_create(prob.h, self.ncomp, _ptr(self.free_ptr), _ptr(self.free_vid), _ptr(self.fac_ptr),
+                                                            _ptr(self.fac_id), int(model), self.cap, C.byref(h)))
+        self._cell = _Cell(h, self.ctx.lib.rdis_hip_lm_plan_destroy, prob._cell)
+        _register(self)
+
+    @property
+    def h(self):
+        return self._cell.h
+
+    def close(self):
+        if getattr(self, "_cell", None):
+            self._cell.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def solve(self, maxiters=25, ftol=3e-8):
+        """every component from the problem's assigned x, the results left assigned; enqueued, nothing is waited for"""
+        self.ctx.check(self.ctx.lib.rdis_hip_lm_plan_solve(self.h, maxiters, ftol))
+
+    def _fetch(self, entry, rows):
+        nc, cap = self.ncomp, self.cap
+        n = max(rows * nc, 1)
+        x = np.zeros((rows, self.nfree))
+        fret, delta, info, hist, nh = np.zeros(n), np.zeros(n), np.zeros((n, 8)), np.zeros((n, cap, 4)), np.zeros(n, dtype=np.int64)
+        self.ctx.check(entry(self.h, _ptr(x), _ptr(fret), _ptr(delta), _ptr(info), _ptr(hist), _ptr(nh)))
+        fp = self.free_ptr
+        return [[LmResult(x=x[s, fp[c]:fp[c + 1]].copy(), fret=float(fret[k]), delta=float(delta[k]), iters=int(info[k, 0]), stop=int(info[k, 1]),
+                          nfev=int(info[k, 2]), njev=int(info[k, 3]), nsolve=int(info[k, 4]), mu=float(info[k, 5]), camera_blocks=int(info[k, 6]),
+                          point_blocks=int(info[k, 7]), history=hist[k, :min(int(nh[k]), cap)].copy())
+                 for c in range(nc) for k in (s * nc + c,)] for s in range(rows)]
+
+    def fetch(self):
+        """the last solve()'s results: a list of LmResult, one per component, what Problem.lm_batch returns (x: the solve's
+        results as the plan kept them, whatever was assigned since)"""
+        return self._fetch(self.ctx.lib.rdis_hip_lm_plan_fetch, 1)[0]
+
+    def solve_population(self, pop: "Population", first=0, count=None, maxiters=25, ftol=3e-8):
+        """every component on members first .. first + count - 1 of pop (default: to the last) in one launch per class: member s
+        starts from its own x, reads its constants there and is left at its result.  The problem's x and the other members are
+        untouched; the population's values become stale.  Enqueued, nothing is waited for"""
+        first, count = pop._range(first, count)
+        self.ctx.check(self.ctx.lib.rdis_hip_lm_plan_solve_population(self.h, pop.h, first, count, maxiters, ftol))
+        self._nmembers = count
+
+    def fetch_population(self):
+        """the last solve_population()'s results: per member of the range a list of LmResult, one per component.  Everything
+        comes from the plan's own buffers: the population may have been written or closed since"""
+        return self._fetch(self.ctx.lib.rdis_hip_lm_plan_fetch_population, self._nmembers)
+
+    def set_option(self, name: str, value: int):
+        """workspace_bytes (default 2^30): bounds the workspace replicas of one population launch"""
+        self.ctx.check(self.ctx.lib.rdis_hip_lm_plan_set_option(self.h, name.encode(), int(value)))
+
+    def info(self, name: str) -> int:
+        """members_per_launch, launches (of the last solve), device_bytes, workspace_bytes, member_workspace_bytes"""
+        v = _i64()
+        self.ctx.check(self.ctx.lib.rdis_hip_lm_plan_get_info(self.h, name.encode(), C.byref(v)))
         return int(v.value)
 
 

@@ -18,6 +18,11 @@
 // Every sum runs in an order fixed by the component's own lists and its class (lm_batch.hpp: the class, and with it the
 // workgroup size, is a function of the component's camera count alone): a component's bits depend neither on what else
 // is in the batch nor on where it stands in it.
+//
+// The kernel is instantiated twice per class from the one body.  In the plans' instantiation the grid's second dimension is the
+// member (rdis_hip_lm_plan_solve_population: a population's rows of x; rdis_hip_lm_plan_solve: one member): a member has its own
+// x, its own replica of the workspace and its own rows of the outputs, and shares everything else.  The member enters pointer
+// sums only, so its bits are those of rdis_hip_lm_batch's instantiation, which has no member terms at all, on its x.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdint>
@@ -33,17 +38,21 @@ namespace rdis_hip {
 namespace {
 
 struct BatchDev {   // everything the kernel needs, by value
-    double* x;
+    double* x;                 // member 0's
     const double *lo, *hi;
     const int *cam, *pt;
     const double2* obs;
     const int *ints, *free32, *order;
     const unsigned char* freem;
     const LmBatchComp* comps;
-    double *res, *hist, *ws;   // [ncomp][LM_BATCH_RES], [ncomp][hist_cap][4] (or null), the workspace slices
+    double *res, *hist, *ws;   // per member: [ncomp][LM_BATCH_RES], [ncomp][hist_cap][4] (or null), the workspace slices
     int R, maxiters;
     long long hist_cap;
     double tau, eps1, eps2, eps3;
+    // the members' instantiation only: member m = blockIdx.y reads and writes x + m x_ms, and so for ws, res and hist (strides
+    // in doubles; everything else is shared by the members); xout + m xout_ms: [nfree] the member's clamped results, kept for the fetch
+    long long x_ms, ws_ms, res_ms, hist_ms, xout_ms;
+    double* xout;
 };
 
 __device__ __forceinline__ double wave_sum(double v) {
@@ -87,7 +96,9 @@ __device__ __forceinline__ void block_reduce(double* s, double* m, double* red) 
 __device__ __forceinline__ int tri(int i) { return i * (i + 1) / 2; }   // start of row i of a packed lower triangle
 __device__ __forceinline__ int vdiag(int k) { return k == 0 ? 0 : k == 1 ? 2 : 5; }   // V's packing: v00 v10 v11 v20 v21 v22
 
-template <int CLS>
+// MEMBERS false: a launch of one member whose pointers are B's own (rdis_hip_lm_batch) -- the member's terms are compiled out;
+// true: the grid's second dimension is the member (the plans' launches).  One body: the arithmetic is the same text.
+template <int CLS, bool MEMBERS>
 __global__ void __launch_bounds__(lm_batch_class_threads(CLS)) k_lm_batch(BatchDev B, int first) {
     constexpr int NT = lm_batch_class_threads(CLS), MAXC = lm_batch_class_cameras(CLS);
     extern __shared__ __attribute__((aligned(16))) double lm_batch_lds[];
@@ -98,6 +109,10 @@ __global__ void __launch_bounds__(lm_batch_class_threads(CLS)) k_lm_batch(BatchD
     double* const S = dc + 9 * MAXC;
     const int tid = threadIdx.x;
     const LmBatchComp C = B.comps[B.order[first + blockIdx.x]];
+    // the member: its x, its replica of the workspace, its rows of the outputs.  Nothing else depends on it: no count, no
+    // stride of a loop, no order of a sum
+    const long long mem = MEMBERS ? (long long)blockIdx.y : 0;
+    double* const x = MEMBERS ? B.x + mem * B.x_ms : B.x;
     const int nf = C.nf, nca = MAXC > 0 ? C.nca : 0, npa = C.npa, nfree = C.nfree, R = B.R, M = 9 * nca;
     const int* const it = B.ints + C.ints0;
     const int *lf = it + C.o_lf, *fci = it + C.o_fci, *fpi = it + C.o_fpi, *cptr = it + C.o_cptr, *clist = it + C.o_clist;
@@ -105,14 +120,14 @@ __global__ void __launch_bounds__(lm_batch_class_threads(CLS)) k_lm_batch(BatchD
     const int *pab = it + C.o_pab, *pairptr = it + C.o_pairptr, *pja = it + C.o_pja, *pjb = it + C.o_pjb;
     const int* const fv = B.free32 + C.free0;
     const LmBatchSlice W = lm_batch_slice(nf, C.nca, npa, nfree, R);
-    double* const ws = B.ws + C.ws0;
+    double* const ws = (MEMBERS ? B.ws + mem * B.ws_ms : B.ws) + C.ws0;
     double *Jc = ws + W.Jc, *Jp = ws + W.Jp, *E = ws + W.e, *T = ws + W.T, *Zc = ws + W.Zc, *V = ws + W.V, *bp = ws + W.bp;
     double *Lp = ws + W.Lp, *yp = ws + W.yp, *dp = ws + W.dp, *psave = ws + W.psave;
 
     auto load12 = [&](int f, double (&v)[12]) {
         const int c = B.cam[f], q = B.pt[f];
 #pragma unroll
-        for (int k = 0; k < 12; ++k) v[k] = B.x[k < 9 ? c + k : q + (k - 9)];
+        for (int k = 0; k < 12; ++k) v[k] = x[k < 9 ? c + k : q + (k - 9)];
     };
     // objective of the listed factors at the current x
     auto objective = [&]() -> double {
@@ -202,7 +217,7 @@ __global__ void __launch_bounds__(lm_batch_class_threads(CLS)) k_lm_batch(BatchD
             m[0] = fmax(m[0], V[6ll * (t / 3) + vdiag(t % 3)]);
             m[1] = fmax(m[1], fabs(bp[t]));
         }
-        for (int i = tid; i < nfree; i += NT) { const double xv = B.x[fv[i]]; s[0] += xv * xv; }
+        for (int i = tid; i < nfree; i += NT) { const double xv = x[fv[i]]; s[0] += xv * xv; }
         block_reduce<NT, 1, 2>(s, m, red);
         maxdiag = m[0]; jte_inf = m[1]; p_L2 = s[0];
     };
@@ -347,7 +362,7 @@ __global__ void __launch_bounds__(lm_batch_class_threads(CLS)) k_lm_batch(BatchD
                 const double lo = B.lo[v], hi = B.hi[v];
                 xn = (lo <= xn && xn <= hi) ? xn : (xn < lo ? lo : hi);
             }
-            B.x[v] = xn;
+            x[v] = xn;
             s[0] += dpv * dpv;
             s[1] += dpv * (damp(mu, floor_, dg) * dpv + b);
         }
@@ -357,7 +372,7 @@ __global__ void __launch_bounds__(lm_batch_class_threads(CLS)) k_lm_batch(BatchD
     };
 
     // ---- the iteration of lm_oracle.lm_optimize / device_lm_ba -----------------------------------------------------------
-    for (int i = tid; i < nfree; i += NT) psave[i] = B.x[fv[i]];
+    for (int i = tid; i < nfree; i += NT) psave[i] = x[fv[i]];
     const double finit = objective();
     double p_eL2 = 2.0 * finit, mu = 0.0;
     long long nu = 2;
@@ -386,7 +401,7 @@ __global__ void __launch_bounds__(lm_batch_class_threads(CLS)) k_lm_batch(BatchD
                 const double dF = p_eL2 - pDp_eL2;
                 const bool ok = dL > 0.0 && dF > 0.0;
                 if (tid == 0 && B.hist && nh < B.hist_cap) {
-                    double* h = B.hist + ((long long)C.comp * B.hist_cap + nh) * 4;
+                    double* h = (MEMBERS ? B.hist + mem * B.hist_ms : B.hist) + ((long long)C.comp * B.hist_cap + nh) * 4;
                     h[0] = mu; h[1] = Dp_L2; h[2] = ftrial; h[3] = ok ? 1.0 : 0.0;
                 }
                 ++nh;
@@ -396,7 +411,7 @@ __global__ void __launch_bounds__(lm_batch_class_threads(CLS)) k_lm_batch(BatchD
                     mu = mu * (tmp >= ONE_THIRD ? tmp : ONE_THIRD);
                     nu = 2;
                     p_eL2 = pDp_eL2;
-                    for (int i = tid; i < nfree; i += NT) psave[i] = B.x[fv[i]];   // (each thread its own entries: written and read by it alone)
+                    for (int i = tid; i < nfree; i += NT) psave[i] = x[fv[i]];   // (each thread its own entries: written and read by it alone)
                     break;
                 }
             }
@@ -412,21 +427,24 @@ __global__ void __launch_bounds__(lm_batch_class_threads(CLS)) k_lm_batch(BatchD
     for (int i = tid; i < nfree; i += NT) {   // x = clamp(accepted point)
         const int v = fv[i];
         const double xv = psave[i], lo = B.lo[v], hi = B.hi[v];
-        B.x[v] = (lo <= xv && xv <= hi) ? xv : (xv < lo ? lo : hi);
+        const double xc = (lo <= xv && xv <= hi) ? xv : (xv < lo ? lo : hi);
+        x[v] = xc;
+        if (MEMBERS) B.xout[mem * B.xout_ms + C.free0 + i] = xc;
     }
     const double fret = objective();
     if (tid == 0) {
-        double* r = B.res + (long long)C.comp * LM_BATCH_RES;
+        double* r = (MEMBERS ? B.res + mem * B.res_ms : B.res) + (long long)C.comp * LM_BATCH_RES;
         r[0] = fret; r[1] = finit; r[2] = k; r[3] = stop; r[4] = nfev; r[5] = njev; r[6] = nsolve; r[7] = mu;
         r[8] = C.nca; r[9] = npa; r[10] = (double)nh; r[11] = 0.0;
     }
 }
 
 template <int CLS>
-hipError_t launch_class(hipStream_t stream, const BatchDev& B, int first, int count) {
+hipError_t launch_class(hipStream_t stream, const BatchDev& B, int first, int count, int members) {
     if (count <= 0) return hipSuccess;
-    return launch_dyn(k_lm_batch<CLS>, dim3((unsigned)count), lm_batch_class_threads(CLS),
-                      lm_batch_lds_doubles(lm_batch_class_cameras(CLS)) * sizeof(double), stream, B, first);
+    const size_t lds = lm_batch_lds_doubles(lm_batch_class_cameras(CLS)) * sizeof(double);
+    if (B.xout) return launch_dyn(k_lm_batch<CLS, true>, dim3((unsigned)count, (unsigned)members), lm_batch_class_threads(CLS), lds, stream, B, first);
+    return launch_dyn(k_lm_batch<CLS, false>, dim3((unsigned)count), lm_batch_class_threads(CLS), lds, stream, B, first);
 }
 
 #define LMB_CHK(expr)                                  \
@@ -441,6 +459,31 @@ LmBatchWorkspace::~LmBatchWorkspace() {
     if (dev) (void)hipFree(dev);
 }
 
+int lm_batch_launch(hipStream_t stream, const LmBatchProblem& P, const void* tables, const LmBatchTableLayout& lay, const int (&n)[LM_BATCH_CLASSES],
+                    const LmBatchOptions& opt, int64_t hist_cap, const LmBatchMembers& M) {
+    const char* const base = static_cast<const char*>(tables);
+    BatchDev B{};
+    B.x = P.x; B.lo = P.lo; B.hi = P.hi; B.cam = P.cam; B.pt = P.pt; B.obs = P.obs;
+    if (!M.xout && M.count != 1) return (int)hipErrorInvalidValue;   // (one member without strides, or members with all of them)
+    B.x_ms = M.x_stride; B.ws_ms = M.ws_stride; B.res_ms = M.res_stride; B.hist_ms = M.hist_stride;
+    B.xout = M.xout; B.xout_ms = M.xout_stride;
+    B.comps = reinterpret_cast<const LmBatchComp*>(base + lay.comps);
+    B.ints = reinterpret_cast<const int*>(base + lay.ints);
+    B.free32 = reinterpret_cast<const int*>(base + lay.free32);
+    B.order = reinterpret_cast<const int*>(base + lay.order);
+    B.freem = reinterpret_cast<const unsigned char*>(base + lay.freem);
+    B.res = M.res;
+    B.hist = hist_cap > 0 ? M.hist : nullptr;
+    B.ws = M.ws;
+    B.R = opt.model; B.maxiters = opt.maxiters; B.hist_cap = hist_cap;
+    B.tau = opt.tau; B.eps1 = opt.eps1; B.eps2 = opt.eps2; B.eps3 = opt.eps3;
+    // one launch per class that occurs, its components heaviest first
+    LMB_CHK(launch_class<2>(stream, B, n[0] + n[1], n[2], M.count));
+    LMB_CHK(launch_class<1>(stream, B, n[0], n[1], M.count));
+    LMB_CHK(launch_class<0>(stream, B, 0, n[0], M.count));
+    return 0;
+}
+
 int device_lm_batch(hipStream_t stream, const LmBatchProblem& P, const LmBatchTables& T, const LmBatchOptions& opt,
                     int64_t hist_cap, LmBatchWorkspace* ws, std::vector<double>* res, std::vector<double>* hist) {
     const size_t ncomp = T.comps.size();
@@ -450,19 +493,12 @@ int device_lm_batch(hipStream_t stream, const LmBatchProblem& P, const LmBatchTa
     // One device block, kept by the caller between calls and grown on demand: the tables (one upload), the results
     // (one download), the history, the components' workspace slices.
     struct Part { size_t bytes, off; };
-    size_t norder = 0;
-    for (const auto& o : T.order) norder += o.size();
-    Part p_ints{T.ints.size() * 4, 0}, p_free{T.free32.size() * 4, 0}, p_order{norder * 4, 0}, p_freem{T.freem.size(), 0},
-        p_comps{ncomp * sizeof(LmBatchComp), 0}, p_res{ncomp * LM_BATCH_RES * 8, 0},
-        p_hist{hist_cap > 0 ? ncomp * (size_t)hist_cap * 32 : 0, 0}, p_ws{(size_t)T.ws_doubles * 8, 0};
-    size_t total = 0, upload = 0;
-    {
-        Part* parts[] = {&p_comps, &p_ints, &p_free, &p_order, &p_freem, &p_res, &p_hist, &p_ws};
-        for (Part* q : parts) {
-            q->off = total;
-            total += (std::max<size_t>(q->bytes, 8) + 255) / 256 * 256;
-            if (q == &p_freem) upload = total;
-        }
+    const LmBatchTableLayout lay = lm_batch_table_layout(T);
+    Part p_res{ncomp * LM_BATCH_RES * 8, 0}, p_hist{hist_cap > 0 ? ncomp * (size_t)hist_cap * 32 : 0, 0}, p_ws{(size_t)T.ws_doubles * 8, 0};
+    size_t total = lay.bytes;
+    for (Part* q : {&p_res, &p_hist, &p_ws}) {
+        q->off = total;
+        total += (std::max<size_t>(q->bytes, 8) + 255) / 256 * 256;
     }
     if (ws->dev_bytes < total) {
         LMB_CHK(hipStreamSynchronize(stream));
@@ -470,39 +506,20 @@ int device_lm_batch(hipStream_t stream, const LmBatchProblem& P, const LmBatchTa
         LMB_CHK(hipMalloc(&ws->dev, total + total / 4));
         ws->dev_bytes = total + total / 4;
     }
-    std::vector<char> stage(upload, 0);
-    std::memcpy(stage.data() + p_comps.off, T.comps.data(), p_comps.bytes);
-    if (p_ints.bytes) std::memcpy(stage.data() + p_ints.off, T.ints.data(), p_ints.bytes);
-    if (p_free.bytes) std::memcpy(stage.data() + p_free.off, T.free32.data(), p_free.bytes);
-    {
-        size_t at = p_order.off;
-        for (const auto& o : T.order) { if (!o.empty()) std::memcpy(stage.data() + at, o.data(), o.size() * 4); at += o.size() * 4; }
-    }
-    std::memcpy(stage.data() + p_freem.off, T.freem.data(), p_freem.bytes);
+    std::vector<char> stage(lay.bytes, 0);
+    lm_batch_stage_tables(T, lay, stage.data());
     char* const base = static_cast<char*>(ws->dev);
-    LMB_CHK(hipMemcpyAsync(base, stage.data(), upload, hipMemcpyHostToDevice, stream));
+    LMB_CHK(hipMemcpyAsync(base, stage.data(), lay.bytes, hipMemcpyHostToDevice, stream));
 
-    BatchDev B{};
-    B.x = P.x; B.lo = P.lo; B.hi = P.hi; B.cam = P.cam; B.pt = P.pt; B.obs = P.obs;
-    B.comps = reinterpret_cast<const LmBatchComp*>(base + p_comps.off);
-    B.ints = reinterpret_cast<const int*>(base + p_ints.off);
-    B.free32 = reinterpret_cast<const int*>(base + p_free.off);
-    B.order = reinterpret_cast<const int*>(base + p_order.off);
-    B.freem = reinterpret_cast<const unsigned char*>(base + p_freem.off);
-    B.res = reinterpret_cast<double*>(base + p_res.off);
-    B.hist = hist_cap > 0 ? reinterpret_cast<double*>(base + p_hist.off) : nullptr;
-    B.ws = reinterpret_cast<double*>(base + p_ws.off);
-    B.R = opt.model; B.maxiters = opt.maxiters; B.hist_cap = hist_cap;
-    B.tau = opt.tau; B.eps1 = opt.eps1; B.eps2 = opt.eps2; B.eps3 = opt.eps3;
-    // one launch per class that occurs, its components heaviest first
-    const int n0 = (int)T.order[0].size(), n1 = (int)T.order[1].size(), n2 = (int)T.order[2].size();
-    LMB_CHK(launch_class<2>(stream, B, n0 + n1, n2));
-    LMB_CHK(launch_class<1>(stream, B, n0, n1));
-    LMB_CHK(launch_class<0>(stream, B, 0, n0));
-    LMB_CHK(hipMemcpyAsync(res->data(), B.res, p_res.bytes, hipMemcpyDeviceToHost, stream));
+    // a launch of one member
+    const LmBatchMembers M{0, reinterpret_cast<double*>(base + p_res.off), 0, reinterpret_cast<double*>(base + p_hist.off), 0,
+                           reinterpret_cast<double*>(base + p_ws.off), 0, nullptr, 0, 1};
+    const int n[LM_BATCH_CLASSES] = {(int)T.order[0].size(), (int)T.order[1].size(), (int)T.order[2].size()};
+    if (int e = lm_batch_launch(stream, P, base, lay, n, opt, hist_cap, M)) return e;
+    LMB_CHK(hipMemcpyAsync(res->data(), M.res, p_res.bytes, hipMemcpyDeviceToHost, stream));
     if (hist_cap > 0) {
         hist->resize(ncomp * (size_t)hist_cap * 4);
-        LMB_CHK(hipMemcpyAsync(hist->data(), B.hist, p_hist.bytes, hipMemcpyDeviceToHost, stream));
+        LMB_CHK(hipMemcpyAsync(hist->data(), M.hist, p_hist.bytes, hipMemcpyDeviceToHost, stream));
     }
     LMB_CHK(hipStreamSynchronize(stream));
     return 0;

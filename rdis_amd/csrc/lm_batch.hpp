@@ -212,6 +212,32 @@ inline int lm_batch_prepare(const LmBatchBlocks& B, int64_t ncomp, const int64_t
     return 0;
 }
 
+// where the tables lie in one device block, uploaded in one copy: comps | ints | free32 | order (class 0, 1, 2) | freem,
+// each part on a 256-byte boundary; `bytes` is the block's size.  Nothing in it depends on x.
+struct LmBatchTableLayout { size_t comps, ints, free32, order, freem, bytes; };
+inline LmBatchTableLayout lm_batch_table_layout(const LmBatchTables& T) {
+    size_t norder = 0;
+    for (const auto& o : T.order) norder += o.size();
+    LmBatchTableLayout L{};
+    size_t at = 0;
+    auto take = [&at](size_t bytes) { const size_t off = at; at += (std::max<size_t>(bytes, 8) + 255) / 256 * 256; return off; };
+    L.comps = take(T.comps.size() * sizeof(LmBatchComp)); L.ints = take(T.ints.size() * 4); L.free32 = take(T.free32.size() * 4);
+    L.order = take(norder * 4); L.freem = take(T.freem.size());
+    L.bytes = at;
+    return L;
+}
+// the block's host image: stage[L.bytes], zero where no table lies
+inline void lm_batch_stage_tables(const LmBatchTables& T, const LmBatchTableLayout& L, char* stage) {
+    std::fill(stage, stage + L.bytes, (char)0);
+    auto put = [stage](size_t off, const void* src, size_t bytes) { if (bytes) std::copy_n(static_cast<const char*>(src), bytes, stage + off); };
+    put(L.comps, T.comps.data(), T.comps.size() * sizeof(LmBatchComp));
+    put(L.ints, T.ints.data(), T.ints.size() * 4);
+    put(L.free32, T.free32.data(), T.free32.size() * 4);
+    size_t at = L.order;
+    for (const auto& o : T.order) { put(at, o.data(), o.size() * 4); at += o.size() * 4; }
+    put(L.freem, T.freem.data(), T.freem.size());
+}
+
 // a component's row of results: fret, finit, iterations, stop code, residual evaluations, Jacobian evaluations, linear solves,
 // final mu, active camera blocks, active point blocks, history records (also those beyond the caller's capacity), unused
 constexpr int LM_BATCH_RES = 12;
@@ -236,6 +262,26 @@ struct LmBatchWorkspace {
     LmBatchWorkspace& operator=(const LmBatchWorkspace&) = delete;
     ~LmBatchWorkspace();
 };
+// The members of one launch (the member is the grid's second dimension): member m solves every component from, and into,
+// P.x + m x_stride, in the workspace replica ws + m ws_stride, and leaves its rows at res + m res_stride ([ncomp][LM_BATCH_RES])
+// and hist + m hist_stride ([ncomp][hist_cap][4]; unused when hist_cap is 0).  Strides in doubles.  lo, hi, the factor
+// arrays and the tables are shared.  A member's bits depend neither on `count` nor on its place among the members.
+// xout + m xout_stride ([nfree], the free list's order) receives the member's clamped results beside x itself: a plan keeps
+// them for its fetch.  xout null: rdis_hip_lm_batch's launch -- one member (count 1), the strides unused, and the kernel's
+// instantiation without member terms; the bits are the same.
+struct LmBatchMembers {
+    long long x_stride;
+    double* res; long long res_stride;
+    double* hist; long long hist_stride;
+    double* ws; long long ws_stride;
+    double* xout; long long xout_stride;
+    int count;
+};
+// Enqueues the solve of every component of an uploaded table block (lm_batch_table_layout; n: the components of each class)
+// for M.count members: one launch per class that occurs, heaviest class first.  No copy, no wait, no allocation.
+// Returns 0 or a hipError_t.
+int lm_batch_launch(hipStream_t stream, const LmBatchProblem& P, const void* tables, const LmBatchTableLayout& lay, const int (&n)[LM_BATCH_CLASSES],
+                    const LmBatchOptions& opt, int64_t hist_cap, const LmBatchMembers& M);
 // Solves every component of T (lm_batch_prepare) from the currently assigned x, which is updated in place: the free
 // variables end at the clamped results.  res: [ncomp][LM_BATCH_RES]; hist: [ncomp][hist_cap][4] (hist_cap 0: none).
 // One upload, one launch per class that occurs, the downloads, one wait.  Returns 0 or a hipError_t.

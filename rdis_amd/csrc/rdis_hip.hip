@@ -2857,18 +2857,19 @@ extern "C" int rdis_hip_lm_optimize(rdis_hip_problem* p, int64_t nfree, const in
 // components' sizes and factor pairs by lm_batch_prepare.
 static_assert(LM_BATCH_EINVAL == RDIS_HIP_EINVAL && LM_BATCH_ERANGE == RDIS_HIP_ERANGE && LM_BATCH_MAX_CAMERAS == RDIS_HIP_LM_BATCH_MAX_CAMERAS,
               "lm_batch.hpp restates include/rdis_hip.h");
-extern "C" int rdis_hip_lm_batch(rdis_hip_problem* p, int64_t ncomp, const int64_t* free_ptr, const int64_t* free_vid,
-                                 const int64_t* fac_ptr, const int64_t* fac_id, double* x_inout, int32_t maxiters, double ftol,
-                                 int32_t model, double* fret, double* delta, double* info8, double* hist4, int64_t hist_cap,
-                                 int64_t* nhist) {
-    if (!p) return RDIS_HIP_EINVAL;
+namespace {
+// What rdis_hip_lm_batch and rdis_hip_lm_plan_create check and build before x is touched (`who` names the entry in the
+// messages): the problem, the model, the lists, the components' independence, then lm_batch_prepare's tables.
+int lm_batch_tables(rdis_hip_problem* p, const std::string& who, int64_t ncomp, const int64_t* free_ptr, const int64_t* free_vid,
+                    const int64_t* fac_ptr, const int64_t* fac_id, int R, LmBatchTables& T) {
     rdis_hip_ctx* c = p->ctx;
-    if (p->kind != KIND_BA) return fail(c, RDIS_HIP_EINVAL, "lm_batch: bundle adjustment problems only");
-    if (ncomp < 0 || !free_ptr || !fac_ptr || maxiters < 1 || hist_cap < 0) return fail(c, RDIS_HIP_EINVAL, "lm_batch: bad arguments");
-    const int R = model & 15;   // (the Schur bits of rdis_hip_lm_optimize are ignored)
-    if (R != 1 && R != 2) return fail(c, RDIS_HIP_EINVAL, "lm_batch: residual model must be 1 or 2");
-    if (p->ncam_blocks <= 0 && p->F > 0) return fail(c, RDIS_HIP_EINVAL, "lm_batch: the factors' camera and point blocks overlap");
-    auto relabel = [](std::string m) { return m.rfind("plan_create", 0) == 0 ? "lm_batch" + m.substr(11) : m; };
+    if (R != 1 && R != 2) return fail(c, RDIS_HIP_EINVAL, who + ": residual model must be 1 or 2");
+    if (p->ncam_blocks <= 0 && p->F > 0) return fail(c, RDIS_HIP_EINVAL, who + ": the factors' camera and point blocks overlap");
+    auto relabel = [&who](std::string m) {
+        for (const char* from : {"plan_create", "lm_batch"})
+            if (m.rfind(from, 0) == 0) return who + m.substr(std::strlen(from));
+        return m;
+    };
     std::string why;
     if (int rc = plan_index_check(ncomp, free_ptr, free_vid, fac_ptr, fac_id, &why)) return fail(c, rc, relabel(why));
     USE_DEVICE(c);
@@ -2889,8 +2890,23 @@ extern "C" int rdis_hip_lm_batch(rdis_hip_problem* p, int64_t ncomp, const int64
     for (int64_t f = 0; f < p->F && layout; ++f)
         layout = p->h_cam[(size_t)f] % 9 == 0 && p->h_cam[(size_t)f] < 9 * ncams && (p->h_pt[(size_t)f] - 9 * ncams) % 3 == 0;
     const LmBatchBlocks blocks{p->N, p->F, p->h_cam.data(), p->h_pt.data(), p->h_block_of.data(), p->h_ptblock_of.data(), layout, ncams};
+    if ((rc = lm_batch_prepare(blocks, ncomp, free_ptr, free_vid, fac_ptr, fac_id, R, T, &why))) return fail(c, rc, relabel(why));
+    return 0;
+}
+}  // namespace
+
+extern "C" int rdis_hip_lm_batch(rdis_hip_problem* p, int64_t ncomp, const int64_t* free_ptr, const int64_t* free_vid,
+                                 const int64_t* fac_ptr, const int64_t* fac_id, double* x_inout, int32_t maxiters, double ftol,
+                                 int32_t model, double* fret, double* delta, double* info8, double* hist4, int64_t hist_cap,
+                                 int64_t* nhist) {
+    if (!p) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = p->ctx;
+    if (p->kind != KIND_BA) return fail(c, RDIS_HIP_EINVAL, "lm_batch: bundle adjustment problems only");
+    if (ncomp < 0 || !free_ptr || !fac_ptr || maxiters < 1 || hist_cap < 0) return fail(c, RDIS_HIP_EINVAL, "lm_batch: bad arguments");
+    const int R = model & 15;   // (the Schur bits of rdis_hip_lm_optimize are ignored)
     LmBatchTables T;
-    if ((rc = lm_batch_prepare(blocks, ncomp, free_ptr, free_vid, fac_ptr, fac_id, R, T, &why))) return fail(c, rc, why);
+    int rc = lm_batch_tables(p, "lm_batch", ncomp, free_ptr, free_vid, fac_ptr, fac_id, R, T);
+    if (rc) return rc;
     const int64_t nfree = free_ptr[ncomp];
     if (x_inout && nfree > 0 && (rc = rdis_hip_set_x(p, nfree, free_vid, x_inout))) return rc;
     const LmBatchProblem P{p->x.as<double>(), p->lo.as<double>(), p->hi.as<double>(), p->cam.as<int>(), p->pt.as<int>(), p->obs.as<double2>()};
@@ -2914,6 +2930,197 @@ extern "C" int rdis_hip_lm_batch(rdis_hip_problem* p, int64_t ncomp, const int64
             std::memcpy(hist4 + (size_t)cc * (size_t)cap * 4, hist.data() + (size_t)cc * (size_t)cap * 4, (size_t)n * 32);
         }
     }
+    return 0;
+}
+
+// =====================================================================================
+// Levenberg-Marquardt plans: lm_batch's tables built and uploaded once, solves that stay on the stream, on the problem's x
+// or on the members of a population (the member is the grid's second dimension of lm_batch.hip's kernel)
+// =====================================================================================
+struct rdis_hip_lm_plan {
+    rdis_hip_problem* prob = nullptr;
+    int64_t ncomp = 0, nfree = 0, hist_cap = 0;
+    int R = 1;
+    LmBatchTableLayout lay{};
+    int ncls[LM_BATCH_CLASSES] = {0, 0, 0};
+    LmPlanLayout layout;                    // replica_layout.hpp: the outputs of a solve's members, the workspace of a launch's
+    DevBuf tables, out, work;
+    int64_t workspace_bytes = (int64_t)1 << 30;   // option "workspace_bytes": bounds `work`
+    // the last solve: 0 none, 1 rdis_hip_lm_plan_solve, 2 rdis_hip_lm_plan_solve_population (of last_count members).  Nothing of the
+    // population is kept: a fetch reads the plan's own `out` block
+    int last_kind = 0;
+    int64_t last_count = 0, last_per_launch = 0, last_launches = 0;
+    std::vector<double> h_res, h_hist;      // fetch's staging
+    double* res_dev(int64_t count) const { return layout.out.at<double>(out.p, LM_PLAN_RES, count); }
+    double* hist_dev(int64_t count) const { return layout.out.at<double>(out.p, LM_PLAN_HIST, count); }
+    double* x_dev(int64_t count) const { return layout.out.at<double>(out.p, LM_PLAN_X, count); }
+};
+
+namespace {
+// `count` members from x0, a member's stride x_stride: outputs for all of them, workspace replicas for the members of one
+// launch, the launches.  After the first call of a kind and size: no allocation; never an upload, a download or a wait.
+int lm_plan_enqueue(rdis_hip_lm_plan* L, double* x0, long long x_stride, int64_t count, int32_t maxiters, double ftol) {
+    rdis_hip_problem* p = L->prob;
+    rdis_hip_ctx* c = p->ctx;
+    L->last_per_launch = 0; L->last_launches = 0;
+    if (L->ncomp == 0) return 0;
+    const int64_t per = members_per_launch(count, L->workspace_bytes, L->layout.work.member_bytes());
+    int rc = ensure(c, L->out, (size_t)L->layout.out.total_bytes(count));
+    if (!rc) rc = ensure(c, L->work, (size_t)L->layout.work.total_bytes(per));
+    if (rc) return rc;
+    const LmBatchOptions o{maxiters, L->R, 1e-3, 1e-15, 1e-15, ftol};
+    const int classes = (L->ncls[0] > 0) + (L->ncls[1] > 0) + (L->ncls[2] > 0);
+    for (int64_t m0 = 0; m0 < count; m0 += per) {
+        const int64_t n = std::min(per, count - m0);
+        const LmBatchProblem P{x0 + m0 * x_stride, p->lo.as<double>(), p->hi.as<double>(), p->cam.as<int>(), p->pt.as<int>(), p->obs.as<double2>()};
+        const LmBatchMembers M{x_stride, L->res_dev(count) + m0 * L->layout.out.doubles(LM_PLAN_RES), L->layout.out.doubles(LM_PLAN_RES),
+                               L->hist_dev(count) + m0 * L->layout.out.doubles(LM_PLAN_HIST), L->layout.out.doubles(LM_PLAN_HIST),
+                               L->layout.work.at<double>(L->work.p, LM_PLAN_WS, per), L->layout.work.doubles(LM_PLAN_WS),
+                               L->x_dev(count) + m0 * L->layout.out.doubles(LM_PLAN_X), L->layout.out.doubles(LM_PLAN_X), (int)n};
+        const int e = lm_batch_launch(c->stream, P, L->tables.p, L->lay, L->ncls, o, L->hist_cap, M);
+        if (e != 0) return fail(c, RDIS_HIP_EDEVICE, std::string("lm_plan_solve: ") + hipGetErrorString((hipError_t)e));
+        L->last_launches += classes;
+    }
+    L->last_per_launch = per;
+    return 0;
+}
+
+// the outputs of the last solve's `count` members: one download each of the members' x, the result rows and the history, one wait
+int lm_plan_download(rdis_hip_lm_plan* L, int64_t count, double* x_out, double* fret, double* delta, double* info8, double* hist4, int64_t* nhist) {
+    rdis_hip_ctx* c = L->prob->ctx;
+    const size_t rows = (size_t)count * (size_t)L->ncomp;
+    if (rows == 0) return 0;
+    const bool want_x = x_out && L->nfree > 0;
+    if (!(want_x || fret || delta || info8 || hist4 || nhist)) return 0;
+    const bool want_hist = hist4 && L->hist_cap > 0;
+    if (want_x) HIPCHK(c, hipMemcpyAsync(x_out, L->x_dev(count), (size_t)count * (size_t)L->nfree * 8, hipMemcpyDeviceToHost, c->stream));
+    L->h_res.resize(rows * LM_BATCH_RES);
+    HIPCHK(c, hipMemcpyAsync(L->h_res.data(), L->res_dev(count), rows * LM_BATCH_RES * 8, hipMemcpyDeviceToHost, c->stream));
+    if (want_hist) {
+        L->h_hist.resize(rows * (size_t)L->hist_cap * 4);
+        HIPCHK(c, hipMemcpyAsync(L->h_hist.data(), L->hist_dev(count), rows * (size_t)L->hist_cap * 32, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t cc = 0; cc < rows; ++cc) {   // (member-major in both: row cc is component cc % ncomp of member cc / ncomp)
+        const double* r = L->h_res.data() + cc * LM_BATCH_RES;
+        if (fret) fret[cc] = r[0];
+        if (delta) delta[cc] = r[0] - r[1];
+        if (info8) {
+            double* i8 = info8 + 8 * cc;
+            i8[0] = r[2]; i8[1] = r[3]; i8[2] = r[4]; i8[3] = r[5]; i8[4] = r[6]; i8[5] = r[7]; i8[6] = r[8]; i8[7] = r[9];
+        }
+        if (nhist) nhist[cc] = (int64_t)r[10];
+        if (want_hist) {
+            const int64_t n = std::min<int64_t>((int64_t)r[10], L->hist_cap);
+            std::memcpy(hist4 + cc * (size_t)L->hist_cap * 4, L->h_hist.data() + cc * (size_t)L->hist_cap * 4, (size_t)n * 32);
+        }
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" int rdis_hip_lm_plan_create(rdis_hip_problem* p, int64_t ncomp, const int64_t* free_ptr, const int64_t* free_vid,
+                                       const int64_t* fac_ptr, const int64_t* fac_id, int32_t model, int64_t hist_cap, rdis_hip_lm_plan** out) {
+    if (!p || !out) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = p->ctx;
+    if (p->kind != KIND_BA) return fail(c, RDIS_HIP_EINVAL, "lm_plan_create: bundle adjustment problems only");
+    if (ncomp < 0 || !free_ptr || !fac_ptr || hist_cap < 0) return fail(c, RDIS_HIP_EINVAL, "lm_plan_create: bad arguments");
+    const int R = model & 15;
+    LmBatchTables T;
+    int rc = lm_batch_tables(p, "lm_plan_create", ncomp, free_ptr, free_vid, fac_ptr, fac_id, R, T);
+    if (rc) return rc;
+    if ((double)ncomp * (double)std::max<int64_t>(hist_cap, 1) >= 1.0e15) return fail(c, RDIS_HIP_ERANGE, "lm_plan_create: history too large");
+    std::unique_ptr<rdis_hip_lm_plan> L(new (std::nothrow) rdis_hip_lm_plan);
+    if (!L) return fail(c, RDIS_HIP_ENOMEM, "lm_plan_create: host allocation");
+    L->prob = p; L->ncomp = ncomp; L->nfree = free_ptr[ncomp]; L->hist_cap = hist_cap; L->R = R;
+    for (int k = 0; k < LM_BATCH_CLASSES; ++k) L->ncls[k] = (int)T.order[k].size();
+    L->lay = lm_batch_table_layout(T);
+    L->layout = lm_plan_layout(ncomp, LM_BATCH_RES, hist_cap, L->nfree, T.ws_doubles);
+    // the one upload of the plan's life: nothing in the tables depends on x
+    std::vector<char> stage(L->lay.bytes);
+    lm_batch_stage_tables(T, L->lay, stage.data());
+    if ((rc = upload(c, L->tables, stage.data(), stage.size()))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (the staging vector ends here)
+    *out = L.release();
+    return 0;
+}
+
+extern "C" void rdis_hip_lm_plan_destroy(rdis_hip_lm_plan* L) {
+    if (!L) return;
+    if (L->prob) { (void)make_current(L->prob->ctx); (void)hipStreamSynchronize(L->prob->ctx->stream); }
+    delete L;
+}
+
+extern "C" int rdis_hip_lm_plan_solve(rdis_hip_lm_plan* L, int32_t maxiters, double ftol) {
+    if (!L) return RDIS_HIP_EINVAL;
+    rdis_hip_problem* p = L->prob;
+    rdis_hip_ctx* c = p->ctx;
+    if (maxiters < 1) return fail(c, RDIS_HIP_EINVAL, "lm_plan_solve: maxiters must be positive");
+    USE_DEVICE(c);
+    const int rc = lm_plan_enqueue(L, p->x.as<double>(), 0, 1, maxiters, ftol);
+    if (rc) return rc;
+    L->last_kind = 1; L->last_count = 1;
+    return 0;
+}
+
+extern "C" int rdis_hip_lm_plan_fetch(rdis_hip_lm_plan* L, double* x_out, double* fret, double* delta, double* info8, double* hist4, int64_t* nhist) {
+    if (!L) return RDIS_HIP_EINVAL;
+    rdis_hip_problem* p = L->prob;
+    rdis_hip_ctx* c = p->ctx;
+    if (L->last_kind != 1)
+        return fail(c, RDIS_HIP_EINVAL, L->last_kind == 0 ? "lm_plan_fetch: nothing was solved yet" : "lm_plan_fetch: the last solve was a population solve (rdis_hip_lm_plan_fetch_population)");
+    USE_DEVICE(c);
+    return lm_plan_download(L, 1, x_out, fret, delta, info8, hist4, nhist);
+}
+
+extern "C" int rdis_hip_lm_plan_solve_population(rdis_hip_lm_plan* L, rdis_hip_population* pop, int64_t first, int64_t count, int32_t maxiters, double ftol) {
+    if (!L || !pop) return RDIS_HIP_EINVAL;
+    rdis_hip_problem* p = L->prob;
+    rdis_hip_ctx* c = p->ctx;
+    if (maxiters < 1) return fail(c, RDIS_HIP_EINVAL, "lm_plan_solve_population: maxiters must be positive");
+    if (pop->prob != p) return fail(c, RDIS_HIP_EINVAL, "lm_plan_solve_population: the population belongs to another problem than the plan's");
+    if (count < 1 || first < 0 || first > pop->nmembers || count > pop->nmembers - first)
+        return fail(c, RDIS_HIP_EINVAL, "lm_plan_solve_population: members out of range (count >= 1, first + count <= nmembers)");
+    if ((double)count * (double)std::max<int64_t>(L->ncomp * std::max<int64_t>(L->hist_cap, 1), 1) >= 1.0e15)
+        return fail(c, RDIS_HIP_ERANGE, "lm_plan_solve_population: too many members");
+    USE_DEVICE(c);
+    pop->eval_valid = false; pop->best_current = false;   // X is written: the values of the last evaluation are stale
+    const int rc = lm_plan_enqueue(L, pop->row(first), (long long)p->N, count, maxiters, ftol);
+    if (rc) return rc;
+    L->last_kind = 2; L->last_count = count;
+    return 0;
+}
+
+extern "C" int rdis_hip_lm_plan_fetch_population(rdis_hip_lm_plan* L, double* x_out, double* fret, double* delta, double* info8, double* hist4,
+                                                 int64_t* nhist) {
+    if (!L) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = L->prob->ctx;
+    if (L->last_kind != 2)
+        return fail(c, RDIS_HIP_EINVAL, L->last_kind == 0 ? "lm_plan_fetch_population: nothing was solved yet" : "lm_plan_fetch_population: the last solve was not a population solve (rdis_hip_lm_plan_fetch)");
+    USE_DEVICE(c);
+    return lm_plan_download(L, L->last_count, x_out, fret, delta, info8, hist4, nhist);
+}
+
+extern "C" int rdis_hip_lm_plan_set_option(rdis_hip_lm_plan* L, const char* name, int64_t value) {
+    if (!L || !name) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = L->prob->ctx;
+    const std::string n(name);
+    if (n != "workspace_bytes") return fail(c, RDIS_HIP_EINVAL, "lm_plan_set_option: unknown option '" + n + "' (workspace_bytes)");
+    if (value < 0) return fail(c, RDIS_HIP_EINVAL, "lm_plan_set_option: workspace_bytes must be >= 0");
+    L->workspace_bytes = value;
+    return 0;
+}
+
+extern "C" int rdis_hip_lm_plan_get_info(rdis_hip_lm_plan* L, const char* name, int64_t* value) {
+    if (!L || !name || !value) return RDIS_HIP_EINVAL;
+    const std::string n(name);
+    if (n == "members_per_launch") *value = L->last_per_launch;
+    else if (n == "launches") *value = L->last_launches;
+    else if (n == "device_bytes") *value = (int64_t)(L->tables.bytes + L->out.bytes + L->work.bytes);
+    else if (n == "workspace_bytes") *value = L->workspace_bytes;
+    else if (n == "member_workspace_bytes") *value = L->layout.work.member_bytes();
+    else return fail(L->prob->ctx, RDIS_HIP_EINVAL, "lm_plan_get_info: unknown name '" + n + "' (members_per_launch, launches, device_bytes, workspace_bytes, "
+                                                    "member_workspace_bytes)");
     return 0;
 }
 

@@ -3,6 +3,8 @@
 // rdis_hip_population_eval and both forms of rdis_hip_population_eval_grad) give every member of a launch a replica of some
 // per-solve arrays, in one buffer laid out [R][part 0] [R][part 1] ...  A ReplicaLayout names the parts and their bytes per
 // member; the buffer's size, the members a budget allows and every pointer and stride the kernels are handed come from it.
+// The Levenberg-Marquardt plan's solves (rdis_hip_lm_plan_solve, rdis_hip_lm_plan_solve_population) describe their two buffers the
+// same way (lm_plan_layout) and split their members by the same rule.
 // Pure host functions: no HIP call, no plan, no population (tests/cpp/replica_layout_test.cpp runs them without a device).
 #pragma once
 #include <algorithm>
@@ -81,14 +83,29 @@ inline ReplicaLayout population_grad_list_layout(int64_t nslots, int64_t partial
     return ReplicaLayout(2, 8 * nslots, 8 * std::max<int64_t>(partials, 1));
 }
 
+// ---- rdis_hip_lm_plan_solve, rdis_hip_lm_plan_solve_population ----
+// two buffers.  `out`, for every member of the solve (kept until fetched): a result row of res_doubles doubles a component,
+// hist_cap history records of four doubles a component, and the member's clamped results x[nfree] in free-list order.  `work`,
+// for the members of one launch only -- the one the budget (the plan option workspace_bytes) is charged with: the components'
+// workspace slices, ws_doubles doubles in all.
+enum { LM_PLAN_RES = 0, LM_PLAN_HIST = 1, LM_PLAN_X = 2 };
+enum { LM_PLAN_WS = 0 };
+struct LmPlanLayout { ReplicaLayout out, work; };
+inline LmPlanLayout lm_plan_layout(int64_t ncomp, int64_t res_doubles, int64_t hist_cap, int64_t nfree, int64_t ws_doubles) {
+    return LmPlanLayout{ReplicaLayout(3, 8 * res_doubles * ncomp, 8 * 4 * hist_cap * ncomp, 8 * nfree), ReplicaLayout(1, 8 * ws_doubles)};
+}
+
 // Members of one launch: the member is the grid's second dimension (at most 65535) and every member of a launch has
 // `member_bytes` of replicas within `budget_bytes` -- at least one member a launch, whatever the budget; a replica of nothing
-// bounds nothing.  No bit of a result depends on it.  The one rule of the five entries.  What its callers can pass:
+// bounds nothing.  No bit of a result depends on it.  The one rule of the five entries and of the Levenberg-Marquardt plan's two
+// solve entries.  What its callers can pass:
 //   count         >= 1: every entry refuses or returns before it asks (nstarts < 1, count < 1; a population has a member);
-//   budget_bytes  >= 0: the plan option starts_workspace_bytes and the population options eval_workspace_bytes and
-//                 grad_workspace_bytes are refused below zero by their option rules (a negative budget would give 1, as zero does);
+//   budget_bytes  >= 0: the plan option starts_workspace_bytes, the population options eval_workspace_bytes and
+//                 grad_workspace_bytes and the Levenberg-Marquardt plan's option workspace_bytes are refused below zero by their
+//                 option rules (a negative budget would give 1, as zero does);
 //   member_bytes  >= 0, and 0 only from the two solve entries (a launch that runs nothing but the tiny-component solver on
-//                 per-factor rotations): the evaluation has at least one partial, 8 bytes, and the gradient's branches at least
+//                 per-factor rotations) and from a Levenberg-Marquardt plan whose components are all empty (no free variable,
+//                 no factor: ws_doubles 0; a plan of no component returns before it asks): the evaluation has at least one partial, 8 bytes, and the gradient's branches at least
 //                 8 (9 + 3 + 1) and 8 (0 + 1) -- its "no factor" branch, the only one without scratch, does not ask.
 inline int64_t members_per_launch(int64_t count, int64_t budget_bytes, int64_t member_bytes) {
     const int64_t fit = member_bytes > 0 ? std::max<int64_t>(1, budget_bytes / member_bytes) : count;
