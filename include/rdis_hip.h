@@ -186,8 +186,20 @@ int rdis_hip_lm_optimize(rdis_hip_problem *p, int64_t nfree, const int64_t *free
  * A component with more than RDIS_HIP_LM_BATCH_MAX_CAMERAS camera blocks that hold a free variable makes the whole call
  * fail with RDIS_HIP_ERANGE before anything is solved (the message names it): such a component belongs on
  * rdis_hip_lm_optimize.  Points and factors per component are not limited.  Two listed factors of a component that join the
- * same camera and point: RDIS_HIP_EINVAL.  Returns 0 also when components stop with codes 4, 5 or 7. */
+ * same camera and point: RDIS_HIP_EINVAL.  Returns 0 also when components stop with codes 4, 5 or 7.
+ *
+ * RDIS_HIP_LM_WIDE, a bit of residual_model read by rdis_hip_lm_batch and rdis_hip_lm_plan_create (rdis_hip_lm_optimize
+ * ignores it): components of 17 to RDIS_HIP_LM_WIDE_MAX_CAMERAS active camera blocks are solved too, as a fourth, wide class
+ * -- the same iteration by one workgroup of 512 lanes, the reduced system (up to 576 unknowns) in the component's workspace
+ * slice instead of the LDS, factorised in panels of 16 columns on the matrix cores.  Nothing changes for components of at
+ * most 16 camera blocks: same class, same bits.  More than RDIS_HIP_LM_WIDE_MAX_CAMERAS: RDIS_HIP_ERANGE as above, the
+ * message naming that limit.  A wide component needs up to 1.5 MB of workspace per member.
+ * Which entry for which size: up to 64 cameras, many components or many population members at once -- this entry and its
+ * plans with the bit set (one launch, no host traffic); one large component alone (full ladybug, 7776 points) --
+ * rdis_hip_lm_optimize, whose launches use the whole device where a wide component has one workgroup. */
 #define RDIS_HIP_LM_BATCH_MAX_CAMERAS 16
+#define RDIS_HIP_LM_WIDE 0x100
+#define RDIS_HIP_LM_WIDE_MAX_CAMERAS 64
 int rdis_hip_lm_batch(rdis_hip_problem *p, int64_t ncomp, const int64_t *free_ptr, const int64_t *free_vid,
                       const int64_t *fac_ptr, const int64_t *fac_id, double *x_inout, int32_t maxiters, double ftol,
                       int32_t residual_model, double *fret, double *delta, double *info8, double *hist4,
@@ -496,11 +508,12 @@ int rdis_hip_plan_objective_device(rdis_hip_plan *plan, void **dev_ptr);
  * an alternation of camera and point plans runs on the stream from end to end.
  *   rdis_hip_lm_plan_create   everything rdis_hip_lm_batch checks before it assigns x, with its codes (messages are
  *                             labelled lm_plan_create): bundle adjustment only, residual_model 1 or 2, RDIS_HIP_EOVERLAP,
- *                             ids in range, more than RDIS_HIP_LM_BATCH_MAX_CAMERAS active camera blocks RDIS_HIP_ERANGE,
+ *                             ids in range, more than RDIS_HIP_LM_BATCH_MAX_CAMERAS active camera blocks RDIS_HIP_ERANGE
+ *                             (with RDIS_HIP_LM_WIDE in residual_model: more than RDIS_HIP_LM_WIDE_MAX_CAMERAS),
  *                             two listed factors joining one camera and point RDIS_HIP_EINVAL.  hist_cap: history records
  *                             kept per component (0: none)
  *   rdis_hip_lm_plan_solve    every component from the problem's currently assigned x, the clamped results left assigned:
- *                             at most three launches (one per class that occurs); bit for bit rdis_hip_lm_batch with
+ *                             at most four launches (one per class that occurs); bit for bit rdis_hip_lm_batch with
  *                             x_inout = NULL
  *   rdis_hip_lm_plan_fetch    waits, then the last solve's outputs with the shapes and meaning of rdis_hip_lm_batch's
  *                             (hist4[c][hist_cap][4] with the plan's hist_cap); x_out: the solve's clamped results,

@@ -35,6 +35,10 @@ class LmResult:
 EXIT_NAMES = {0: "ftol", 1: "gtol", 2: "gg==0", 3: "itmax", 4: "dbrent-itmax", 5: "nan",
               6: "empty", 7: "sync-timeout"}
 STATUS_ROLLED_BACK = 0x100
+# include/rdis_hip.h: the bit of residual_model that lets rdis_hip_lm_batch / rdis_hip_lm_plan_create take components of 17 to
+# LM_WIDE_MAX_CAMERAS active camera blocks
+LM_WIDE = 0x100
+LM_WIDE_MAX_CAMERAS = 64
 
 _ERRORS = {-1: "EINVAL", -2: "ENOMEM", -3: "EDEVICE", -4: "EOVERLAP", -5: "ERANGE"}
 
@@ -368,10 +372,12 @@ class Problem:
                         nfev=int(info[2]), njev=int(info[3]), nsolve=int(info[4]), mu=float(info[5]),
                         camera_blocks=int(info[6]), point_blocks=int(info[7]), history=hist[:min(int(nh[0]), hist.shape[0])].copy())
 
-    def lm_batch(self, free_ptr, free_vid, fac_ptr, fac_id, x=None, maxiters=25, ftol=3e-8, history=64, model=1):
+    def lm_batch(self, free_ptr, free_vid, fac_ptr, fac_id, x=None, maxiters=25, ftol=3e-8, history=64, model=1, wide=False):
         """Levenberg-Marquardt for a batch of small independent components (the lists of cgd_batch / components), one
         workgroup per component, one call.  x: start values concatenated in free-variable order (None: the assigned x).
+        wide: components of 17 to LM_WIDE_MAX_CAMERAS active camera blocks are solved too (RDIS_HIP_LM_WIDE) instead of refused.
         Returns a list of LmResult, one per component; the variables are left assigned to the results."""
+        model = int(model) | (LM_WIDE if wide else 0)
         free_ptr, free_vid, fac_ptr, fac_id = _i(free_ptr), _i(free_vid), _i(fac_ptr), _i(fac_id)
         nc = free_ptr.shape[0] - 1
         xin = None if x is None else _f(x).copy()
@@ -617,9 +623,10 @@ class Population:
 class LmPlan:
     """rdis_hip_lm_plan: the tables of Problem.lm_batch for a list of small independent components, built and uploaded once.
     solve() / solve_population() only enqueue launches; fetch() / fetch_population() wait and download.  model: residual model
-    1 or 2; history: records kept per component."""
+    1 or 2; history: records kept per component; wide: components of 17 to LM_WIDE_MAX_CAMERAS active camera blocks are taken
+    (RDIS_HIP_LM_WIDE) instead of refused."""
 
-    def __init__(self, prob: Problem, free_ptr, free_vid, fac_ptr, fac_id, model=1, history=64):
+    def __init__(self, prob: Problem, free_ptr, free_vid, fac_ptr, fac_id, model=1, history=64, wide=False):
         self.prob, self.ctx = prob, prob.ctx
         self.free_ptr, self.free_vid = _i(free_ptr), _i(free_vid)
         self.fac_ptr, self.fac_id = _i(fac_ptr), _i(fac_id)
@@ -629,7 +636,7 @@ class LmPlan:
         self._nmembers = 0
         h = _vp()
         self.ctx.check(self.ctx.lib.rdis_hip_lm_plan_create(prob.h, self.ncomp, _ptr(self.free_ptr), _ptr(self.free_vid), _ptr(self.fac_ptr),
-                                                            _ptr(self.fac_id), int(model), self.cap, C.byref(h)))
+                                                            _ptr(self.fac_id), int(model) | (LM_WIDE if wide else 0), self.cap, C.byref(h)))
         self._cell = _Cell(h, self.ctx.lib.rdis_hip_lm_plan_destroy, prob._cell)
         _register(self)
 

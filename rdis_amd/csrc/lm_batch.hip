@@ -15,6 +15,10 @@
 // the right-hand side as one more row, so that the factorisation leaves L^-1 rhs behind and only L^T dc = z remains.
 // Per-factor rows (Jc, Jp, e, T, Z blocks) and per-point blocks are in the component's workspace slice in HBM.
 //
+// A component of 17 to 64 cameras (class 3, the wide class, by option) runs the same iteration; its reduced system (up to
+// 576 unknowns) does not fit the LDS, lies in the workspace slice as 16 x 16 tiles (lm_batch.hpp: LmWideTiles) and is
+// factorised in panels of 16 columns that pass through the LDS, the trailing update on the matrix cores.
+//
 // Every sum runs in an order fixed by the component's own lists and its class (lm_batch.hpp: the class, and with it the
 // workgroup size, is a function of the component's camera count alone): a component's bits depend neither on what else
 // is in the batch nor on where it stands in it.
@@ -92,6 +96,8 @@ __device__ __forceinline__ void block_reduce(double* s, double* m, double* red) 
         for (int k = 0; k < KM; ++k) m[k] = fmax(m[k], red[K * w + KS + k]);
     }
 }
+
+typedef double d4 __attribute__((ext_vector_type(4)));   // the accumulator of v_mfma_f64_16x16x4_f64
 
 __device__ __forceinline__ int tri(int i) { return i * (i + 1) / 2; }   // start of row i of a packed lower triangle
 __device__ __forceinline__ int vdiag(int k) { return k == 0 ? 0 : k == 1 ? 2 : 5; }   // V's packing: v00 v10 v11 v20 v21 v22
@@ -186,7 +192,30 @@ __global__ void __launch_bounds__(lm_batch_class_threads(CLS)) k_lm_batch(BatchD
                 const int b0 = cptr[c], b1 = cptr[c + 1];
                 const int row = k < 81 ? k / 9 : k - 81, col = k < 81 ? k - 9 * (k / 9) : 0;
                 double acc = 0.0;
-                for (int u = b0; u < b1; ++u)
+                int u = b0;
+                if constexpr (CLS == 3) {
+                    // (a wide component's cameras have hundreds of rows and the workgroup has the unit to itself: the operands
+                    // of four factors are fetched before they are added, in the same order)
+                    for (; u + 4 <= b1; u += 4) {
+                        double p[4][2], q[4][2];
+#pragma unroll
+                        for (int v = 0; v < 4; ++v) {
+                            const long long j = clist[u + v];
+#pragma unroll
+                            for (int r = 0; r < 2; ++r) {
+                                const long long jr = j * R + (r < R ? r : 0);
+                                p[v][r] = Jc[9 * jr + row];
+                                q[v][r] = k < 81 ? Jc[9 * jr + col] : E[jr];
+                            }
+                        }
+#pragma unroll
+                        for (int v = 0; v < 4; ++v)
+#pragma unroll
+                            for (int r = 0; r < 2; ++r)
+                                if (r < R) acc += p[v][r] * q[v][r];
+                    }
+                }
+                for (; u < b1; ++u)
                     for (int r = 0; r < R; ++r) {
                         const long long jr = (long long)clist[u] * R + r;
                         acc += Jc[9 * jr + row] * (k < 81 ? Jc[9 * jr + col] : E[jr]);
@@ -262,6 +291,204 @@ __global__ void __launch_bounds__(lm_batch_class_threads(CLS)) k_lm_batch(BatchD
         }
         __syncthreads();
         bool solved = true;
+        if constexpr (CLS == 3) {
+            // The wide class: the reduced system lies in the slice's 16 x 16 tiles (LmWideTiles: rows 0 .. M, the right-hand
+            // side as row M) and is factorised right-looking in panels of 16 columns that pass through the LDS.
+            constexpr int TS = LM_WIDE_TILE, PS = LM_WIDE_PANEL_STRIDE;
+            const LmWideTiles G(nca);
+            double* const Sg = ws + W.S;
+            double* const P = S;                 // the panel: row r of its tile rows at P + PS r
+            double* const flag = red + LM_BATCH_LDS_HEAD - 1;   // 0: a pivot <= 0 (block_reduce uses the scratch's first 24 at most)
+            const int tx = tid & 15, ty = tid >> 4, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+            // S = U + damping on the block diagonal, zero elsewhere, the tiles' padding and row M included
+            for (int row = ty; row < TS * G.nt; row += NT / 16)
+                for (int col = tx; col < TS * (row / TS + 1); col += 16) {
+                    double v = 0.0;
+                    if (row < M && col <= row) {
+                        if (row / 9 == col / 9) v = U[81 * (row / 9) + 9 * (row % 9) + (col % 9)];
+                        if (row == col) v += damp(mu, floor_, v);
+                    }
+                    Sg[G.at(row, col)] = v;
+                }
+            __syncthreads();
+            for (int t = tid; t < M; t += NT) {   // row M: rhs = bc - Z y
+                const int c = t / 9, a = t - 9 * c;
+                double acc = 0.0;
+#pragma unroll 4
+                for (int u = cptr[c]; u < cptr[c + 1]; ++u) {
+                    const int j = clist[u], pi = fpi[j];
+                    if (pi < 0) continue;
+                    for (int r = 0; r < R; ++r) {
+                        const long long jr = (long long)j * R + r;
+                        const double wv_ = T[3 * jr] * yp[3ll * pi] + T[3 * jr + 1] * yp[3ll * pi + 1] + T[3 * jr + 2] * yp[3ll * pi + 2];
+                        acc += Jc[9 * jr + a] * wv_;
+                    }
+                }
+                Sg[G.at(M, t)] = bc[t] - acc;
+            }
+            // S -= Z Z^T: a thread per entry of a pair's 9 x 9 block, over the points both cameras see, in point order
+            for (int t = tid; t < 81 * C.npair; t += NT) {
+                const int q = t / 81, k = t - 81 * q, row = k / 9, col = k - 9 * row;
+                const int a = pab[2 * q], b = pab[2 * q + 1];
+                if (a == b && col > row) continue;
+                double acc = 0.0;
+                int e = pairptr[q];
+                const int e1 = pairptr[q + 1];
+                // (a wide component's pairs share many points and the workgroup has the unit to itself: the operands of four
+                // entries are fetched before they are added, in the same order)
+                for (; e + 4 <= e1; e += 4) {
+                    double za[4][3], zb[4][3];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const double *pa = Zc + 27ll * pja[e + u] + row, *pb = Zc + 27ll * pjb[e + u] + col;
+                        za[u][0] = pa[0]; za[u][1] = pa[9]; za[u][2] = pa[18];
+                        zb[u][0] = pb[0]; zb[u][1] = pb[9]; zb[u][2] = pb[18];
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) acc += za[u][0] * zb[u][0] + za[u][1] * zb[u][1] + za[u][2] * zb[u][2];
+                }
+                for (; e < e1; ++e) {
+                    const double *za = Zc + 27ll * pja[e], *zb = Zc + 27ll * pjb[e];
+                    acc += za[row] * zb[col] + za[9 + row] * zb[9 + col] + za[18 + row] * zb[18 + col];
+                }
+                Sg[G.at(9 * a + row, 9 * b + col)] -= acc;
+            }
+            // Cholesky by panels; row M (the right-hand side) rides along as the last row of every panel
+            for (int kp = 0; kp < G.np; ++kp) {
+                __syncthreads();   // (the stores of S above / of the last trailing update; the panel's last readers)
+                const int nr = TS * (G.nt - kp), w = min(TS, M - TS * kp);   // the panel's rows; its columns that exist
+                for (int e = tid; e < nr * TS; e += NT) {
+                    const int r = e >> 4, c = e & 15;
+                    P[PS * r + c] = Sg[G.tile(kp + (r >> 4), kp) + ((r & 15) << 4) + c];
+                }
+                if (tid == 0) *flag = 1.0;
+                __syncthreads();
+                if (tid < 64) {   // the diagonal tile in wave 0's registers: lane r (and r + 16, ...) holds row r; by columns
+                    const int r = lane & 15;
+                    double a[TS];
+#pragma unroll
+                    for (int c = 0; c < TS; ++c) a[c] = P[PS * r + c];
+                    bool okp = true;
+#pragma unroll
+                    for (int c = 0; c < TS; ++c) {
+                        if (c < w && okp) {   // (the same for every lane)
+                            const double d = __shfl(a[c], c);
+                            if (!(d > 0.0)) {
+                                okp = false;
+                            } else {
+                                const double l = sqrt(d);
+                                a[c] = r == c ? l : a[c] / l;
+#pragma unroll
+                                for (int j = c + 1; j < TS; ++j)
+                                    if (j < w) a[j] -= a[c] * __shfl(a[c], j);   // (entries right of the diagonal: computed, never stored)
+                            }
+                        }
+                    }
+                    if (lane < TS)
+#pragma unroll
+                        for (int c = 0; c < TS; ++c)
+                            if (c <= r && c < w) P[PS * r + c] = a[c];
+                    if (lane == 0 && !okp) *flag = 0.0;
+                }
+                __syncthreads();
+                if (*flag == 0.0) { solved = false; break; }   // (every thread reads the same value)
+                for (int r = TS + tid; r < nr; r += NT) {   // the rows below: row L_kk^T = row, a lane per row
+                    double a[TS];
+#pragma unroll
+                    for (int c = 0; c < TS; ++c) a[c] = P[PS * r + c];
+#pragma unroll
+                    for (int c = 0; c < TS; ++c)
+                        if (c < w) {
+                            double v = a[c];
+#pragma unroll
+                            for (int j = 0; j < c; ++j) v -= a[j] * P[PS * c + j];
+                            a[c] = v / P[PS * c + c];
+                        }
+#pragma unroll
+                    for (int c = 0; c < TS; ++c) P[PS * r + c] = a[c];
+                }
+                __syncthreads();
+                for (int e = tid; e < nr * TS; e += NT) {
+                    const int r = e >> 4, c = e & 15;
+                    Sg[G.tile(kp + (r >> 4), kp) + ((r & 15) << 4) + c] = P[PS * r + c];
+                }
+                // trailing update on the matrix cores: tile (ti, tj) -= P_ti P_tj^T, the waves striding over the tile pairs.
+                // v_mfma_f64_16x16x4_f64 (lm_solver.hip's k_cam): lane l supplies A[l & 15][l >> 4] and B[l >> 4][l & 15], its
+                // result register r is D[(l >> 4) + 4 r][l & 15]; four of them cover the panel's sixteen columns.
+                {
+                    const int i16 = lane & 15, kq = lane >> 4;
+                    // a wave's unit of work: up to four neighbouring tiles of one tile row (they share P_ti and lie one behind the
+                    // other), all loaded before the first is updated
+                    int cnt = 0;
+                    for (int ti = kp + 1; ti < G.nt; ++ti) {
+                        const int tjend = min(ti, G.np - 1);
+                        for (int tj0 = kp + 1; tj0 <= tjend; tj0 += 4, cnt = (cnt + 1) & (NT / 64 - 1)) {
+                            if (cnt != wv) continue;
+                            double* const tl = Sg + G.tile(ti, tj0) + TS * kq + i16;
+                            const double* const pa = P + PS * (TS * (ti - kp) + i16) + kq;
+                            const double* const pb = P + PS * (TS * (tj0 - kp) + i16) + kq;
+                            const int n = min(4, tjend - tj0 + 1);
+                            const double a0 = -pa[0], a1 = -pa[4], a2 = -pa[8], a3 = -pa[12];
+                            d4 acc[4];
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) {   // (beyond the row's end: its last tile once more, computed and not stored)
+                                const double* const t = tl + TS * TS * min(u, n - 1);
+                                acc[u] = d4{t[0], t[4 * TS], t[8 * TS], t[12 * TS]};
+                            }
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) {
+                                const double* const b = pb + PS * TS * min(u, n - 1);
+                                acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b[0], acc[u], 0, 0, 0);
+                                acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b[4], acc[u], 0, 0, 0);
+                                acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, b[8], acc[u], 0, 0, 0);
+                                acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a3, b[12], acc[u], 0, 0, 0);
+                            }
+#pragma unroll
+                            for (int u = 0; u < 4; ++u)
+                                if (u < n) {
+                                    tl[TS * TS * u] = acc[u][0]; tl[TS * TS * u + 4 * TS] = acc[u][1];
+                                    tl[TS * TS * u + 8 * TS] = acc[u][2]; tl[TS * TS * u + 12 * TS] = acc[u][3];
+                                }
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            if (solved) {   // L^T dc = z (row M), tile row by tile row from the bottom
+                for (int t = tid; t < M; t += NT) dc[t] = Sg[G.at(M, t)];
+                for (int kt = G.np - 1; kt >= 0; --kt) {
+                    const int w = min(TS, M - TS * kt);
+                    if (tid < TS * TS) P[tid] = Sg[G.tile(kt, kt) + tid];
+                    __syncthreads();
+                    if (tid < 64) {   // the tile's own unknowns in wave 0: lane r holds z_r
+                        const int r = lane & 15;
+                        double z = r < w ? dc[TS * kt + r] : 0.0;
+#pragma unroll
+                        for (int k = TS - 1; k >= 0; --k)
+                            if (k < w) {
+                                const double xk = __shfl(z, k) / P[TS * k + k];
+                                if (r == k) z = xk;
+                                else if (r < k) z -= P[TS * k + r] * xk;
+                            }
+                        if (lane < w) dc[TS * kt + lane] = z;
+                    }
+                    __syncthreads();
+                    for (int i = tid; i < TS * kt; i += NT) {   // ... taken out of the unknowns above, a lane per unknown
+                        const double* const col = Sg + G.tile(kt, i / TS) + i % TS;
+                        double l[TS];   // (all sixteen rows of the tile exist; those beyond w are loaded and not used)
+#pragma unroll
+                        for (int k = 0; k < TS; ++k) l[k] = col[TS * k];
+                        double acc = dc[i];
+#pragma unroll
+                        for (int k = TS - 1; k >= 0; --k)
+                            if (k < w) acc -= l[k] * dc[TS * kt + k];
+                        dc[i] = acc;
+                    }
+                }
+            }
+            __syncthreads();
+            if (!solved) return false;
+        } else
         if (MAXC > 0 && nca > 0) {
             const int tx = tid & 15, ty = tid >> 4;
             // S = U + damping on the block diagonal, zero elsewhere; row M: rhs = bc - Z y
@@ -442,7 +669,7 @@ __global__ void __launch_bounds__(lm_batch_class_threads(CLS)) k_lm_batch(BatchD
 template <int CLS>
 hipError_t launch_class(hipStream_t stream, const BatchDev& B, int first, int count, int members) {
     if (count <= 0) return hipSuccess;
-    const size_t lds = lm_batch_lds_doubles(lm_batch_class_cameras(CLS)) * sizeof(double);
+    const size_t lds = lm_batch_class_lds_doubles(CLS) * sizeof(double);
     if (B.xout) return launch_dyn(k_lm_batch<CLS, true>, dim3((unsigned)count, (unsigned)members), lm_batch_class_threads(CLS), lds, stream, B, first);
     return launch_dyn(k_lm_batch<CLS, false>, dim3((unsigned)count), lm_batch_class_threads(CLS), lds, stream, B, first);
 }
@@ -478,6 +705,7 @@ int lm_batch_launch(hipStream_t stream, const LmBatchProblem& P, const void* tab
     B.R = opt.model; B.maxiters = opt.maxiters; B.hist_cap = hist_cap;
     B.tau = opt.tau; B.eps1 = opt.eps1; B.eps2 = opt.eps2; B.eps3 = opt.eps3;
     // one launch per class that occurs, its components heaviest first
+    LMB_CHK(launch_class<3>(stream, B, n[0] + n[1] + n[2], n[3], M.count));
     LMB_CHK(launch_class<2>(stream, B, n[0] + n[1], n[2], M.count));
     LMB_CHK(launch_class<1>(stream, B, n[0], n[1], M.count));
     LMB_CHK(launch_class<0>(stream, B, 0, n[0], M.count));
@@ -514,7 +742,7 @@ int device_lm_batch(hipStream_t stream, const LmBatchProblem& P, const LmBatchTa
     // a launch of one member
     const LmBatchMembers M{0, reinterpret_cast<double*>(base + p_res.off), 0, reinterpret_cast<double*>(base + p_hist.off), 0,
                            reinterpret_cast<double*>(base + p_ws.off), 0, nullptr, 0, 1};
-    const int n[LM_BATCH_CLASSES] = {(int)T.order[0].size(), (int)T.order[1].size(), (int)T.order[2].size()};
+    const int n[LM_BATCH_CLASSES] = {(int)T.order[0].size(), (int)T.order[1].size(), (int)T.order[2].size(), (int)T.order[3].size()};
     if (int e = lm_batch_launch(stream, P, base, lay, n, opt, hist_cap, M)) return e;
     LMB_CHK(hipMemcpyAsync(res->data(), M.res, p_res.bytes, hipMemcpyDeviceToHost, stream));
     if (hist_cap > 0) {

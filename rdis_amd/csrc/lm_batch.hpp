@@ -6,6 +6,10 @@
 // the factors' local block indices, the factor lists per block, the camera pairs that share a point -- decides every
 // component's class and lays out its workspace slice.  No HIP call, no context: everything that can be refused is
 // refused here, before anything is launched or written.
+//
+// Components of 17 to 64 active camera blocks are the *wide* class (3), taken only where the caller opts in (RDIS_HIP_LM_WIDE
+// in residual_model): their reduced system does not fit the LDS and lies in the component's workspace slice, in 16 x 16 tiles
+// (LmWideTiles below: the one description host and device read).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -22,13 +26,15 @@
 namespace rdis_hip {
 
 constexpr int LM_BATCH_MAX_CAMERAS = 16;   // include/rdis_hip.h: RDIS_HIP_LM_BATCH_MAX_CAMERAS
+constexpr int LM_BATCH_WIDE_MAX_CAMERAS = 64;   // include/rdis_hip.h: RDIS_HIP_LM_WIDE_MAX_CAMERAS (with the option RDIS_HIP_LM_WIDE)
 constexpr int LM_BATCH_EINVAL = -1, LM_BATCH_ERANGE = -5;   // include/rdis_hip.h's codes (rdis_hip.hip asserts them equal)
 
 // ---- component classes: the workgroup and its dynamic LDS are a function of the component alone ---------------------------
-// class 0: no active camera block (points only: no reduced system);  1: up to 6 camera blocks;  2: up to 16.
-constexpr int LM_BATCH_CLASSES = 3;
-LMB_HD constexpr int lm_batch_class(int nca) { return nca == 0 ? 0 : nca <= 6 ? 1 : 2; }
-LMB_HD constexpr int lm_batch_class_cameras(int cls) { return cls == 0 ? 0 : cls == 1 ? 6 : LM_BATCH_MAX_CAMERAS; }
+// class 0: no active camera block (points only: no reduced system);  1: up to 6 camera blocks;  2: up to 16;
+// 3 (wide, by option): 17 up to 64, the reduced system in the workspace slice.
+constexpr int LM_BATCH_CLASSES = 4;
+LMB_HD constexpr int lm_batch_class(int nca) { return nca == 0 ? 0 : nca <= 6 ? 1 : nca <= LM_BATCH_MAX_CAMERAS ? 2 : 3; }
+LMB_HD constexpr int lm_batch_class_cameras(int cls) { return cls == 0 ? 0 : cls == 1 ? 6 : cls == 2 ? LM_BATCH_MAX_CAMERAS : LM_BATCH_WIDE_MAX_CAMERAS; }
 LMB_HD constexpr int lm_batch_class_threads(int cls) { return cls == 0 ? 64 : cls == 1 ? 256 : 512; }
 // LDS of a class, in doubles: reduction scratch [64] | U [81 C] | bc [9 C] | dc [9 C] | the reduced system's
 // lower triangle, packed by rows, with the right-hand side as row M = 9 C: (M + 1)(M + 2) / 2
@@ -38,8 +44,38 @@ LMB_HD constexpr size_t lm_batch_lds_doubles(int maxc) {
                      : (size_t)LM_BATCH_LDS_HEAD + 81 * (size_t)maxc + 18 * (size_t)maxc + (size_t)(9 * maxc + 1) * (size_t)(9 * maxc + 2) / 2;
 }
 
+
+// ---- the wide class's reduced system: S with the right-hand side as row M = 9 C, as the lower triangle of 16 x 16 tiles ----
+// Tile (ti, tj), tj <= ti, is the ti (ti + 1) / 2 + tj-th run of 256 doubles, row-major inside.  nt = ceil((M + 1) / 16) tile
+// rows hold rows 0 .. M; np = ceil(M / 16) column panels hold the columns that are factorised (0 .. M - 1).  Rows and
+// columns beyond M inside the last tiles are padding: written as zero, never read into a result.  At 64 cameras: 37 tile
+// rows, 703 tiles, 1 439 744 bytes.
+constexpr int LM_WIDE_TILE = 16;
+struct LmWideTiles {
+    int M, nt, np;
+    LMB_HD constexpr explicit LmWideTiles(int nca) : M(9 * nca), nt((9 * nca + 1 + LM_WIDE_TILE - 1) / LM_WIDE_TILE), np((9 * nca + LM_WIDE_TILE - 1) / LM_WIDE_TILE) {}
+    LMB_HD constexpr long long doubles() const { return (long long)nt * (nt + 1) / 2 * (LM_WIDE_TILE * LM_WIDE_TILE); }
+    LMB_HD constexpr long long tile(int ti, int tj) const { return ((long long)ti * (ti + 1) / 2 + tj) * (LM_WIDE_TILE * LM_WIDE_TILE); }   // tj <= ti
+    LMB_HD constexpr long long at(int row, int col) const {   // col / 16 <= row / 16
+        return tile(row / LM_WIDE_TILE, col / LM_WIDE_TILE) + (row % LM_WIDE_TILE) * LM_WIDE_TILE + col % LM_WIDE_TILE;
+    }
+};
+// LDS of the wide class, in doubles: reduction scratch [64] | U [81 C] | bc [9 C] | dc [9 C] | one panel of 16 columns: the
+// 16 nt rows of the tile rows (those above the panel's own tile row are not loaded), a row every LM_WIDE_PANEL_STRIDE doubles
+// (17: lanes that read one column of sixteen rows hit sixteen different pairs of banks)
+constexpr int LM_WIDE_PANEL_STRIDE = 17;
+LMB_HD constexpr size_t lm_batch_wide_lds_doubles(int maxc) {
+    return (size_t)LM_BATCH_LDS_HEAD + 81 * (size_t)maxc + 18 * (size_t)maxc + (size_t)LmWideTiles(maxc).nt * LM_WIDE_TILE * LM_WIDE_PANEL_STRIDE;
+}
+LMB_HD constexpr size_t lm_batch_class_lds_doubles(int cls) {
+    return cls == 3 ? lm_batch_wide_lds_doubles(lm_batch_class_cameras(3)) : lm_batch_lds_doubles(lm_batch_class_cameras(cls));
+}
+static_assert(lm_batch_class_lds_doubles(3) * sizeof(double) <= 160 * 1024 && lm_batch_class_lds_doubles(2) * sizeof(double) <= 160 * 1024,
+              "a class's LDS fits the 160 KiB of a compute unit");
+
 // ---- a component's workspace slice in HBM (doubles; offsets from the slice's start) -------------------------------------------
-struct LmBatchSlice { long long Jc, Jp, e, T, Zc, V, bp, Lp, yp, dp, psave, total; };
+// (S: the wide class's tiles, LmWideTiles(nca).doubles() of them, appended behind what every class has; total includes it)
+struct LmBatchSlice { long long Jc, Jp, e, T, Zc, V, bp, Lp, yp, dp, psave, total, S; };
 // nf listed factors with R residual rows each, nca / npa active camera / point blocks, nfree free variables
 LMB_HD inline LmBatchSlice lm_batch_slice(long long nf, long long nca, long long npa, long long nfree, long long R) {
     LmBatchSlice s{};
@@ -49,6 +85,8 @@ LMB_HD inline LmBatchSlice lm_batch_slice(long long nf, long long nca, long long
     s.Zc = take(nca > 0 && npa > 0 ? nf * 27 : 0);
     s.V = take(npa * 6); s.bp = take(npa * 3); s.Lp = take(npa * 6); s.yp = take(npa * 3); s.dp = take(npa * 3);
     s.psave = take(nfree);
+    s.S = o;
+    if (lm_batch_class((int)nca) == 3) (void)take(LmWideTiles((int)nca).doubles());
     s.total = o;
     return s;
 }
@@ -84,9 +122,13 @@ struct LmBatchBlocks {
     int ncams;
 };
 
+// the key of a camera pair (a, b), b <= a: ordered as (a, b) whatever the class
+constexpr int LM_BATCH_PAIR_STRIDE = LM_BATCH_WIDE_MAX_CAMERAS + 1;
+
 // 0, or a code with *msg.  The lists have passed plan_index_build: ids in range, components independent.
+// wide: components of 17 to LM_BATCH_WIDE_MAX_CAMERAS active camera blocks are taken (class 3) instead of refused.
 inline int lm_batch_prepare(const LmBatchBlocks& B, int64_t ncomp, const int64_t* free_ptr, const int64_t* free_vid,
-                            const int64_t* fac_ptr, const int64_t* fac_id, int R, LmBatchTables& T, std::string* msg) {
+                            const int64_t* fac_ptr, const int64_t* fac_id, int R, LmBatchTables& T, std::string* msg, bool wide = false) {
     auto refuse = [&](int code, std::string m) { *msg = std::move(m); return code; };
     const int64_t nfree_all = free_ptr[ncomp];
     T.comps.assign((size_t)ncomp, LmBatchComp{});
@@ -125,11 +167,12 @@ inline int lm_batch_prepare(const LmBatchBlocks& B, int64_t ncomp, const int64_t
         std::sort(pts.begin(), pts.end());
         const int nca = (int)cams.size(), npa = (int)pts.size();
         auto unmark = [&]() { for (int b : cams) loc[(size_t)b] = -1; for (int b : pts) loc[(size_t)b] = -1; };
-        if (nca > LM_BATCH_MAX_CAMERAS) {
+        if (nca > (wide ? LM_BATCH_WIDE_MAX_CAMERAS : LM_BATCH_MAX_CAMERAS)) {
             unmark();
             return refuse(LM_BATCH_ERANGE, "lm_batch: component " + std::to_string(cc) + " has " + std::to_string(nca) +
-                                               " active camera blocks, the limit is " + std::to_string(LM_BATCH_MAX_CAMERAS) +
-                                               " (RDIS_HIP_LM_BATCH_MAX_CAMERAS): solve it with rdis_hip_lm_optimize");
+                                               " active camera blocks, the limit is " + std::to_string(wide ? LM_BATCH_WIDE_MAX_CAMERAS : LM_BATCH_MAX_CAMERAS) +
+                                               (wide ? " (RDIS_HIP_LM_WIDE_MAX_CAMERAS, with RDIS_HIP_LM_WIDE)" : " (RDIS_HIP_LM_BATCH_MAX_CAMERAS)") +
+                                               ": solve it with rdis_hip_lm_optimize");
         }
         for (int c = 0; c < nca; ++c) loc[(size_t)cams[(size_t)c]] = c;
         for (int p = 0; p < npa; ++p) loc[(size_t)pts[(size_t)p]] = p;
@@ -182,7 +225,7 @@ inline int lm_batch_prepare(const LmBatchBlocks& B, int64_t ncomp, const int64_t
                 for (int u = t0; u < t1; ++u) {
                     const int jb = plist[(size_t)u], b = fci[(size_t)jb];
                     if (b < 0 || b > a) continue;
-                    ents.push_back({a * (LM_BATCH_MAX_CAMERAS + 1) + b, ja, jb});
+                    ents.push_back({a * LM_BATCH_PAIR_STRIDE + b, ja, jb});
                 }
             }
         }
@@ -190,7 +233,7 @@ inline int lm_batch_prepare(const LmBatchBlocks& B, int64_t ncomp, const int64_t
         for (size_t i = 0; i < ents.size(); ++i) {
             if (i == 0 || ents[i].key != ents[i - 1].key) {
                 if (i > 0) pairptr.push_back((int)i);
-                pab.push_back(ents[i].key / (LM_BATCH_MAX_CAMERAS + 1)); pab.push_back(ents[i].key % (LM_BATCH_MAX_CAMERAS + 1));
+                pab.push_back(ents[i].key / LM_BATCH_PAIR_STRIDE); pab.push_back(ents[i].key % LM_BATCH_PAIR_STRIDE);
             }
             pja.push_back(ents[i].ja); pjb.push_back(ents[i].jb);
         }
@@ -212,7 +255,7 @@ inline int lm_batch_prepare(const LmBatchBlocks& B, int64_t ncomp, const int64_t
     return 0;
 }
 
-// where the tables lie in one device block, uploaded in one copy: comps | ints | free32 | order (class 0, 1, 2) | freem,
+// where the tables lie in one device block, uploaded in one copy: comps | ints | free32 | order (class 0, 1, 2, 3) | freem,
 // each part on a 256-byte boundary; `bytes` is the block's size.  Nothing in it depends on x.
 struct LmBatchTableLayout { size_t comps, ints, free32, order, freem, bytes; };
 inline LmBatchTableLayout lm_batch_table_layout(const LmBatchTables& T) {
@@ -278,7 +321,7 @@ struct LmBatchMembers {
     int count;
 };
 // Enqueues the solve of every component of an uploaded table block (lm_batch_table_layout; n: the components of each class)
-// for M.count members: one launch per class that occurs, heaviest class first.  No copy, no wait, no allocation.
+// for M.count members: one launch per class that occurs (at most four), heaviest class first.  No copy, no wait, no allocation.
 // Returns 0 or a hipError_t.
 int lm_batch_launch(hipStream_t stream, const LmBatchProblem& P, const void* tables, const LmBatchTableLayout& lay, const int (&n)[LM_BATCH_CLASSES],
                     const LmBatchOptions& opt, int64_t hist_cap, const LmBatchMembers& M);

@@ -2855,13 +2855,14 @@ extern "C" int rdis_hip_lm_optimize(rdis_hip_problem* p, int64_t nfree, const in
 // Levenberg-Marquardt for a batch of small components, one workgroup each (lm_batch.hip).  Everything that can be refused
 // is refused on the host, before x is touched or anything is launched: the lists by the plan index's checks, the
 // components' sizes and factor pairs by lm_batch_prepare.
-static_assert(LM_BATCH_EINVAL == RDIS_HIP_EINVAL && LM_BATCH_ERANGE == RDIS_HIP_ERANGE && LM_BATCH_MAX_CAMERAS == RDIS_HIP_LM_BATCH_MAX_CAMERAS,
+static_assert(LM_BATCH_EINVAL == RDIS_HIP_EINVAL && LM_BATCH_ERANGE == RDIS_HIP_ERANGE && LM_BATCH_MAX_CAMERAS == RDIS_HIP_LM_BATCH_MAX_CAMERAS &&
+                  LM_BATCH_WIDE_MAX_CAMERAS == RDIS_HIP_LM_WIDE_MAX_CAMERAS && (RDIS_HIP_LM_WIDE & 255) == 0,
               "lm_batch.hpp restates include/rdis_hip.h");
 namespace {
 // What rdis_hip_lm_batch and rdis_hip_lm_plan_create check and build before x is touched (`who` names the entry in the
 // messages): the problem, the model, the lists, the components' independence, then lm_batch_prepare's tables.
 int lm_batch_tables(rdis_hip_problem* p, const std::string& who, int64_t ncomp, const int64_t* free_ptr, const int64_t* free_vid,
-                    const int64_t* fac_ptr, const int64_t* fac_id, int R, LmBatchTables& T) {
+                    const int64_t* fac_ptr, const int64_t* fac_id, int R, bool wide, LmBatchTables& T) {
     rdis_hip_ctx* c = p->ctx;
     if (R != 1 && R != 2) return fail(c, RDIS_HIP_EINVAL, who + ": residual model must be 1 or 2");
     if (p->ncam_blocks <= 0 && p->F > 0) return fail(c, RDIS_HIP_EINVAL, who + ": the factors' camera and point blocks overlap");
@@ -2890,7 +2891,7 @@ int lm_batch_tables(rdis_hip_problem* p, const std::string& who, int64_t ncomp, 
     for (int64_t f = 0; f < p->F && layout; ++f)
         layout = p->h_cam[(size_t)f] % 9 == 0 && p->h_cam[(size_t)f] < 9 * ncams && (p->h_pt[(size_t)f] - 9 * ncams) % 3 == 0;
     const LmBatchBlocks blocks{p->N, p->F, p->h_cam.data(), p->h_pt.data(), p->h_block_of.data(), p->h_ptblock_of.data(), layout, ncams};
-    if ((rc = lm_batch_prepare(blocks, ncomp, free_ptr, free_vid, fac_ptr, fac_id, R, T, &why))) return fail(c, rc, relabel(why));
+    if ((rc = lm_batch_prepare(blocks, ncomp, free_ptr, free_vid, fac_ptr, fac_id, R, T, &why, wide))) return fail(c, rc, relabel(why));
     return 0;
 }
 }  // namespace
@@ -2904,8 +2905,9 @@ extern "C" int rdis_hip_lm_batch(rdis_hip_problem* p, int64_t ncomp, const int64
     if (p->kind != KIND_BA) return fail(c, RDIS_HIP_EINVAL, "lm_batch: bundle adjustment problems only");
     if (ncomp < 0 || !free_ptr || !fac_ptr || maxiters < 1 || hist_cap < 0) return fail(c, RDIS_HIP_EINVAL, "lm_batch: bad arguments");
     const int R = model & 15;   // (the Schur bits of rdis_hip_lm_optimize are ignored)
+    const bool wide = (model & RDIS_HIP_LM_WIDE) != 0;
     LmBatchTables T;
-    int rc = lm_batch_tables(p, "lm_batch", ncomp, free_ptr, free_vid, fac_ptr, fac_id, R, T);
+    int rc = lm_batch_tables(p, "lm_batch", ncomp, free_ptr, free_vid, fac_ptr, fac_id, R, wide, T);
     if (rc) return rc;
     const int64_t nfree = free_ptr[ncomp];
     if (x_inout && nfree > 0 && (rc = rdis_hip_set_x(p, nfree, free_vid, x_inout))) return rc;
@@ -2942,7 +2944,7 @@ struct rdis_hip_lm_plan {
     int64_t ncomp = 0, nfree = 0, hist_cap = 0;
     int R = 1;
     LmBatchTableLayout lay{};
-    int ncls[LM_BATCH_CLASSES] = {0, 0, 0};
+    int ncls[LM_BATCH_CLASSES] = {};
     LmPlanLayout layout;                    // replica_layout.hpp: the outputs of a solve's members, the workspace of a launch's
     DevBuf tables, out, work;
     int64_t workspace_bytes = (int64_t)1 << 30;   // option "workspace_bytes": bounds `work`
@@ -2969,7 +2971,7 @@ int lm_plan_enqueue(rdis_hip_lm_plan* L, double* x0, long long x_stride, int64_t
     if (!rc) rc = ensure(c, L->work, (size_t)L->layout.work.total_bytes(per));
     if (rc) return rc;
     const LmBatchOptions o{maxiters, L->R, 1e-3, 1e-15, 1e-15, ftol};
-    const int classes = (L->ncls[0] > 0) + (L->ncls[1] > 0) + (L->ncls[2] > 0);
+    const int classes = (L->ncls[0] > 0) + (L->ncls[1] > 0) + (L->ncls[2] > 0) + (L->ncls[3] > 0);
     for (int64_t m0 = 0; m0 < count; m0 += per) {
         const int64_t n = std::min(per, count - m0);
         const LmBatchProblem P{x0 + m0 * x_stride, p->lo.as<double>(), p->hi.as<double>(), p->cam.as<int>(), p->pt.as<int>(), p->obs.as<double2>()};
@@ -3026,8 +3028,9 @@ extern "C" int rdis_hip_lm_plan_create(rdis_hip_problem* p, int64_t ncomp, const
     if (p->kind != KIND_BA) return fail(c, RDIS_HIP_EINVAL, "lm_plan_create: bundle adjustment problems only");
     if (ncomp < 0 || !free_ptr || !fac_ptr || hist_cap < 0) return fail(c, RDIS_HIP_EINVAL, "lm_plan_create: bad arguments");
     const int R = model & 15;
+    const bool wide = (model & RDIS_HIP_LM_WIDE) != 0;
     LmBatchTables T;
-    int rc = lm_batch_tables(p, "lm_plan_create", ncomp, free_ptr, free_vid, fac_ptr, fac_id, R, T);
+    int rc = lm_batch_tables(p, "lm_plan_create", ncomp, free_ptr, free_vid, fac_ptr, fac_id, R, wide, T);
     if (rc) return rc;
     if ((double)ncomp * (double)std::max<int64_t>(hist_cap, 1) >= 1.0e15) return fail(c, RDIS_HIP_ERANGE, "lm_plan_create: history too large");
     std::unique_ptr<rdis_hip_lm_plan> L(new (std::nothrow) rdis_hip_lm_plan);
