@@ -532,7 +532,41 @@ int rdis_hip_plan_objective_device(rdis_hip_plan *plan, void **dev_ptr);
  *                             launch; a solve of more members than fit is split into launches (at least one member
  *                             each), the same bits whatever the split
  *   rdis_hip_lm_plan_get_info "members_per_launch", "launches" (of the last solve), "device_bytes", "workspace_bytes",
- *                             "member_workspace_bytes" (one member's workspace replica) */
+ *                             "member_workspace_bytes" (one member's workspace replica)
+ *
+ * Multi-start solves: what an RDIS node keeps of its random restarts (RDISOptimizer.cpp:1087-1094), with Levenberg-Marquardt.
+ *   rdis_hip_lm_plan_solve_starts   x_starts[nstarts][nfree], a host array in the plan's free-variable order, copied before
+ *                             the call returns.  Start s solves every component from the problem's currently assigned x
+ *                             with the plan's free variables replaced by row s; variables that are not free in the plan
+ *                             are constants all starts share.  Every (start, component) is bit for bit what
+ *                             rdis_hip_lm_batch with x_inout = NULL returns and leaves on a problem whose x is that vector.
+ *                             Afterwards best[c] is the start with the lowest fret[s][c] (the lowest index on a tie; a NaN
+ *                             never, unless every value is one: then 0), the free variables of component c are assigned
+ *                             that start's clamped result, and the plan's ordinary outputs hold the winner's row per
+ *                             component: rdis_hip_lm_plan_fetch returns them, its x_out is what was left assigned.  The
+ *                             solves run on scratch rows: no other variable of the problem is written at any time.  The
+ *                             starts of one launch are bounded by "workspace_bytes", a start charged
+ *                             "member_workspace_bytes" + 8 nvars bytes; more starts run in rounds, the same bits whatever
+ *                             the split ("members_per_launch", "launches": the solver's launches, classes x rounds; beside
+ *                             them one small kernel a round and two at the end).  Nothing else is copied, nothing is waited
+ *                             for, and after the first call of a size nothing is allocated.  RDIS_HIP_EINVAL: nstarts < 1,
+ *                             x_starts NULL, maxiters < 1; RDIS_HIP_ERANGE: a start count that cannot be sized -- all before
+ *                             anything is launched, copied or marked.  A plan of no component: 0, and nothing is done
+ *   rdis_hip_lm_plan_solve_starts_population   the same solve, start s taken from row first + s of a population of the
+ *                             plan's problem: only the plan's free variables are read from the row, the constants are still
+ *                             the problem's x.  The population is only read -- its rows, its values and what
+ *                             rdis_hip_population_best answers stay -- and no host memory is touched, so starts drawn with
+ *                             rdis_hip_population_sample never leave the device.  RDIS_HIP_EINVAL: another problem's
+ *                             population, count < 1, a range out of bounds
+ *   rdis_hip_lm_plan_fetch_starts   waits, then all starts' outputs, [nstarts][ncomp]... like
+ *                             rdis_hip_lm_plan_fetch_population's, x_out[nstarts][nfree] and best[ncomp].  Any pointer may
+ *                             be NULL.  RDIS_HIP_EINVAL after any other solve or before one; rdis_hip_lm_plan_fetch_population
+ *                             after a multi-start solve likewise.  Nothing is changed by a refused fetch
+ *   rdis_hip_lm_plan_objective_device   enqueues one kernel that sums fret over the plan's ordinary outputs -- after
+ *                             rdis_hip_lm_plan_solve the solve's rows, after a multi-start solve the winners' -- in a fixed
+ *                             order (one workgroup: a lane's stride in component order, a butterfly over the wave, the waves
+ *                             in wave order); a device pointer to one double, valid until the plan's next solve.
+ *                             RDIS_HIP_EINVAL before any solve and after a population solve */
 typedef struct rdis_hip_lm_plan rdis_hip_lm_plan;
 int rdis_hip_lm_plan_create(rdis_hip_problem *p, int64_t ncomp, const int64_t *free_ptr, const int64_t *free_vid,
                             const int64_t *fac_ptr, const int64_t *fac_id, int32_t residual_model, int64_t hist_cap,
@@ -545,6 +579,13 @@ int rdis_hip_lm_plan_solve_population(rdis_hip_lm_plan *plan, rdis_hip_populatio
                                       int32_t maxiters, double ftol);
 int rdis_hip_lm_plan_fetch_population(rdis_hip_lm_plan *plan, double *x_out, double *fret, double *delta, double *info8,
                                       double *hist4, int64_t *nhist);
+int rdis_hip_lm_plan_solve_starts(rdis_hip_lm_plan *plan, int64_t nstarts, const double *x_starts, int32_t maxiters,
+                                  double ftol);
+int rdis_hip_lm_plan_solve_starts_population(rdis_hip_lm_plan *plan, rdis_hip_population *pop, int64_t first,
+                                             int64_t count, int32_t maxiters, double ftol);
+int rdis_hip_lm_plan_fetch_starts(rdis_hip_lm_plan *plan, double *x_out, double *fret, double *delta, double *info8,
+                                  double *hist4, int64_t *nhist, int32_t *best);
+int rdis_hip_lm_plan_objective_device(rdis_hip_lm_plan *plan, void **dev_ptr);
 int rdis_hip_lm_plan_set_option(rdis_hip_lm_plan *plan, const char *name, int64_t value);
 int rdis_hip_lm_plan_get_info(rdis_hip_lm_plan *plan, const char *name, int64_t *value);
 

@@ -129,6 +129,10 @@ SYMBOLS = {
     "rdis_hip_lm_plan_fetch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rdis_hip_lm_plan_solve_population": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int32, C.c_double]),
     "rdis_hip_lm_plan_fetch_population": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rdis_hip_lm_plan_solve_starts": (C.c_int, [_vp, _i64, _vp, C.c_int32, C.c_double]),
+    "rdis_hip_lm_plan_solve_starts_population": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int32, C.c_double]),
+    "rdis_hip_lm_plan_fetch_starts": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rdis_hip_lm_plan_objective_device": (C.c_int, [_vp, C.POINTER(_vp)]),
     "rdis_hip_lm_plan_set_option": (C.c_int, [_vp, C.c_char_p, _i64]),
     "rdis_hip_lm_plan_get_info": (C.c_int, [_vp, C.c_char_p, C.POINTER(_i64)]),
     "rdis_hip_components": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
@@ -622,7 +626,8 @@ class Population:
 
 class LmPlan:
     """rdis_hip_lm_plan: the tables of Problem.lm_batch for a list of small independent components, built and uploaded once.
-    solve() / solve_population() only enqueue launches; fetch() / fetch_population() wait and download.  model: residual model
+    solve() / solve_population() / solve_starts() / solve_starts_population() only enqueue launches; fetch() / fetch_population() /
+    fetch_starts() wait and download.  model: residual model
     1 or 2; history: records kept per component; wide: components of 17 to LM_WIDE_MAX_CAMERAS active camera blocks are taken
     (RDIS_HIP_LM_WIDE) instead of refused."""
 
@@ -634,6 +639,7 @@ class LmPlan:
         self.nfree = int(self.free_ptr[-1])
         self.cap = max(int(history), 1)
         self._nmembers = 0
+        self._nstarts = 0
         h = _vp()
         self.ctx.check(self.ctx.lib.rdis_hip_lm_plan_create(prob.h, self.ncomp, _ptr(self.free_ptr), _ptr(self.free_vid), _ptr(self.fac_ptr),
                                                             _ptr(self.fac_id), int(model) | (LM_WIDE if wide else 0), self.cap, C.byref(h)))
@@ -658,12 +664,12 @@ class LmPlan:
         """every component from the problem's assigned x, the results left assigned; enqueued, nothing is waited for"""
         self.ctx.check(self.ctx.lib.rdis_hip_lm_plan_solve(self.h, maxiters, ftol))
 
-    def _fetch(self, entry, rows):
+    def _fetch(self, entry, rows, *more):
         nc, cap = self.ncomp, self.cap
         n = max(rows * nc, 1)
         x = np.zeros((rows, self.nfree))
         fret, delta, info, hist, nh = np.zeros(n), np.zeros(n), np.zeros((n, 8)), np.zeros((n, cap, 4)), np.zeros(n, dtype=np.int64)
-        self.ctx.check(entry(self.h, _ptr(x), _ptr(fret), _ptr(delta), _ptr(info), _ptr(hist), _ptr(nh)))
+        self.ctx.check(entry(self.h, _ptr(x), _ptr(fret), _ptr(delta), _ptr(info), _ptr(hist), _ptr(nh), *more))
         fp = self.free_ptr
         return [[LmResult(x=x[s, fp[c]:fp[c + 1]].copy(), fret=float(fret[k]), delta=float(delta[k]), iters=int(info[k, 0]), stop=int(info[k, 1]),
                           nfev=int(info[k, 2]), njev=int(info[k, 3]), nsolve=int(info[k, 4]), mu=float(info[k, 5]), camera_blocks=int(info[k, 6]),
@@ -687,6 +693,41 @@ class LmPlan:
         """the last solve_population()'s results: per member of the range a list of LmResult, one per component.  Everything
         comes from the plan's own buffers: the population may have been written or closed since"""
         return self._fetch(self.ctx.lib.rdis_hip_lm_plan_fetch_population, self._nmembers)
+
+    def solve_starts(self, x_starts, maxiters=25, ftol=3e-8):
+        """every component from each row of x_starts [nstarts, nfree] (the plan's free-variable order; everything else is the
+        problem's assigned x), the problem left at the best start per component; fetch() then returns the winners.  Enqueued:
+        x_starts is copied before this returns, nothing is waited for"""
+        xs = None if x_starts is None else _f(x_starts)     # (None: the library refuses)
+        if xs is not None and (xs.ndim != 2 or xs.shape[1] != self.nfree):
+            raise ValueError("x_starts must be [nstarts, nfree]")
+        n = 1 if xs is None else xs.shape[0]
+        self.ctx.check(self.ctx.lib.rdis_hip_lm_plan_solve_starts(self.h, n, _ptr(xs), maxiters, ftol))
+        self._nstarts = n
+
+    def solve_starts_population(self, pop: "Population", first=0, count=None, maxiters=25, ftol=3e-8):
+        """the same with start s read from member first + s of pop (the plan's free variables only; the constants are the
+        problem's x).  The population is only read; nothing leaves the device"""
+        first, count = pop._range(first, count)
+        self.ctx.check(self.ctx.lib.rdis_hip_lm_plan_solve_starts_population(self.h, pop.h, first, count, maxiters, ftol))
+        self._nstarts = count
+
+    def fetch_starts(self):
+        """(rows, best) of the last multi-start solve: rows as fetch_population() returns them, one list of LmResult per start;
+        best [ncomp] (int32): the start each component was left at"""
+        best = np.zeros(max(self.ncomp, 1), dtype=np.int32)
+        rows = self._fetch(self.ctx.lib.rdis_hip_lm_plan_fetch_starts, self._nstarts, _ptr(best))
+        return rows, best[:self.ncomp]
+
+    def objective_device_ptr(self) -> int:
+        p = _vp()
+        self.ctx.check(self.ctx.lib.rdis_hip_lm_plan_objective_device(self.h, C.byref(p)))
+        return p.value
+
+    def objective(self) -> float:
+        """the sum of fret over the plan's ordinary outputs (after solve(): its rows; after a multi-start solve: the winners'),
+        summed on the device in a fixed order; waits"""
+        return float(np.frombuffer(self.ctx.copy_to_host(self.objective_device_ptr(), 8), dtype=np.float64)[0])
 
     def set_option(self, name: str, value: int):
         """workspace_bytes (default 2^30): bounds the workspace replicas of one population launch"""

@@ -284,6 +284,7 @@ inline void lm_batch_stage_tables(const LmBatchTables& T, const LmBatchTableLayo
 // a component's row of results: fret, finit, iterations, stop code, residual evaluations, Jacobian evaluations, linear solves,
 // final mu, active camera blocks, active point blocks, history records (also those beyond the caller's capacity), unused
 constexpr int LM_BATCH_RES = 12;
+constexpr int LM_BATCH_RES_NHIST = 10;   // where in the row the history's record count stands
 
 #if defined(__HIPCC__)
 struct LmBatchProblem {     // device arrays of an uploaded bundle-adjustment problem

@@ -1,0 +1,107 @@
+// lm_starts.hip -- the kernels a Levenberg-Marquardt plan's multi-start solve runs around lm_batch.hip's (lm_starts.hpp): the
+// scratch rows of x the starts of a launch are solved in, the selection of every component's best start, the gather of the
+// winners' x into the problem's, and the sum of the plan's objective.  Plain vector stores only; no atomics.
+#include <hip/hip_runtime.h>
+
+#include "lm_starts.hpp"
+
+namespace rdis_hip {
+namespace {
+
+// Grid (blocks over N, starts of the launch), as population_sample_kernel: one lane per (start, variable), a wave stores 64
+// consecutive doubles of a row.  pos and x are read once per row; the start's values by pos (scattered over the row's free
+// entries: 8 N bytes read, 8 N written per start at most).
+__global__ void __launch_bounds__(256)
+k_lm_starts_fill(double* __restrict__ rows, long long N, const double* __restrict__ x, const int* __restrict__ pos, const double* __restrict__ src,
+                 long long src_stride, int by_pos, long long first, long long count) {
+    for (long long r = blockIdx.y; r < count; r += gridDim.y) {
+        const double* __restrict__ from = src + (first + r) * src_stride;
+        double* __restrict__ row = rows + r * N;
+        for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < N; v += (long long)gridDim.x * blockDim.x) {
+            const int k = pos[v];
+            row[v] = k >= 0 ? from[by_pos ? (long long)k : v] : x[v];
+        }
+    }
+}
+
+// One lane per component: the scan over the starts' fret (lm_starts_best), then the winner's result row and the history
+// records it wrote (at most hist_cap) into the winners' row.
+__global__ void __launch_bounds__(256)
+k_lm_starts_select(LmStartsOut O, long long nstarts, long long ncomp) {
+    for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < ncomp; c += (long long)gridDim.x * blockDim.x) {
+        const long long b = lm_starts_best(nstarts, O.res + c * O.res_doubles, O.res_ms);
+        O.best[c] = (int)b;
+        const double* __restrict__ from = O.res + b * O.res_ms + c * O.res_doubles;
+        double* __restrict__ to = O.res + nstarts * O.res_ms + c * O.res_doubles;
+        for (int i = 0; i < O.res_doubles; ++i) to[i] = from[i];
+        if (O.hist_cap > 0) {
+            const long long written = (long long)from[O.nhist_at];
+            const long long n = 4 * (written < O.hist_cap ? written : O.hist_cap);
+            const double* __restrict__ hf = O.hist + b * O.hist_ms + c * O.hist_cap * 4;
+            double* __restrict__ ht = O.hist + nstarts * O.hist_ms + c * O.hist_cap * 4;
+            for (long long i = 0; i < n; ++i) ht[i] = hf[i];
+        }
+    }
+}
+
+// One lane per entry of the free list
+__global__ void __launch_bounds__(256)
+k_lm_starts_gather(LmStartsOut O, long long nstarts, long long nfree, const int* __restrict__ free32, const int* __restrict__ comp_of,
+                   double* __restrict__ x) {
+    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < nfree; k += (long long)gridDim.x * blockDim.x) {
+        const double v = O.xout[(long long)O.best[comp_of[k]] * O.xout_ms + k];
+        x[free32[k]] = v;
+        O.xout[nstarts * O.xout_ms + k] = v;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_lm_plan_objective(long long ncomp, const double* __restrict__ res, long long stride, double* __restrict__ out) {
+    __shared__ double red[4];
+    double acc = 0.0;
+    for (long long c = threadIdx.x; c < ncomp; c += 256) acc += res[c * stride];
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int w = 0; w < 4; ++w) s += red[w];
+        out[0] = s;
+    }
+}
+
+// blocks of 256 lanes over `work` items, at most `cap` (the kernels stride beyond)
+unsigned blocks_for(long long work, long long cap) {
+    const long long b = (work + 255) / 256;
+    return (unsigned)(b < 1 ? 1 : b > cap ? cap : b);
+}
+
+}  // namespace
+
+hipError_t lm_starts_fill_launch(hipStream_t stream, int blocks, double* rows, long long N, const double* x, const int* pos, const double* src,
+                                 long long src_stride, bool by_pos, long long first, int count) {
+    if (count <= 0 || N <= 0) return hipSuccess;
+    if (count > 65535) return hipErrorInvalidValue;
+    k_lm_starts_fill<<<dim3(blocks_for(N, blocks), (unsigned)count), 256, 0, stream>>>(rows, N, x, pos, src, src_stride, by_pos ? 1 : 0, first, count);
+    return hipGetLastError();
+}
+
+hipError_t lm_starts_select_launch(hipStream_t stream, const LmStartsOut& O, long long nstarts, long long ncomp) {
+    if (ncomp <= 0) return hipSuccess;
+    k_lm_starts_select<<<blocks_for(ncomp, 4096), 256, 0, stream>>>(O, nstarts, ncomp);
+    return hipGetLastError();
+}
+
+hipError_t lm_starts_gather_launch(hipStream_t stream, const LmStartsOut& O, long long nstarts, long long nfree, const int* free32, const int* comp_of,
+                                   double* x) {
+    if (nfree <= 0) return hipSuccess;
+    k_lm_starts_gather<<<blocks_for(nfree, 4096), 256, 0, stream>>>(O, nstarts, nfree, free32, comp_of, x);
+    return hipGetLastError();
+}
+
+hipError_t lm_plan_objective_launch(hipStream_t stream, long long ncomp, const double* res, long long stride, double* out) {
+    k_lm_plan_objective<<<1, 256, 0, stream>>>(ncomp, res, stride, out);
+    return hipGetLastError();
+}
+
+}  // namespace rdis_hip

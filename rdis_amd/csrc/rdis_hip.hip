@@ -18,6 +18,7 @@
 #include "solver_lds.hpp"
 #include "population_api.hpp"
 #include "population_grid.hpp"
+#include "lm_starts.hpp"
 #include "solver_pipe.hpp"
 #include "solver_quad.hpp"
 #include "solver_stream.hpp"
@@ -2946,16 +2947,29 @@ struct rdis_hip_lm_plan {
     LmBatchTableLayout lay{};
     int ncls[LM_BATCH_CLASSES] = {};
     LmPlanLayout layout;                    // replica_layout.hpp: the outputs of a solve's members, the workspace of a launch's
+    LmStartsLayout starts;                  // ... and of a multi-start solve: a row more (the winners'), best, a scratch row of x a start
     DevBuf tables, out, work;
     int64_t workspace_bytes = (int64_t)1 << 30;   // option "workspace_bytes": bounds `work`
-    // the last solve: 0 none, 1 rdis_hip_lm_plan_solve, 2 rdis_hip_lm_plan_solve_population (of last_count members).  Nothing of the
-    // population is kept: a fetch reads the plan's own `out` block
+    // the last solve: 0 none, 1 rdis_hip_lm_plan_solve, 2 rdis_hip_lm_plan_solve_population (of last_count members), 3 a multi-start
+    // solve (of last_count starts).  Nothing of the population is kept: a fetch reads the plan's own `out` block, which holds
+    // last_rows rows of each field; the plan's ordinary outputs -- what rdis_hip_lm_plan_fetch returns and
+    // rdis_hip_lm_plan_objective_device sums -- are row last_rows - 1 (kind 1: the one row; kind 3: the winners')
     int last_kind = 0;
-    int64_t last_count = 0, last_per_launch = 0, last_launches = 0;
+    int64_t last_count = 0, last_rows = 0, last_per_launch = 0, last_launches = 0;
     std::vector<double> h_res, h_hist;      // fetch's staging
-    double* res_dev(int64_t count) const { return layout.out.at<double>(out.p, LM_PLAN_RES, count); }
-    double* hist_dev(int64_t count) const { return layout.out.at<double>(out.p, LM_PLAN_HIST, count); }
-    double* x_dev(int64_t count) const { return layout.out.at<double>(out.p, LM_PLAN_X, count); }
+    // multi-start solves.  The lists are kept from create (host memory only); everything else appears at the first such solve:
+    // the tables pos[N] | comp_of[nfree] (lm_starts.hpp) in a buffer of their own, the uploaded starts [nstarts][nfree] with their
+    // pinned staging, and the one double of rdis_hip_lm_plan_objective_device
+    std::vector<int64_t> h_free_ptr, h_free_vid;
+    std::vector<int32_t> h_starts_tables;
+    DevBuf starts_tables, starts_in, starts_stage, objective;
+    hipEvent_t starts_stage_ev = nullptr;
+    bool starts_stage_busy = false;
+    ~rdis_hip_lm_plan() { if (starts_stage_ev) (void)hipEventDestroy(starts_stage_ev); }
+    // row `row` of a field of `out` laid out for `rows` rows
+    double* res_dev(int64_t rows, int64_t row = 0) const { return layout.out.at<double>(out.p, LM_PLAN_RES, rows) + row * layout.out.doubles(LM_PLAN_RES); }
+    double* hist_dev(int64_t rows, int64_t row = 0) const { return layout.out.at<double>(out.p, LM_PLAN_HIST, rows) + row * layout.out.doubles(LM_PLAN_HIST); }
+    double* x_dev(int64_t rows, int64_t row = 0) const { return layout.out.at<double>(out.p, LM_PLAN_X, rows) + row * layout.out.doubles(LM_PLAN_X); }
 };
 
 namespace {
@@ -2987,23 +3001,25 @@ int lm_plan_enqueue(rdis_hip_lm_plan* L, double* x0, long long x_stride, int64_t
     return 0;
 }
 
-// the outputs of the last solve's `count` members: one download each of the members' x, the result rows and the history, one wait
-int lm_plan_download(rdis_hip_lm_plan* L, int64_t count, double* x_out, double* fret, double* delta, double* info8, double* hist4, int64_t* nhist) {
+// `count` rows of the last solve's outputs from row `row0` on (the block holds L->last_rows): one download each of the rows' x, the
+// result rows and the history, one wait
+int lm_plan_download(rdis_hip_lm_plan* L, int64_t row0, int64_t count, double* x_out, double* fret, double* delta, double* info8, double* hist4, int64_t* nhist) {
     rdis_hip_ctx* c = L->prob->ctx;
+    const int64_t held = L->last_rows;
     const size_t rows = (size_t)count * (size_t)L->ncomp;
     if (rows == 0) return 0;
     const bool want_x = x_out && L->nfree > 0;
     if (!(want_x || fret || delta || info8 || hist4 || nhist)) return 0;
     const bool want_hist = hist4 && L->hist_cap > 0;
-    if (want_x) HIPCHK(c, hipMemcpyAsync(x_out, L->x_dev(count), (size_t)count * (size_t)L->nfree * 8, hipMemcpyDeviceToHost, c->stream));
+    if (want_x) HIPCHK(c, hipMemcpyAsync(x_out, L->x_dev(held, row0), (size_t)count * (size_t)L->nfree * 8, hipMemcpyDeviceToHost, c->stream));
     L->h_res.resize(rows * LM_BATCH_RES);
-    HIPCHK(c, hipMemcpyAsync(L->h_res.data(), L->res_dev(count), rows * LM_BATCH_RES * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(L->h_res.data(), L->res_dev(held, row0), rows * LM_BATCH_RES * 8, hipMemcpyDeviceToHost, c->stream));
     if (want_hist) {
         L->h_hist.resize(rows * (size_t)L->hist_cap * 4);
-        HIPCHK(c, hipMemcpyAsync(L->h_hist.data(), L->hist_dev(count), rows * (size_t)L->hist_cap * 32, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(L->h_hist.data(), L->hist_dev(held, row0), rows * (size_t)L->hist_cap * 32, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (size_t cc = 0; cc < rows; ++cc) {   // (member-major in both: row cc is component cc % ncomp of member cc / ncomp)
+    for (size_t cc = 0; cc < rows; ++cc) {   // (row-major in both: entry cc is component cc % ncomp of row row0 + cc / ncomp)
         const double* r = L->h_res.data() + cc * LM_BATCH_RES;
         if (fret) fret[cc] = r[0];
         if (delta) delta[cc] = r[0] - r[1];
@@ -3039,6 +3055,9 @@ extern "C" int rdis_hip_lm_plan_create(rdis_hip_problem* p, int64_t ncomp, const
     for (int k = 0; k < LM_BATCH_CLASSES; ++k) L->ncls[k] = (int)T.order[k].size();
     L->lay = lm_batch_table_layout(T);
     L->layout = lm_plan_layout(ncomp, LM_BATCH_RES, hist_cap, L->nfree, T.ws_doubles);
+    L->starts = lm_starts_layout(ncomp, LM_BATCH_RES, hist_cap, L->nfree, T.ws_doubles, p->N);
+    L->h_free_ptr.assign(free_ptr, free_ptr + ncomp + 1);   // (for lm_starts_tables, at the first multi-start solve)
+    if (L->nfree > 0) L->h_free_vid.assign(free_vid, free_vid + L->nfree);
     // the one upload of the plan's life: nothing in the tables depends on x
     std::vector<char> stage(L->lay.bytes);
     lm_batch_stage_tables(T, L->lay, stage.data());
@@ -3062,7 +3081,7 @@ extern "C" int rdis_hip_lm_plan_solve(rdis_hip_lm_plan* L, int32_t maxiters, dou
     USE_DEVICE(c);
     const int rc = lm_plan_enqueue(L, p->x.as<double>(), 0, 1, maxiters, ftol);
     if (rc) return rc;
-    L->last_kind = 1; L->last_count = 1;
+    L->last_kind = 1; L->last_count = 1; L->last_rows = 1;
     return 0;
 }
 
@@ -3070,10 +3089,10 @@ extern "C" int rdis_hip_lm_plan_fetch(rdis_hip_lm_plan* L, double* x_out, double
     if (!L) return RDIS_HIP_EINVAL;
     rdis_hip_problem* p = L->prob;
     rdis_hip_ctx* c = p->ctx;
-    if (L->last_kind != 1)
+    if (L->last_kind != 1 && L->last_kind != 3)
         return fail(c, RDIS_HIP_EINVAL, L->last_kind == 0 ? "lm_plan_fetch: nothing was solved yet" : "lm_plan_fetch: the last solve was a population solve (rdis_hip_lm_plan_fetch_population)");
     USE_DEVICE(c);
-    return lm_plan_download(L, 1, x_out, fret, delta, info8, hist4, nhist);
+    return lm_plan_download(L, L->last_rows - 1, 1, x_out, fret, delta, info8, hist4, nhist);   // (after a multi-start solve: the winners' row)
 }
 
 extern "C" int rdis_hip_lm_plan_solve_population(rdis_hip_lm_plan* L, rdis_hip_population* pop, int64_t first, int64_t count, int32_t maxiters, double ftol) {
@@ -3090,7 +3109,7 @@ extern "C" int rdis_hip_lm_plan_solve_population(rdis_hip_lm_plan* L, rdis_hip_p
     pop->eval_valid = false; pop->best_current = false;   // X is written: the values of the last evaluation are stale
     const int rc = lm_plan_enqueue(L, pop->row(first), (long long)p->N, count, maxiters, ftol);
     if (rc) return rc;
-    L->last_kind = 2; L->last_count = count;
+    L->last_kind = 2; L->last_count = count; L->last_rows = count;
     return 0;
 }
 
@@ -3101,7 +3120,146 @@ extern "C" int rdis_hip_lm_plan_fetch_population(rdis_hip_lm_plan* L, double* x_
     if (L->last_kind != 2)
         return fail(c, RDIS_HIP_EINVAL, L->last_kind == 0 ? "lm_plan_fetch_population: nothing was solved yet" : "lm_plan_fetch_population: the last solve was not a population solve (rdis_hip_lm_plan_fetch)");
     USE_DEVICE(c);
-    return lm_plan_download(L, L->last_count, x_out, fret, delta, info8, hist4, nhist);
+    return lm_plan_download(L, 0, L->last_count, x_out, fret, delta, info8, hist4, nhist);
+}
+
+// ---- multi-start solves: every component from each of S rows of start values, the problem left at the best start per component ----
+namespace {
+// What both entries do once their starts are on the device: `src` holds start s's values at src + (first + s) * src_stride, in
+// free-list order (by_pos) or by variable id.  Rounds of fill + the class launches on scratch rows, then select and gather.
+// After the first call of a size: no allocation; never a wait.
+int lm_plan_enqueue_starts(rdis_hip_lm_plan* L, const char* who, int64_t nstarts, const double* src, long long src_stride, bool by_pos, int64_t first,
+                           int32_t maxiters, double ftol) {
+    rdis_hip_problem* p = L->prob;
+    rdis_hip_ctx* c = p->ctx;
+    const LmStartsLayout& Y = L->starts;
+    const int64_t rows = Y.out_rows(nstarts);
+    const int64_t per = members_per_launch(nstarts, L->workspace_bytes, Y.work.member_bytes());
+    int rc = ensure(c, L->out, (size_t)Y.out_bytes(nstarts));
+    if (!rc) rc = ensure(c, L->work, (size_t)Y.work.total_bytes(per));
+    if (rc) return rc;
+    const int* const pos = L->starts_tables.as<int>();
+    const int* const comp_of = pos + p->N;
+    double* const xrows = Y.work.at<double>(L->work.p, LM_STARTS_ROWS, per);
+    const LmBatchOptions o{maxiters, L->R, 1e-3, 1e-15, 1e-15, ftol};
+    const int classes = (L->ncls[0] > 0) + (L->ncls[1] > 0) + (L->ncls[2] > 0) + (L->ncls[3] > 0);
+    L->last_kind = 0;   // (what an earlier solve left in `out` is overwritten from here on)
+    L->last_per_launch = 0; L->last_launches = 0;
+    for (int64_t m0 = 0; m0 < nstarts; m0 += per) {
+        const int64_t n = std::min(per, nstarts - m0);
+        HIPCHK(c, lm_starts_fill_launch(c->stream, grid_for(c, p->N, 256), xrows, p->N, p->x.as<double>(), pos, src, src_stride, by_pos, first + m0, (int)n));
+        const LmBatchProblem P{xrows, p->lo.as<double>(), p->hi.as<double>(), p->cam.as<int>(), p->pt.as<int>(), p->obs.as<double2>()};
+        const LmBatchMembers M{(long long)p->N, L->res_dev(rows, m0), Y.out.doubles(LM_PLAN_RES), L->hist_dev(rows, m0), Y.out.doubles(LM_PLAN_HIST),
+                               Y.work.at<double>(L->work.p, LM_STARTS_WS, per), Y.work.doubles(LM_STARTS_WS),
+                               L->x_dev(rows, m0), Y.out.doubles(LM_PLAN_X), (int)n};
+        const int e = lm_batch_launch(c->stream, P, L->tables.p, L->lay, L->ncls, o, L->hist_cap, M);
+        if (e != 0) return fail(c, RDIS_HIP_EDEVICE, std::string(who) + ": " + hipGetErrorString((hipError_t)e));
+        L->last_launches += classes;
+    }
+    const LmStartsOut O{L->res_dev(rows), L->hist_dev(rows), L->x_dev(rows), Y.out.doubles(LM_PLAN_RES), Y.out.doubles(LM_PLAN_HIST), Y.out.doubles(LM_PLAN_X),
+                        (long long)L->hist_cap, LM_BATCH_RES, LM_BATCH_RES_NHIST, reinterpret_cast<int*>(static_cast<char*>(L->out.p) + Y.best_offset(nstarts))};
+    HIPCHK(c, lm_starts_select_launch(c->stream, O, nstarts, L->ncomp));
+    HIPCHK(c, lm_starts_gather_launch(c->stream, O, nstarts, L->nfree, reinterpret_cast<const int*>(static_cast<const char*>(L->tables.p) + L->lay.free32),
+                                      comp_of, p->x.as<double>()));
+    L->last_per_launch = per;
+    L->last_kind = 3; L->last_count = nstarts; L->last_rows = rows;
+    return 0;
+}
+
+// pos[N] | comp_of[nfree], built and uploaded at the first multi-start solve (the host image is kept: the upload is asynchronous)
+int lm_plan_starts_tables(rdis_hip_lm_plan* L) {
+    if (L->starts_tables.p) return 0;
+    rdis_hip_problem* p = L->prob;
+    std::vector<int32_t> pos, comp_of;
+    lm_starts_tables(p->N, L->ncomp, L->h_free_ptr.data(), L->h_free_vid.data(), pos, comp_of);
+    L->h_starts_tables = std::move(pos);
+    L->h_starts_tables.insert(L->h_starts_tables.end(), comp_of.begin(), comp_of.end());
+    return upload(p->ctx, L->starts_tables, L->h_starts_tables);
+}
+
+// a start count the outputs can be sized for: rows of int32 ids, byte counts far inside int64
+bool lm_plan_starts_sizable(const rdis_hip_lm_plan* L, int64_t nstarts) {
+    const double row = (double)std::max<int64_t>(std::max<int64_t>(L->ncomp * (LM_BATCH_RES + 4 * std::max<int64_t>(L->hist_cap, 1)), L->nfree), 1);
+    return nstarts < (1ll << 31) - 1 && ((double)nstarts + 1.0) * row < 1.0e15;
+}
+}  // namespace
+
+extern "C" int rdis_hip_lm_plan_solve_starts(rdis_hip_lm_plan* L, int64_t nstarts, const double* x_starts, int32_t maxiters, double ftol) {
+    if (!L) return RDIS_HIP_EINVAL;
+    rdis_hip_problem* p = L->prob;
+    rdis_hip_ctx* c = p->ctx;
+    if (maxiters < 1) return fail(c, RDIS_HIP_EINVAL, "lm_plan_solve_starts: maxiters must be positive");
+    if (nstarts < 1) return fail(c, RDIS_HIP_EINVAL, "lm_plan_solve_starts: nstarts must be at least 1");
+    if (!x_starts) return fail(c, RDIS_HIP_EINVAL, "lm_plan_solve_starts: x_starts is NULL (a row of start values per start)");
+    if (!lm_plan_starts_sizable(L, nstarts)) return fail(c, RDIS_HIP_ERANGE, "lm_plan_solve_starts: too many starts");
+    if (L->ncomp == 0) return 0;
+    USE_DEVICE(c);
+    int rc = lm_plan_starts_tables(L);
+    if (rc) return rc;
+    // the starts: through pinned memory, so that the caller may reuse x_starts the moment this returns and nothing waits
+    const size_t in_bytes = (size_t)nstarts * (size_t)L->nfree * sizeof(double);
+    if ((rc = ensure(c, L->starts_in, in_bytes))) return rc;
+    if (in_bytes > 0 && in_bytes <= STARTS_STAGE_MAX_BYTES) {
+        if (L->starts_stage_busy) { HIPCHK(c, hipEventSynchronize(L->starts_stage_ev)); L->starts_stage_busy = false; }
+        if (L->starts_stage.bytes < in_bytes && (rc = halloc(c, L->starts_stage, in_bytes))) return rc;
+        if (!L->starts_stage_ev) HIPCHK(c, hipEventCreateWithFlags(&L->starts_stage_ev, hipEventDisableTiming));
+        std::memcpy(L->starts_stage.p, x_starts, in_bytes);
+        HIPCHK(c, hipMemcpyAsync(L->starts_in.p, L->starts_stage.p, in_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(L->starts_stage_ev, c->stream));
+        L->starts_stage_busy = true;
+    } else if (in_bytes > 0) {
+        HIPCHK(c, hipMemcpyAsync(L->starts_in.p, x_starts, in_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return lm_plan_enqueue_starts(L, "lm_plan_solve_starts", nstarts, L->starts_in.as<double>(), (long long)L->nfree, true, 0, maxiters, ftol);
+}
+
+extern "C" int rdis_hip_lm_plan_solve_starts_population(rdis_hip_lm_plan* L, rdis_hip_population* pop, int64_t first, int64_t count, int32_t maxiters,
+                                                        double ftol) {
+    if (!L || !pop) return RDIS_HIP_EINVAL;
+    rdis_hip_problem* p = L->prob;
+    rdis_hip_ctx* c = p->ctx;
+    if (maxiters < 1) return fail(c, RDIS_HIP_EINVAL, "lm_plan_solve_starts_population: maxiters must be positive");
+    if (pop->prob != p) return fail(c, RDIS_HIP_EINVAL, "lm_plan_solve_starts_population: the population belongs to another problem than the plan's");
+    if (count < 1 || first < 0 || first > pop->nmembers || count > pop->nmembers - first)
+        return fail(c, RDIS_HIP_EINVAL, "lm_plan_solve_starts_population: members out of range (count >= 1, first + count <= nmembers)");
+    if (!lm_plan_starts_sizable(L, count)) return fail(c, RDIS_HIP_ERANGE, "lm_plan_solve_starts_population: too many starts");
+    if (L->ncomp == 0) return 0;
+    USE_DEVICE(c);
+    const int rc = lm_plan_starts_tables(L);
+    if (rc) return rc;
+    // (the population is read only: its rows, its values and what rdis_hip_population_best answers stay as they are)
+    return lm_plan_enqueue_starts(L, "lm_plan_solve_starts_population", count, pop->X.as<double>(), (long long)p->N, false, first, maxiters, ftol);
+}
+
+extern "C" int rdis_hip_lm_plan_fetch_starts(rdis_hip_lm_plan* L, double* x_out, double* fret, double* delta, double* info8, double* hist4, int64_t* nhist,
+                                             int32_t* best) {
+    if (!L) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = L->prob->ctx;
+    if (L->last_kind != 3)
+        return fail(c, RDIS_HIP_EINVAL, L->last_kind == 0 ? "lm_plan_fetch_starts: nothing was solved yet" : "lm_plan_fetch_starts: the last solve was not a multi-start solve (rdis_hip_lm_plan_fetch, rdis_hip_lm_plan_fetch_population)");
+    USE_DEVICE(c);
+    if (best && L->ncomp > 0)   // (on the stream, ahead of the download's wait -- or of this one's, where nothing else is asked for)
+        HIPCHK(c, hipMemcpyAsync(best, static_cast<const char*>(L->out.p) + L->starts.best_offset(L->last_count), (size_t)L->ncomp * sizeof(int32_t),
+                                 hipMemcpyDeviceToHost, c->stream));
+    const int rc = lm_plan_download(L, 0, L->last_count, x_out, fret, delta, info8, hist4, nhist);
+    if (rc) return rc;
+    if (best && L->ncomp > 0) HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int rdis_hip_lm_plan_objective_device(rdis_hip_lm_plan* L, void** dev_ptr) {
+    if (!L || !dev_ptr) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = L->prob->ctx;
+    if (L->last_kind != 1 && L->last_kind != 3)
+        return fail(c, RDIS_HIP_EINVAL, L->last_kind == 0 ? "lm_plan_objective_device: nothing was solved yet"
+                                                          : "lm_plan_objective_device: the last solve was a population solve (its members have no common objective)");
+    USE_DEVICE(c);
+    if (!L->objective.p) { const int rc = dalloc(c, L->objective, sizeof(double)); if (rc) return rc; }
+    HIPCHK(c, lm_plan_objective_launch(c->stream, L->ncomp, L->ncomp > 0 ? L->res_dev(L->last_rows, L->last_rows - 1) : nullptr, LM_BATCH_RES,
+                                       L->objective.as<double>()));
+    *dev_ptr = L->objective.p;
+    return 0;
 }
 
 extern "C" int rdis_hip_lm_plan_set_option(rdis_hip_lm_plan* L, const char* name, int64_t value) {
@@ -3119,7 +3277,7 @@ extern "C" int rdis_hip_lm_plan_get_info(rdis_hip_lm_plan* L, const char* name, 
     const std::string n(name);
     if (n == "members_per_launch") *value = L->last_per_launch;
     else if (n == "launches") *value = L->last_launches;
-    else if (n == "device_bytes") *value = (int64_t)(L->tables.bytes + L->out.bytes + L->work.bytes);
+    else if (n == "device_bytes") *value = (int64_t)(L->tables.bytes + L->out.bytes + L->work.bytes + L->starts_tables.bytes + L->starts_in.bytes + L->objective.bytes);
     else if (n == "workspace_bytes") *value = L->workspace_bytes;
     else if (n == "member_workspace_bytes") *value = L->layout.work.member_bytes();
     else return fail(L->prob->ctx, RDIS_HIP_EINVAL, "lm_plan_get_info: unknown name '" + n + "' (members_per_launch, launches, device_bytes, workspace_bytes, "

@@ -4,7 +4,8 @@
 // per-solve arrays, in one buffer laid out [R][part 0] [R][part 1] ...  A ReplicaLayout names the parts and their bytes per
 // member; the buffer's size, the members a budget allows and every pointer and stride the kernels are handed come from it.
 // The Levenberg-Marquardt plan's solves (rdis_hip_lm_plan_solve, rdis_hip_lm_plan_solve_population) describe their two buffers the
-// same way (lm_plan_layout) and split their members by the same rule.
+// same way (lm_plan_layout) and split their members by the same rule; its multi-start solves (rdis_hip_lm_plan_solve_starts,
+// rdis_hip_lm_plan_solve_starts_population) add a winners' row, best[ncomp] and a scratch row of x a start (lm_starts_layout).
 // Pure host functions: no HIP call, no plan, no population (tests/cpp/replica_layout_test.cpp runs them without a device).
 #pragma once
 #include <algorithm>
@@ -93,6 +94,25 @@ enum { LM_PLAN_WS = 0 };
 struct LmPlanLayout { ReplicaLayout out, work; };
 inline LmPlanLayout lm_plan_layout(int64_t ncomp, int64_t res_doubles, int64_t hist_cap, int64_t nfree, int64_t ws_doubles) {
     return LmPlanLayout{ReplicaLayout(3, 8 * res_doubles * ncomp, 8 * 4 * hist_cap * ncomp, 8 * nfree), ReplicaLayout(1, 8 * ws_doubles)};
+}
+
+// ---- rdis_hip_lm_plan_solve_starts, rdis_hip_lm_plan_solve_starts_population ----
+// The same two buffers for a solve of nstarts starts.  `out` has nstarts + 1 rows of lm_plan_layout's three fields: row s < nstarts
+// is start s's, row nstarts the winners' (per component the row of its best start: the plan's ordinary outputs after such a
+// solve); behind the rows best[ncomp] (int32, padded to 8 bytes).  `work` charges a start of a launch its workspace slices and its
+// scratch row of x (N doubles: the free variables from the start, everything else the problem's x).
+enum { LM_STARTS_WS = 0, LM_STARTS_ROWS = 1 };
+struct LmStartsLayout {
+    ReplicaLayout out, work;
+    int64_t ncomp = 0;
+    int64_t out_rows(int64_t nstarts) const { return nstarts + 1; }
+    int64_t winners_row(int64_t nstarts) const { return nstarts; }
+    int64_t best_offset(int64_t nstarts) const { return out.total_bytes(out_rows(nstarts)); }   // bytes from out's base to best[ncomp]
+    int64_t best_bytes() const { return (4 * std::max<int64_t>(ncomp, 0) + 7) / 8 * 8; }
+    int64_t out_bytes(int64_t nstarts) const { return best_offset(nstarts) + best_bytes(); }
+};
+inline LmStartsLayout lm_starts_layout(int64_t ncomp, int64_t res_doubles, int64_t hist_cap, int64_t nfree, int64_t ws_doubles, int64_t nvars) {
+    return LmStartsLayout{lm_plan_layout(ncomp, res_doubles, hist_cap, nfree, ws_doubles).out, ReplicaLayout(2, 8 * ws_doubles, 8 * nvars), ncomp};
 }
 
 // Members of one launch: the member is the grid's second dimension (at most 65535) and every member of a launch has
