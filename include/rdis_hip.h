@@ -164,7 +164,16 @@ int rdis_hip_grad_each_ba(rdis_hip_problem *p, int64_t nf, const int64_t *fac, d
  * info[8] = {iterations, stop code (levmar's: 1 small gradient, 2 small step, 3 itmax,
  * 4 singular, 5 no further reduction, 6 small error, 7 invalid values), residual evaluations,
  * Jacobian evaluations, linear solves, final damping mu, camera blocks, point blocks};
- * hist (may be NULL): up to hist_cap records {mu, |Dp|^2, f(trial), accepted} per linear solve. */
+ * hist (may be NULL): up to hist_cap records {mu, |Dp|^2, f(trial), accepted} per linear solve.
+ * A start at which the listed factors' value is not finite (a NaN coordinate; a point in a camera's plane) ends with
+ * code 7 before anything is linearised: 0 iterations, 1 residual evaluation, no Jacobian evaluation, no linear solve, no
+ * history record, fret not finite; a NaN coordinate is left NaN, every other free variable clamped into its domain as
+ * always.  The same holds for every component of rdis_hip_lm_batch and of the plans below, whatever its class; the other
+ * components of the call, and the other members or starts, are not affected.  (maxiters < 1 is RDIS_HIP_EINVAL in every
+ * entry, so no call skips that test and returns code 3 for such a start.)
+ * Listed factors that read no free variable of the call (or of a component) are not refused: the gradient is zero, the
+ * solve ends with code 1 at iteration 0 (1 Jacobian evaluation, no linear solve), x = clamp(start), fret = the value at
+ * the start.  A free camera or point block that no listed factor reads is damped like the others and gets the step 0. */
 int rdis_hip_lm_optimize(rdis_hip_problem *p, int64_t nfree, const int64_t *free_vid, int64_t nf,
                          const int64_t *fac_id, double *x_inout, int32_t maxiters, double ftol,
                          int32_t residual_model, double *fret, double *delta, double *info8, double *hist4, int64_t hist_cap,

@@ -13,7 +13,10 @@ non-linear least squares problems", 2004, Alg. 3.16).  Dense linear algebra in n
 solver (Schur complement over camera / point blocks) is checked against it step by step.
 
 Stop codes (levmar's numbering): 1 small gradient, 2 small step, 3 itmax, 4 singular, 5 no further
-reduction possible, 6 small error, 7 invalid values."""
+reduction possible, 6 small error, 7 invalid values.  A start whose objective is not finite ends with code 7 before
+anything is linearised (0 iterations, 1 residual evaluation, no solve); a NaN coordinate stays NaN through the clamp.
+With maxiters = 0 the loop, and that test with it, does not run: code 3 for any start (the device entries refuse
+maxiters < 1)."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -98,6 +101,9 @@ def lm_optimize(o, free_vid=None, fac=None, x=None, maxiters=25, ftol=3e-8, tau=
     hist = []
     k = 0
     while k < maxiters and not stop:
+        if not np.isfinite(p_eL2):            # a start whose objective is not finite: nothing is linearised
+            stop = 7
+            break
         if p_eL2 <= eps3:
             stop = 6
             break

@@ -607,6 +607,7 @@ __global__ void __launch_bounds__(lm_batch_class_threads(CLS)) k_lm_batch(BatchD
     long long nh = 0;
     const double EPSILON = 1e-12, ONE_THIRD = 0.3333333334;
     while (k < B.maxiters && !stop) {
+        if (!isfinite(p_eL2)) { stop = 7; break; }   // a start whose objective is not finite: nothing is linearised (every thread holds the same sum)
         if (p_eL2 <= B.eps3) { stop = 6; break; }
         double maxdiag, jte_inf, p_L2;
         linearise(maxdiag, jte_inf, p_L2);
@@ -654,7 +655,7 @@ __global__ void __launch_bounds__(lm_batch_class_threads(CLS)) k_lm_batch(BatchD
     for (int i = tid; i < nfree; i += NT) {   // x = clamp(accepted point)
         const int v = fv[i];
         const double xv = psave[i], lo = B.lo[v], hi = B.hi[v];
-        const double xc = (lo <= xv && xv <= hi) ? xv : (xv < lo ? lo : hi);
+        const double xc = xv < lo ? lo : (xv > hi ? hi : xv);   // (a NaN stays a NaN)
         x[v] = xc;
         if (MEMBERS) B.xout[mem * B.xout_ms + C.free0 + i] = xc;
     }

@@ -743,7 +743,7 @@ __global__ void __launch_bounds__(1024) k_apply(Dev D, int mode) {
             D.P.x[v] = D.psave[t];
         } else {
             const double x = D.psave[t], lo = D.P.lo[v], hi = D.P.hi[v];
-            D.P.x[v] = (lo <= x && x <= hi) ? x : (x < lo ? lo : hi);
+            D.P.x[v] = x < lo ? lo : (x > hi ? hi : x);   // (a NaN stays a NaN)
         }
     }
     if (mode != 0) return;
@@ -1036,6 +1036,7 @@ int device_lm_ba(hipStream_t stream, const LmProblem& P, int64_t nfree, const in
     int stop = 0, k = 0;
     const double EPSILON = 1e-12, ONE_THIRD = 0.3333333334;
     while (k < opt.maxiters && !stop) {
+        if (!std::isfinite(p_eL2)) { stop = 7; break; }   // a start whose objective is not finite: nothing is linearised
         if (p_eL2 <= opt.eps3) { stop = 6; break; }
         if ((rc = run(enqueue_linearise))) return rc;
         ++out->njev;

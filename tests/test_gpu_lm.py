@@ -10,10 +10,12 @@ from oracle import lm_oracle as LM
 from oracle import oracle as O
 from rdis_amd import capi, problems as P
 
+from lm_exit_cases import check_identities
+
 pytestmark = pytest.mark.gpu
 
 
-def _compare(r, ro, tol_hist=1e-7):
+def _compare(r, ro, tol_hist=1e-7, cap=256):
     # Once a trial objective equals the current one to 1e-11 the solve has converged and accepting or
     # rejecting a step is decided by rounding: histories are compared up to that point, results always.
     n_cmp, fcur = len(ro.history), ro.finit
@@ -23,10 +25,18 @@ def _compare(r, ro, tol_hist=1e-7):
             break
         if ok:
             fcur = ft
+    # the loop's counter identities, whatever the exit (cap: the capacity the history was fetched with -- the default of Problem.lm_optimize)
+    check_identities(r, ro.finit, cap)
     if n_cmp == len(ro.history):
         assert (r.iters, r.stop, r.nsolve, r.nfev, r.njev) == (ro.iters, ro.stop, ro.nsolve, ro.nfev, ro.njev)
         assert len(r.history) == len(ro.history)
         assert abs(r.mu - ro.mu) <= 1e-6 * ro.mu
+    else:
+        # the oracle converged: the device ends as the oracle does, or -- where rounding decides the last steps -- with a small
+        # step (2) or refused steps (5)
+        assert r.stop in (2, 5, ro.stop)
+        if ro.stop in (2, 5):
+            assert r.stop in (2, 5)
     assert len(r.history) >= n_cmp
     for (mu, dp, ft, ok), (omu, odp, oft, ook) in list(zip(r.history, ro.history))[:n_cmp]:
         assert bool(ok) == bool(ook)                                    # same accept / reject decisions

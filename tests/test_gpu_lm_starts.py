@@ -4,7 +4,7 @@ the best start per component.  The yardstick is rdis_hip_lm_batch on a fresh pro
 tests/test_gpu_lm_plan.py: every (start, component) must equal it with == -- every field, the history's and x's bytes -- and
 the winners, the problem's x afterwards and the plan's ordinary outputs must be what the select rule, written with numpy, makes
 of those results.  tests/test_lm_starts_cpu.py pins that the starts discriminate (distinct winners, no near ties) and checks the
-rule's NaN cases, which no test here feeds."""
+rule's NaN cases; tests/test_gpu_lm_exits.py feeds them on the device (one NaN start among four, and all four)."""
 import math
 
 import numpy as np
