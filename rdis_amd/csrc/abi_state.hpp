@@ -249,6 +249,11 @@ struct rdis_hip_plan : PlanOptions, PlanIndex {
     // results block: xout[nfree] fret[nc] delta[nc] (f64) | nfeval[nc] ngeval[nc] (i64) | iters[nc] status[nc] trace_n[nc] (i32)
     size_t out_bytes = 0;
     cvec h_out;
+    // a resident plan's host image of the results block is pinned (plan_create): the D2H copy of rdis_hip_plan_fetch then lands
+    // without the runtime's staging of a pageable destination.  It starts at byte h_pin_base of the block (a long x never passes
+    // through it: DIRECT_X_BYTES).  Empty -- a transient plan, a block over the bound, no pinned memory to be had -- : h_out.
+    DevBuf h_pin;
+    size_t h_pin_base = 0;
     bool have_start = false;
 
     // ---- what prepare_partition decides: which components go where (rebuilt when an option changes) ----
@@ -261,6 +266,7 @@ struct rdis_hip_plan : PlanOptions, PlanIndex {
     std::vector<ivec> h_coop_wg;
     bool use_pipe = false;            // the plan's groups fit the pipelined layout (fewer factor lanes per workgroup)
     bool pipelined() const { return use_pipe; }
+    bool objective_in_solver = false; // the plan's one launch is the single-group pipelined solver, which stores the objective itself (CoopArgs::objective)
     int coop_lanes() const;           // factor lanes per workgroup of a cooperative group
     std::vector<StreamItem> stream;
     ivec h_rest;                      // the batch list: tiny components, then the plain solver's, the point-major ones, the LDS-resident ones

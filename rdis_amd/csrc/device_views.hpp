@@ -183,6 +183,8 @@ struct CoopArgs {
     int stale;             // ... with it, plan option emulate_stale_cache: the reference's factor cache (Variable.cpp:66-76, Factor.h:228-234)
     int poll_inflight;     // pipelined solver, plan option coop_poll_inflight: the collector keeps several polls of a slot in flight (solver_pipe.hpp: sweep_ring)
     int poll_stagger;      // ... x64 cycles between two of them (coop_poll_stagger)
+    double* objective;     // pipelined solver, a plan whose one launch is this group: where the lane that writes fret stores the plan's
+                           // objective as well (what objective_sum_kernel would make of the one fret); nullptr otherwise
 };
 
 // One launch solves several components side by side: workgroups [wg0, wg0 + nwg) of the grid form

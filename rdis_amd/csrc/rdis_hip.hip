@@ -744,6 +744,7 @@ namespace {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 constexpr size_t DIRECT_X_BYTES = 4u << 20;    // a result vector this long is copied straight into the caller's array (rdis_hip_plan_fetch)
+constexpr size_t PINNED_OUT_MAX_BYTES = 64u << 20;   // a resident plan's host image of its results block is pinned up to this size
 constexpr size_t STAGE_MAX_BYTES = 1u << 20;   // start points staged through pinned memory up to this size (resident plans)
 
 // plan memory: a persistent plan owns hipMalloc'ed buffers; a transient one (cgd_batch, i.e.
@@ -846,7 +847,16 @@ static int plan_create_impl(rdis_hip_problem* p, bool transient, int64_t ncomp, 
     if (!rc) rc = plan_alloc(L, L->outbuf, L->out_bytes);
     if (!rc) rc = plan_alloc(L, L->objective, 64);
     if (rc) return rc;
-    L->h_out.resize(L->out_bytes);
+    if (!transient && L->out_bytes > 0) {
+        // (a result vector of DIRECT_X_BYTES and more goes straight into the caller's array or is not fetched at all)
+        const size_t base = (size_t)nfree * 8 >= DIRECT_X_BYTES ? (size_t)nfree * 8 : 0;
+        if (L->out_bytes - base <= PINNED_OUT_MAX_BYTES) {
+            const std::string err = c->err;
+            if (halloc(c, L->h_pin, L->out_bytes - base) == 0) L->h_pin_base = base;
+            else { (void)hipGetLastError(); c->err = err; }   // no pinned memory: the pageable block below, and no error
+        }
+    }
+    if (!L->h_pin.p) L->h_out.resize(L->out_bytes);
     if (!blk.empty()) HIPCHK(c, hipMemcpyAsync(L->ints.p, blk.data(), blk.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     guard.l = nullptr;
     *out = L;
@@ -987,6 +997,7 @@ void drop_partition(rdis_hip_plan* L) {
     L->h_coop_wg.clear();
     L->stream.clear();
     L->h_rest.clear();
+    L->objective_in_solver = false;
 }
 
 // workgroups of a component's cooperative group with `lanes` factor lanes each: a lane per factor / variable, a wave per long gradient run
@@ -1411,7 +1422,7 @@ int pack_coop_launches(rdis_hip_plan* L, int cap) {
                            // (a small group's sweep is one entry per lane: polling early costs it less than waiting)
                            it.nwg * (L->coop_lanes() / 64) <= 64 ? std::min(4, L->coop_poll_delay) : L->coop_poll_delay,
                            L->coop_speculate, L->factor_rounding == 1 ? 1 : 0, (L->factor_rounding == 1 && L->emulate_stale) ? 1 : 0,
-                           L->coop_poll_inflight, L->coop_poll_stagger};
+                           L->coop_poll_inflight, L->coop_poll_stagger, nullptr /* set below */};
             g.wg0 = cl.total_wg; g.nwg = it.nwg;
             hg.push_back(g);
             hw.insert(hw.end(), (size_t)it.nwg, cl.count);
@@ -1436,10 +1447,14 @@ int pack_coop_launches(rdis_hip_plan* L, int cap) {
         HIPCHK(c, hipMemcpyAsync(L->coop_launches.back().wg_group.p, L->h_coop_wg.back().data(),
                                  L->h_coop_wg.back().size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     }
+    // a plan whose one launch is the single-group pipelined solver: that kernel stores the plan's objective with the component's
+    // fret, and rdis_hip_plan_solve launches no objective_sum_kernel behind it
+    L->objective_in_solver = L->pipelined() && L->ncomp == 1 && L->coop.size() == 1 && L->h_rest.empty() && L->stream.empty();
     // (the state pointers only now: the buffer may have moved while the launches were sized)
     for (size_t l = 0; l < L->coop_launches.size(); ++l) {
         std::vector<CoopGroup>& hg = L->h_coop_groups[l];
         for (size_t g = 0; g < hg.size(); ++g) hg[g].a.st = p->coop_state.as<CoopState>() + g;
+        if (L->objective_in_solver) hg[0].a.objective = L->objective.as<double>();
         HIPCHK(c, hipMemcpyAsync(L->coop_launches[l].groups.p, hg.data(), hg.size() * sizeof(CoopGroup), hipMemcpyHostToDevice, c->stream));
     }
     return 0;
@@ -1880,8 +1895,10 @@ extern "C" int rdis_hip_plan_solve(rdis_hip_plan* L, int32_t maxiters, double ft
     HIPCHK(c, hipEventRecord(p->ev1, c->stream));
     L->timed = true;
     p->last_timed_plan = L;
-    objective_sum_kernel<<<1, 256, 0, c->stream>>>((int)L->ncomp, V.fret, L->objective.as<double>());
-    HIPCHK(c, hipGetLastError());
+    if (!L->objective_in_solver) {   // (else the one launch above has stored it: pack_coop_launches)
+        objective_sum_kernel<<<1, 256, 0, c->stream>>>((int)L->ncomp, V.fret, L->objective.as<double>());
+        HIPCHK(c, hipGetLastError());
+    }
     return 0;
 }
 
@@ -1898,14 +1915,16 @@ extern "C" int rdis_hip_plan_fetch(rdis_hip_plan* L, double* x_out, double* fret
     const bool direct_x = x_out != nullptr && nf * 8 >= DIRECT_X_BYTES;
     const size_t skip = (x_out && !direct_x) ? 0 : nf * 8;
     if (direct_x) HIPCHK(c, hipMemcpyAsync(x_out, L->outbuf.p, nf * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(L->h_out.data() + skip, static_cast<char*>(L->outbuf.p) + skip, L->out_bytes - skip,
-                             hipMemcpyDeviceToHost, c->stream));
+    // (a resident plan's image of the block is pinned and starts at byte h_pin_base of it, plan_create: never behind `skip`)
+    const size_t base = L->h_pin.p ? L->h_pin_base : 0;
+    char* const img = L->h_pin.p ? L->h_pin.as<char>() : L->h_out.data();
+    HIPCHK(c, hipMemcpyAsync(img + (skip - base), static_cast<char*>(L->outbuf.p) + skip, L->out_bytes - skip, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const char* h = L->h_out.data();
-    if (x_out && !direct_x) std::memcpy(x_out, h, nf * 8);
-    if (fret) std::memcpy(fret, h + nf * 8, nc * 8);
-    if (delta) std::memcpy(delta, h + (nf + nc) * 8, nc * 8);
-    const char* i64 = h + (nf + 2 * nc) * 8;
+    if (x_out && !direct_x) std::memcpy(x_out, img, nf * 8);
+    const char* h = img + (nf * 8 - base);   // the per-component results
+    if (fret) std::memcpy(fret, h, nc * 8);
+    if (delta) std::memcpy(delta, h + nc * 8, nc * 8);
+    const char* i64 = h + 2 * nc * 8;
     if (nfeval) std::memcpy(nfeval, i64, nc * 8);
     if (ngeval) std::memcpy(ngeval, i64 + nc * 8, nc * 8);
     const char* i32 = i64 + 2 * nc * 8;

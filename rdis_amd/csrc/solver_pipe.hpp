@@ -1126,6 +1126,9 @@ __device__ __forceinline__ void pipe_solve(const ProblemView& P, const PlanView&
         L.fret[comp] = S.fret; L.delta[comp] = S.fret - S.finit; L.iters[comp] = S.iter;
         L.status[comp] = S.status; L.nfeval[comp] = S.nfeval; L.ngeval[comp] = S.ngeval;
         if (L.trace_n) L.trace_n[comp] = E.trn;
+        // the plan's objective where this launch is the whole solve (rdis_hip_plan_solve then launches no objective_sum_kernel):
+        // that kernel's sum of one component is 0.0 + fret, in lane 0 and again with every zero of the other lanes
+        if (A.objective) *A.objective = 0.0 + S.fret;
     }
 #ifdef RDIS_COOP_TIMING
     if (wg == 0 && (tid & 63) == 0 && tid < 192 && A.timing) {
