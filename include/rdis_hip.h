@@ -575,7 +575,19 @@ int rdis_hip_plan_objective_device(rdis_hip_plan *plan, void **dev_ptr);
  *                             rdis_hip_lm_plan_solve the solve's rows, after a multi-start solve the winners' -- in a fixed
  *                             order (one workgroup: a lane's stride in component order, a butterfly over the wave, the waves
  *                             in wave order); a device pointer to one double, valid until the plan's next solve.
- *                             RDIS_HIP_EINVAL before any solve and after a population solve */
+ *                             RDIS_HIP_EINVAL before any solve and after a population solve
+ *   rdis_hip_lm_plan_summary_device   enqueues one kernel (one workgroup) over the same rows and returns a device pointer to
+ *                             RDIS_HIP_LM_SUMMARY_DOUBLES doubles, valid until the plan's next summary: what a caller that
+ *                             alternates plans needs of a step without fetching every component's arrays --
+ *                               [0] sum of fret   [1] sum of delta   [2] sum of iterations   [3] sum of residual evaluations
+ *                               [4] sum of Jacobian evaluations   [5] sum of linear solves
+ *                               [6..12] the number of components that ended with stop code 1..7
+ *                               [13] the number of components whose fret is not finite   [14], [15] zero.
+ *                             Every field is added in rdis_hip_lm_plan_objective_device's order, so [0] is that entry's double
+ *                             bit for bit and the counts are exact.  Nothing a fetch returns is written.  No wait.
+ *                             RDIS_HIP_EINVAL before any solve and after a population solve
+ *   rdis_hip_lm_plan_summary  the same, then waits and copies the 128 bytes to out16 (through a pinned host image) */
+#define RDIS_HIP_LM_SUMMARY_DOUBLES 16
 typedef struct rdis_hip_lm_plan rdis_hip_lm_plan;
 int rdis_hip_lm_plan_create(rdis_hip_problem *p, int64_t ncomp, const int64_t *free_ptr, const int64_t *free_vid,
                             const int64_t *fac_ptr, const int64_t *fac_id, int32_t residual_model, int64_t hist_cap,
@@ -595,6 +607,8 @@ int rdis_hip_lm_plan_solve_starts_population(rdis_hip_lm_plan *plan, rdis_hip_po
 int rdis_hip_lm_plan_fetch_starts(rdis_hip_lm_plan *plan, double *x_out, double *fret, double *delta, double *info8,
                                   double *hist4, int64_t *nhist, int32_t *best);
 int rdis_hip_lm_plan_objective_device(rdis_hip_lm_plan *plan, void **dev_ptr);
+int rdis_hip_lm_plan_summary_device(rdis_hip_lm_plan *plan, void **dev_ptr);
+int rdis_hip_lm_plan_summary(rdis_hip_lm_plan *plan, double *out16);
 int rdis_hip_lm_plan_set_option(rdis_hip_lm_plan *plan, const char *name, int64_t value);
 int rdis_hip_lm_plan_get_info(rdis_hip_lm_plan *plan, const char *name, int64_t *value);
 

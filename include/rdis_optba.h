@@ -18,7 +18,17 @@
  *              971-1147, 1507-1577).
  * options   nopts (name, value) pairs: SSmaxit, SSftol (src/SubspaceOptimizer.cpp:26-32), AVblkpct, steptol,
  *              maxSweeps, sepPiecePct, nRRperLvl, nRRatTop, minRR, maxNAtoRR, noAssignLimitAtTop, restartSeed,
- *              maxCalls (rdis_levels.h); anything else is an error.
+ *              maxCalls, batch, lmStepDetail (rdis_levels.h; lmStepDetail is read with useCGD 0 only, default 1); and optBA's switch between its two subspace optimisers
+ *              (optBA.cpp:155-158):
+ *                useCGD              1 (default): rdis::HipCGDSubspaceOptimizer, exactly the run this entry made before the
+ *                                    switch existed; 0: rdis::HipLMSubspaceOptimizer -- every node valued by
+ *                                    Levenberg-Marquardt (resident rdis_hip_lm_plans with the wide class; a component of
+ *                                    more than 64 cameras by a call of its own).  One device
+ *                LMmodel             1 (default): the reference's residual sqrt(2 E_j) per factor; 2: the two pixel residuals
+ *                LMsingleMinFactors  0: off; t > 0: a component with at least t factors is solved by a call of its own
+ *                                    instead of inside a plan (default 1024, a measured crossover: DESIGN.md 3.17)
+ *              (the last two are read with useCGD 0 only).  A value that is not one of these whole numbers: -3.
+ *              Anything else is an error.
  * out       RDIS_OPTBA_NOUT doubles:
  *              [0] final objective            [1] objective at the file's values
  *              [2] subspace-optimizer calls   [3] their CG iterations (Frprmn outer iterations), summed
@@ -27,6 +37,8 @@
  *              [6] seconds for the decomposition (separators + device labelling)
  *              [7] nodes of the decomposition tree   [8] objective evaluations of the calls, summed (schedule 1)
  *              [9] sweeps (schedule 0) / trace records (schedule 1)
+ *              With useCGD 0: [3] is the sum of Levenberg-Marquardt iterations and [8] the sum of residual evaluations
+ *              (both schedules).
  * x_out     may be NULL; else the final values of all variables (9 ncams + 3 npts doubles).
  * Returns 0, -1 (file cannot be loaded), -2 (an exception: message on stderr), -3 (bad arguments).
  */

@@ -39,6 +39,7 @@ STATUS_ROLLED_BACK = 0x100
 # LM_WIDE_MAX_CAMERAS active camera blocks
 LM_WIDE = 0x100
 LM_WIDE_MAX_CAMERAS = 64
+LM_SUMMARY_DOUBLES = 16      # RDIS_HIP_LM_SUMMARY_DOUBLES: what LmPlan.summary() returns
 
 _ERRORS = {-1: "EINVAL", -2: "ENOMEM", -3: "EDEVICE", -4: "EOVERLAP", -5: "ERANGE"}
 
@@ -133,6 +134,8 @@ SYMBOLS = {
     "rdis_hip_lm_plan_solve_starts_population": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int32, C.c_double]),
     "rdis_hip_lm_plan_fetch_starts": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rdis_hip_lm_plan_objective_device": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "rdis_hip_lm_plan_summary_device": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "rdis_hip_lm_plan_summary": (C.c_int, [_vp, _vp]),
     "rdis_hip_lm_plan_set_option": (C.c_int, [_vp, C.c_char_p, _i64]),
     "rdis_hip_lm_plan_get_info": (C.c_int, [_vp, C.c_char_p, C.POINTER(_i64)]),
     "rdis_hip_components": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
@@ -728,6 +731,19 @@ class LmPlan:
         """the sum of fret over the plan's ordinary outputs (after solve(): its rows; after a multi-start solve: the winners'),
         summed on the device in a fixed order; waits"""
         return float(np.frombuffer(self.ctx.copy_to_host(self.objective_device_ptr(), 8), dtype=np.float64)[0])
+
+    def summary(self) -> np.ndarray:
+        """16 doubles over the plan's ordinary outputs, summed on the device in objective()'s order: [0] sum of fret (== objective()),
+        [1] of delta, [2] of iterations, [3] of residual and [4] of Jacobian evaluations, [5] of linear solves, [6..12] components
+        per stop code 1..7, [13] components whose fret is not finite, [14], [15] zero; waits"""
+        out = np.zeros(LM_SUMMARY_DOUBLES)
+        self.ctx.check(self.ctx.lib.rdis_hip_lm_plan_summary(self.h, _ptr(out)))
+        return out
+
+    def summary_device_ptr(self) -> int:
+        p = _vp()
+        self.ctx.check(self.ctx.lib.rdis_hip_lm_plan_summary_device(self.h, C.byref(p)))
+        return p.value
 
     def set_option(self, name: str, value: int):
         """workspace_bytes (default 2^30): bounds the workspace replicas of one population launch"""

@@ -1,6 +1,6 @@
 // lm_starts.hip -- the kernels a Levenberg-Marquardt plan's multi-start solve runs around lm_batch.hip's (lm_starts.hpp): the
 // scratch rows of x the starts of a launch are solved in, the selection of every component's best start, the gather of the
-// winners' x into the problem's, and the sum of the plan's objective.  Plain vector stores only; no atomics.
+// winners' x into the problem's, the sum of the plan's objective and the 16 doubles of a step's summary.  Plain vector stores only; no atomics.
 #include <hip/hip_runtime.h>
 
 #include "lm_starts.hpp"
@@ -70,6 +70,43 @@ k_lm_plan_objective(long long ncomp, const double* __restrict__ res, long long s
     }
 }
 
+// The plan's ordinary outputs in 16 doubles (lm_starts.hpp: LmPlanSummary): every field added in k_lm_plan_objective's order -- a
+// lane's stride over the components in component order, a butterfly over the wave, the waves in wave order -- so field 0 is bit for
+// bit that kernel's sum and the counts (whole numbers far below 2^53) are exact.  Lane 0 stores the block; nothing else is written.
+__global__ void __launch_bounds__(256)
+k_lm_plan_summary(long long ncomp, const double* __restrict__ res, long long stride, double* __restrict__ out) {
+    __shared__ double red[4][LM_SUMMARY_FIELDS];
+    double acc[LM_SUMMARY_FIELDS];
+    for (int k = 0; k < LM_SUMMARY_FIELDS; ++k) acc[k] = 0.0;
+    for (long long c = threadIdx.x; c < ncomp; c += 256) {
+        const double* __restrict__ r = res + c * stride;
+        const double fret = r[LM_ROW_FRET];
+        acc[LM_SUMMARY_FRET] += fret;
+        acc[LM_SUMMARY_DELTA] += fret - r[LM_ROW_F0];   // (delta as a fetch forms it)
+        acc[LM_SUMMARY_ITERS] += r[LM_ROW_INFO + 0];
+        acc[LM_SUMMARY_NFEV] += r[LM_ROW_INFO + 2];
+        acc[LM_SUMMARY_NJEV] += r[LM_ROW_INFO + 3];
+        acc[LM_SUMMARY_NSOLVE] += r[LM_ROW_INFO + 4];
+        const int stop = (int)r[LM_ROW_INFO + 1];
+        for (int k = 1; k <= 7; ++k) acc[LM_SUMMARY_STOP1 + k - 1] += stop == k ? 1.0 : 0.0;
+        acc[LM_SUMMARY_NONFINITE] += (fret - fret == 0.0) ? 0.0 : 1.0;
+    }
+    for (int k = 0; k < LM_SUMMARY_FIELDS; ++k) {
+        double a = acc[k];
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = a;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 0; k < LM_SUMMARY_FIELDS; ++k) {
+            double s = 0.0;
+            for (int w = 0; w < 4; ++w) s += red[w][k];
+            out[k] = s;
+        }
+        for (int k = LM_SUMMARY_FIELDS; k < LM_SUMMARY_DOUBLES; ++k) out[k] = 0.0;
+    }
+}
+
 // blocks of 256 lanes over `work` items, at most `cap` (the kernels stride beyond)
 unsigned blocks_for(long long work, long long cap) {
     const long long b = (work + 255) / 256;
@@ -101,6 +138,11 @@ hipError_t lm_starts_gather_launch(hipStream_t stream, const LmStartsOut& O, lon
 
 hipError_t lm_plan_objective_launch(hipStream_t stream, long long ncomp, const double* res, long long stride, double* out) {
     k_lm_plan_objective<<<1, 256, 0, stream>>>(ncomp, res, stride, out);
+    return hipGetLastError();
+}
+
+hipError_t lm_plan_summary_launch(hipStream_t stream, long long ncomp, const double* res, long long stride, double* out) {
+    k_lm_plan_summary<<<1, 256, 0, stream>>>(ncomp, res, stride, out);
     return hipGetLastError();
 }
 

@@ -42,6 +42,14 @@ RDIS_SELECT_FN long long lm_starts_best(long long nstarts, const double* f, long
     return b;
 }
 
+// A step's summary (rdis_hip_lm_plan_summary): 16 doubles over the plan's ordinary outputs.  Where a result row keeps what is
+// summed (lm_batch.hip writes the row: fret, the value at the start, then info8) and where each sum stands in the block; the
+// counts of stop codes 1..7 follow LM_SUMMARY_STOP1, the last two doubles are zero.
+constexpr int LM_ROW_FRET = 0, LM_ROW_F0 = 1, LM_ROW_INFO = 2;
+constexpr int LM_SUMMARY_DOUBLES = 16;   // RDIS_HIP_LM_SUMMARY_DOUBLES (rdis_hip.hip asserts both equal)
+constexpr int LM_SUMMARY_FRET = 0, LM_SUMMARY_DELTA = 1, LM_SUMMARY_ITERS = 2, LM_SUMMARY_NFEV = 3, LM_SUMMARY_NJEV = 4, LM_SUMMARY_NSOLVE = 5,
+              LM_SUMMARY_STOP1 = 6, LM_SUMMARY_NONFINITE = 13, LM_SUMMARY_FIELDS = 14;
+
 #if defined(__HIPCC__)
 // What the launches below share: the plan's outputs for R = nstarts + 1 rows (replica_layout.hpp: lm_starts_layout; strides in
 // doubles) and its tables.
@@ -64,6 +72,9 @@ hipError_t lm_starts_gather_launch(hipStream_t stream, const LmStartsOut& O, lon
 // out[0] = the sum of res[c * stride], c < ncomp, in a fixed order: one workgroup of 256, a lane's stride in component order, a
 // butterfly over the wave, then the waves in wave order
 hipError_t lm_plan_objective_launch(hipStream_t stream, long long ncomp, const double* res, long long stride, double* out);
+// out[0 .. LM_SUMMARY_DOUBLES): the fields above over the rows res + c * stride, c < ncomp, every field in that same order; one
+// workgroup of 256, lane 0 stores the block with plain stores
+hipError_t lm_plan_summary_launch(hipStream_t stream, long long ncomp, const double* res, long long stride, double* out);
 #endif
 
 }  // namespace rdis_hip

@@ -2982,6 +2982,11 @@ struct rdis_hip_lm_plan {
     std::vector<int64_t> h_free_ptr, h_free_vid;
     std::vector<int32_t> h_starts_tables;
     DevBuf starts_tables, starts_in, starts_stage, objective;
+    // rdis_hip_lm_plan_summary: the 16 doubles on the device and their host image -- pinned, or the pageable block where no pinned
+    // memory is to be had; both appear at the first summary
+    DevBuf summary, summary_pin;
+    double summary_host[RDIS_HIP_LM_SUMMARY_DOUBLES] = {};
+    bool summary_pin_tried = false;
     hipEvent_t starts_stage_ev = nullptr;
     bool starts_stage_busy = false;
     ~rdis_hip_lm_plan() { if (starts_stage_ev) (void)hipEventDestroy(starts_stage_ev); }
@@ -3281,6 +3286,42 @@ extern "C" int rdis_hip_lm_plan_objective_device(rdis_hip_lm_plan* L, void** dev
     return 0;
 }
 
+static_assert(RDIS_HIP_LM_SUMMARY_DOUBLES == LM_SUMMARY_DOUBLES, "the summary block of rdis_hip.h and lm_starts.hpp");
+
+extern "C" int rdis_hip_lm_plan_summary_device(rdis_hip_lm_plan* L, void** dev_ptr) {
+    if (!L || !dev_ptr) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = L->prob->ctx;
+    if (L->last_kind != 1 && L->last_kind != 3)
+        return fail(c, RDIS_HIP_EINVAL, L->last_kind == 0 ? "lm_plan_summary: nothing was solved yet"
+                                                          : "lm_plan_summary: the last solve was a population solve (its members have no common summary)");
+    USE_DEVICE(c);
+    if (!L->summary.p) { const int rc = dalloc(c, L->summary, sizeof(double) * LM_SUMMARY_DOUBLES); if (rc) return rc; }
+    // the ordinary outputs' result rows, a component's stride as lm_plan_layout lays a row of them out
+    const long long stride = L->ncomp > 0 ? L->layout.out.doubles(LM_PLAN_RES) / L->ncomp : 0;
+    HIPCHK(c, lm_plan_summary_launch(c->stream, L->ncomp, L->ncomp > 0 ? L->res_dev(L->last_rows, L->last_rows - 1) : nullptr, stride, L->summary.as<double>()));
+    *dev_ptr = L->summary.p;
+    return 0;
+}
+
+extern "C" int rdis_hip_lm_plan_summary(rdis_hip_lm_plan* L, double* out16) {
+    if (!L || !out16) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = L->prob->ctx;
+    void* dev = nullptr;
+    const int rc = rdis_hip_lm_plan_summary_device(L, &dev);
+    if (rc) return rc;
+    USE_DEVICE(c);
+    if (!L->summary_pin_tried) {
+        L->summary_pin_tried = true;
+        const std::string err = c->err;
+        if (halloc(c, L->summary_pin, sizeof(L->summary_host)) != 0) { (void)hipGetLastError(); c->err = err; }   // no pinned memory: the pageable block, and no error
+    }
+    double* const img = L->summary_pin.p ? L->summary_pin.as<double>() : L->summary_host;
+    HIPCHK(c, hipMemcpyAsync(img, dev, sizeof(L->summary_host), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(out16, img, sizeof(L->summary_host));
+    return 0;
+}
+
 extern "C" int rdis_hip_lm_plan_set_option(rdis_hip_lm_plan* L, const char* name, int64_t value) {
     if (!L || !name) return RDIS_HIP_EINVAL;
     rdis_hip_ctx* c = L->prob->ctx;
@@ -3296,7 +3337,7 @@ extern "C" int rdis_hip_lm_plan_get_info(rdis_hip_lm_plan* L, const char* name, 
     const std::string n(name);
     if (n == "members_per_launch") *value = L->last_per_launch;
     else if (n == "launches") *value = L->last_launches;
-    else if (n == "device_bytes") *value = (int64_t)(L->tables.bytes + L->out.bytes + L->work.bytes + L->starts_tables.bytes + L->starts_in.bytes + L->objective.bytes);
+    else if (n == "device_bytes") *value = (int64_t)(L->tables.bytes + L->out.bytes + L->work.bytes + L->starts_tables.bytes + L->starts_in.bytes + L->objective.bytes + L->summary.bytes);
     else if (n == "workspace_bytes") *value = L->workspace_bytes;
     else if (n == "member_workspace_bytes") *value = L->layout.work.member_bytes();
     else return fail(L->prob->ctx, RDIS_HIP_EINVAL, "lm_plan_get_info: unknown name '" + n + "' (members_per_launch, launches, device_bytes, workspace_bytes, "

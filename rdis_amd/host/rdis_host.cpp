@@ -11,6 +11,7 @@
 #include <sstream>
 
 #include "../../include/rdis_hip.h"
+#include "lm_routing.h"
 
 namespace rdis {
 
@@ -112,6 +113,8 @@ OptimizableFunction::~OptimizableFunction() {
     // optimisers that outlive the function must not be left with plans of a freed device problem
     for (HipCGDSubspaceOptimizer* o : plan_holders_) o->functionGone();
     plan_holders_.clear();
+    for (HipLMSubspaceOptimizer* o : lm_plan_holders_) o->functionGone();
+    lm_plan_holders_.clear();
     for (rdis_hip_comm* m : comms_) rdis_hip_comm_destroy(m);
     comms_.clear();
     if (prob_) rdis_hip_free_problem(prob_);
@@ -845,8 +848,168 @@ Numeric HipCGDSubspaceOptimizer::optimizeBatch(std::vector<Component>& comps, co
     return total;
 }
 
+// ------------------------------------------------------------------ HipLMSubspaceOptimizer
+struct HipLMSubspaceOptimizer::CachedPlan {
+    unsigned long long hash = 0, used = 0;
+    int model = 0;
+    std::vector<int64_t> free_ptr, free_vid, fac_ptr, fac_id;
+    rdis_hip_lm_plan* plan = nullptr;
+};
+
 HipLMSubspaceOptimizer::HipLMSubspaceOptimizer(OptimizableFunction& f_)
-    : SubspaceOptimizer(f_), model_(1), last_iters_(0), last_stop_(0), last_nsolve_(0) {}
+    : SubspaceOptimizer(f_), model_(1), last_iters_(0), last_stop_(0), last_nsolve_(0) {
+    f.lm_plan_holders_.push_back(this);
+}
+
+HipLMSubspaceOptimizer::~HipLMSubspaceOptimizer() {
+    dropPlans();
+    if (function_alive_) {
+        std::vector<HipLMSubspaceOptimizer*>& h = f.lm_plan_holders_;
+        h.erase(std::remove(h.begin(), h.end(), this), h.end());
+    }
+}
+
+void HipLMSubspaceOptimizer::functionGone() {   // called by ~OptimizableFunction while its device problem still exists
+    dropPlans();
+    function_alive_ = false;
+}
+
+void HipLMSubspaceOptimizer::dropPlans() {
+    for (CachedPlan* e : cache_) { if (e->plan) rdis_hip_lm_plan_destroy(e->plan); delete e; }
+    cache_.clear();
+}
+
+void HipLMSubspaceOptimizer::setPlanCache(size_t entries) {
+    cache_cap_ = entries;
+    if (cache_.size() > cache_cap_) dropPlans();
+}
+
+void HipLMSubspaceOptimizer::setResidualModel(int m) {
+    if (m != 1 && m != 2) throw std::invalid_argument("HipLMSubspaceOptimizer: LMmodel must be 1 or 2");
+    model_ = m;
+}
+
+void HipLMSubspaceOptimizer::setParameters(const Options& options) {
+    SubspaceOptimizer::setParameters(options);
+    if (options.count("LMmodel")) {
+        const double m = options.as<double>("LMmodel");
+        if (m != 1.0 && m != 2.0) throw std::invalid_argument("HipLMSubspaceOptimizer: LMmodel must be 1 or 2");
+        model_ = (int)m;
+    }
+    if (options.count("LMsingleMinFactors")) {
+        const double t = options.as<double>("LMsingleMinFactors");
+        if (!(t >= 0.0) || t != std::floor(t) || t > 9.0e15) throw std::invalid_argument("HipLMSubspaceOptimizer: LMsingleMinFactors must be a whole number >= 0");
+        single_min_factors_ = (long long)t;
+    }
+}
+
+int HipLMSubspaceOptimizer::routeOf(const std::vector<int64_t>& free_vid, size_t first, size_t last, size_t nfactors) const {
+    const BundleAdjustmentFunction* ba = dynamic_cast<const BundleAdjustmentFunction*>(&f);
+    if (!ba) throw std::logic_error("HipLMSubspaceOptimizer: bundle adjustment functions only");
+    return lmRoute(lmActiveCameras(free_vid.data() + first, last - first, ba->getNumCameras()), (long long)nfactors, single_min_factors_);
+}
+
+// The plan of these lists under the current model: found in the cache (a hit), or made and kept, the least recently used one
+// going first.  With the cache off the plan is the caller's to destroy (transient).
+HipLMSubspaceOptimizer::CachedPlan* HipLMSubspaceOptimizer::cachedPlan(const std::vector<int64_t>& free_ptr, const std::vector<int64_t>& free_vid,
+                                                                       const std::vector<int64_t>& fac_ptr, const std::vector<int64_t>& fac_id, bool& transient) {
+    unsigned long long h = 1469598103934665603ull + (unsigned long long)model_;   // FNV-1a over the four lists
+    auto mix = [&](const std::vector<int64_t>& v) {
+        for (int64_t x : v) { h ^= (unsigned long long)x; h *= 1099511628211ull; }
+        h ^= 0x9e3779b97f4a7c15ull + v.size(); h *= 1099511628211ull;
+    };
+    mix(free_ptr); mix(free_vid); mix(fac_ptr); mix(fac_id);
+    for (CachedPlan* e : cache_)
+        if (e->hash == h && e->model == model_ && e->free_vid == free_vid && e->fac_id == fac_id && e->free_ptr == free_ptr && e->fac_ptr == fac_ptr) {
+            e->used = ++cache_tick_;
+            ++cache_hits_;
+            transient = false;
+            return e;
+        }
+    ++cache_misses_;
+    while (cache_cap_ > 0 && cache_.size() >= cache_cap_) {
+        size_t lru = 0;
+        for (size_t i = 1; i < cache_.size(); ++i) if (cache_[i]->used < cache_[lru]->used) lru = i;
+        if (cache_[lru]->plan) rdis_hip_lm_plan_destroy(cache_[lru]->plan);
+        delete cache_[lru];
+        cache_.erase(cache_.begin() + (long)lru);
+    }
+    std::unique_ptr<CachedPlan> e(new CachedPlan);
+    e->hash = h; e->used = ++cache_tick_; e->model = model_;
+    e->free_ptr = free_ptr; e->free_vid = free_vid; e->fac_ptr = fac_ptr; e->fac_id = fac_id;
+    check(f.deviceContext(), rdis_hip_lm_plan_create(f.deviceProblem(), (int64_t)free_ptr.size() - 1, free_ptr.data(), free_vid.data(), fac_ptr.data(),
+                                                     fac_id.data(), (int32_t)(model_ | RDIS_HIP_LM_WIDE), 0, &e->plan), "rdis_hip_lm_plan_create");
+    transient = cache_cap_ == 0;
+    if (!transient) cache_.push_back(e.get());
+    return e.release();
+}
+
+Numeric HipLMSubspaceOptimizer::optimizeBatch(std::vector<Component>& comps, const bool printdbg) {
+    if (f.numDevices() > 1)
+        throw std::logic_error("HipLMSubspaceOptimizer::optimizeBatch: one device only -- Levenberg-Marquardt plans are not shared out over several devices");
+    const size_t nc = comps.size();
+    last_batch_singles_ = 0;
+    std::vector<size_t> planned, singles;
+    std::vector<int64_t> free_ptr(1, 0), free_vid, fac_ptr(1, 0), fac_id, ids;
+    for (size_t c = 0; c < nc; ++c) {
+        Component& C = comps[c];
+        if (C.xval.size() != C.vars.size()) throw std::invalid_argument("optimizeBatch: xval.size() != vars.size()");
+        ids.clear();
+        for (const Variable* v : C.vars) ids.push_back(v->getID());
+        if (routeOf(ids, 0, ids.size(), C.factors.size()) == LM_ROUTE_SINGLE) { singles.push_back(c); continue; }
+        planned.push_back(c);
+        free_vid.insert(free_vid.end(), ids.begin(), ids.end());
+        for (const Factor* fa : C.factors) fac_id.push_back(fa->getID());
+        free_ptr.push_back((int64_t)free_vid.size());
+        fac_ptr.push_back((int64_t)fac_id.size());
+    }
+    // every component starts from its xval: assigned on the host side here, on the device with the next deviceProblem()
+    for (size_t c : planned)
+        for (size_t i = 0; i < comps[c].vars.size(); ++i) comps[c].vars[i]->assign(comps[c].xval[i]);
+    if (!planned.empty()) {
+        bool transient = false;
+        CachedPlan* cp = cachedPlan(free_ptr, free_vid, fac_ptr, fac_id, transient);
+        struct Release { CachedPlan* e; bool on; ~Release() { if (on) { rdis_hip_lm_plan_destroy(e->plan); delete e; } } } release{cp, transient};
+        rdis_hip_ctx* ctx = f.deviceContext();
+        (void)f.deviceProblem();   // (pushes the starts and every pending assignment of a constant)
+        const size_t np = planned.size();
+        std::vector<double> x(free_vid.size()), fret(np), delta(np), info(8 * np);
+        check(ctx, rdis_hip_lm_plan_solve(cp->plan, (int32_t)maxiters, ftol), "rdis_hip_lm_plan_solve");
+        check(ctx, rdis_hip_lm_plan_fetch(cp->plan, x.data(), fret.data(), delta.data(), info.data(), nullptr, nullptr), "rdis_hip_lm_plan_fetch");
+        for (size_t k = 0; k < np; ++k) {
+            Component& C = comps[planned[k]];
+            const double* i8 = info.data() + 8 * k;
+            C.fret = fret[k]; C.deltaFval = delta[k]; C.iters = (int)i8[0]; C.status = (int)i8[1];
+            C.nfeval = (long long)i8[2]; C.ngeval = (long long)i8[3];
+            // the variables are left assigned to the final, clamped values (LMSubspaceOptimizer.cpp:104-108); the device holds them
+            for (size_t i = 0; i < C.vars.size(); ++i) {
+                Variable* v = C.vars[i];
+                const double val = x[(size_t)free_ptr[k] + i];
+                C.xval[i] = val;
+                v->assigned_ = true; v->value_ = val;
+                f.onVarAssigned(v->getID(), val);
+            }
+        }
+    }
+    // the components no plan takes (or the option sends away): one call each, which has the whole device
+    for (size_t c : singles) {
+        Component& C = comps[c];
+        Numeric delta = 0;
+        C.fret = optimize(C.vars, C.factors, C.xval, delta, false);
+        C.deltaFval = delta; C.iters = last_iters_; C.status = last_stop_; C.nfeval = last_nfev_; C.ngeval = last_njev_;
+    }
+    last_batch_singles_ = (long long)singles.size();
+    Numeric total = 0;
+    for (size_t c = 0; c < nc; ++c) {
+        const Component& C = comps[c];
+        total += C.fret;
+        if (C.status == 7) std::cerr << "HipLM: invalid values in component " << c << " (stop code 7)" << std::endl;
+        if (printdbg)
+            std::cout << "LM SS opt returned " << C.fret << " (init " << C.fret - C.deltaFval << ", diff " << C.deltaFval << ") after " << C.iters
+                      << " iterations -- termination: " << C.status << std::endl;
+    }
+    return total;
+}
 
 Numeric HipLMSubspaceOptimizer::optimize(const VariablePtrVec& vars, const FactorPtrVec& factors, NumericVec& xval,
                                          Numeric& deltaFval, const bool printdbg) {
@@ -868,6 +1031,7 @@ Numeric HipLMSubspaceOptimizer::optimize(const VariablePtrVec& vars, const Facto
     }
     deltaFval = delta;
     last_iters_ = (int)info[0]; last_stop_ = (int)info[1]; last_nsolve_ = (int)info[4];
+    last_nfev_ = (long long)info[2]; last_njev_ = (long long)info[3];
     if (printdbg)
         std::cout << "LM SS opt returned " << fret << " (init " << fret - delta << ", diff " << delta << ") after "
                   << last_iters_ << " iterations -- termination: " << last_stop_ << ", #linsolves " << last_nsolve_ << std::endl;

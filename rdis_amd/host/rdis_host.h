@@ -18,7 +18,7 @@
 //     eval / computeGradient / getVariables; SURVEY.md section 7, hard part 7).
 //   * setParameters takes rdis::Options (a string->value map) because Boost
 //     program_options is not available here; INTEGRATION.md shows the one-line adapter.
-//   * HipCGDSubspaceOptimizer::optimizeBatch solves sibling components in one launch.
+//   * HipCGDSubspaceOptimizer::optimizeBatch (and HipLMSubspaceOptimizer's) solves sibling components in one launch.
 #ifndef RDIS_HOST_H_
 #define RDIS_HOST_H_
 
@@ -49,6 +49,7 @@ typedef std::vector<std::pair<VariableID, Numeric> > PartialGradient;
 class Factor;
 class OptimizableFunction;
 class HipCGDSubspaceOptimizer;
+class HipLMSubspaceOptimizer;
 
 // SSmaxit / SSftol carrier (stands in for boost::program_options::variables_map)
 class Options {
@@ -261,6 +262,7 @@ private:
     mutable std::vector<char> is_dirty_;
     std::unordered_map<std::string, Variable*> by_name_;
     mutable std::vector<HipCGDSubspaceOptimizer*> plan_holders_;   // optimisers with cached plans of prob_
+    mutable std::vector<HipLMSubspaceOptimizer*> lm_plan_holders_;
 };
 
 class BundleAdjustmentFunction : public OptimizableFunction {
@@ -322,6 +324,17 @@ protected:
     Numeric ftol;
 };
 
+// One component of an optimizeBatch call (both optimisers below): sibling components of one recursion level share no free
+// variable and no factor (src/Component.cpp:508-549).
+struct SubspaceComponent {
+    VariablePtrVec vars;
+    FactorPtrVec factors;
+    NumericVec xval;      // in: start, out: final clamped values
+    Numeric fret, deltaFval;
+    int iters, status;    // CGD: Frprmn iterations, exit status; Levenberg-Marquardt: iterations, levmar's stop code
+    long long nfeval, ngeval;   // objective / gradient evaluations; Levenberg-Marquardt: residual / Jacobian evaluations
+};
+
 // The drop-in for CGDSubspaceOptimizer: same contract, solved on the MI355X.
 class HipCGDSubspaceOptimizer : public SubspaceOptimizer {
 public:
@@ -332,14 +345,7 @@ public:
 
     // sibling components of one recursion level in one launch (they share no free variable
     // and no factor, src/Component.cpp:508-549).  Returns the sum of the components' values.
-    struct Component {
-        VariablePtrVec vars;
-        FactorPtrVec factors;
-        NumericVec xval;      // in: start, out: final clamped values
-        Numeric fret, deltaFval;
-        int iters, status;
-        long long nfeval, ngeval;
-    };
+    using Component = SubspaceComponent;
     Numeric optimizeBatch(std::vector<Component>& comps, const bool printdbg);
     // the batch's objective as the devices' all-reduce left it (rdis_hip_allreduce_objective_all: RCCL over xGMI between the
     // listed GPUs, the host where there is no communicator) -- what a caller that keeps its state on the devices reads; the
@@ -415,16 +421,59 @@ private:
 class HipLMSubspaceOptimizer : public SubspaceOptimizer {
 public:
     explicit HipLMSubspaceOptimizer(OptimizableFunction& f_);
-    virtual ~HipLMSubspaceOptimizer() {}
+    virtual ~HipLMSubspaceOptimizer();
+    // SSmaxit, SSftol; LMmodel (1, the default: the reference's residual sqrt(2 E_j) per factor; 2: the two pixel residuals);
+    // LMsingleMinFactors (0: off; t > 0: a component of optimizeBatch or of a level with at least t listed factors is solved by
+    // a call of its own -- lm_routing.h.  Default 1024, a measured crossover, DESIGN.md 3.17: alone in its launch a component
+    // of 268 factors takes the same time both ways, one of 818 factors and every larger one measured is 2 to 20 times faster
+    // by rdis_hip_lm_optimize, whose launches use the whole device, than as one workgroup of a plan)
+    virtual void setParameters(const Options& options);
     virtual Numeric optimize(const VariablePtrVec& vars, const FactorPtrVec& factors, NumericVec& xinit,
                              Numeric& deltaFval, const bool printdbg);
+
+    // HipCGDSubspaceOptimizer::optimizeBatch's contract with Levenberg-Marquardt: sibling components in one launch per class.
+    // xval holds the start on entry and the clamped result on exit, fret / deltaFval as for CGD, iters the iterations, status
+    // levmar's stop code, nfeval / ngeval the residual / Jacobian evaluations; the variables are left assigned; returns the
+    // sum of fret in component order.  Where a component goes is lm_routing.h's rule: more than
+    // RDIS_HIP_LM_WIDE_MAX_CAMERAS active camera blocks, or LMsingleMinFactors factors and more -- rdis_hip_lm_optimize on its
+    // own, after the others; every other component into one rdis_hip_lm_plan made with RDIS_HIP_LM_WIDE.  Components are
+    // independent: the order of the two groups changes no bit.  One device only: with OptimizableFunction::setDevices of more
+    // than one device the call throws.
+    using Component = SubspaceComponent;
+    Numeric optimizeBatch(std::vector<Component>& comps, const bool printdbg);
+    // the route of a component with these free variables and this many listed factors (LM_ROUTE_PLAN / LM_ROUTE_SINGLE)
+    int routeOf(const std::vector<int64_t>& free_vid, size_t first, size_t last, size_t nfactors) const;
+    long long lastBatchSingles() const { return last_batch_singles_; }   // components of the last optimizeBatch solved on their own
+
+    // Plans are kept keyed by the four lists and the model, least recently used first out (HipCGDSubspaceOptimizer::
+    // setPlanCache): the reference's schedule asks for the same sets again and again.  0 switches the cache off.
+    void setPlanCache(size_t entries);
+    size_t planCacheHits() const { return cache_hits_; }
+    size_t planCacheMisses() const { return cache_misses_; }
+    size_t planCacheEntries() const { return cache_.size(); }
+
     int lastIters() const { return last_iters_; }
     int lastStop() const { return last_stop_; }          // levmar's termination code (info[6])
     int lastLinearSolves() const { return last_nsolve_; }
+    long long lastResidualEvals() const { return last_nfev_; }
+    long long lastJacobianEvals() const { return last_njev_; }
     // 1 (default): the reference's residual sqrt(2 E_j) per factor; 2: the two pixel residuals
-    void setResidualModel(int m) { model_ = m; }
+    void setResidualModel(int m);
+    int residualModel() const { return model_; }
+    long long singleMinFactors() const { return single_min_factors_; }
 private:
+    struct CachedPlan;
+    CachedPlan* cachedPlan(const std::vector<int64_t>& free_ptr, const std::vector<int64_t>& free_vid,
+                           const std::vector<int64_t>& fac_ptr, const std::vector<int64_t>& fac_id, bool& transient);
+    void dropPlans();
+    friend class OptimizableFunction;
+    void functionGone();
     int model_, last_iters_, last_stop_, last_nsolve_;
+    long long last_nfev_ = 0, last_njev_ = 0, single_min_factors_ = 1024, last_batch_singles_ = 0;
+    std::vector<CachedPlan*> cache_;
+    size_t cache_cap_ = 256, cache_hits_ = 0, cache_misses_ = 0;
+    unsigned long long cache_tick_ = 0;
+    bool function_alive_ = true;
 };
 
 // error raised when the HIP library reports a failure (no silent fallback)

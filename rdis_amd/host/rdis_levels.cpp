@@ -10,6 +10,7 @@
 #include <numeric>
 
 #include "../../include/rdis_hip.h"
+#include "lm_routing.h"
 
 namespace rdis {
 
@@ -41,10 +42,22 @@ struct HipRDISLevelOptimizer::LevelPlan {
     rdis_hip_plan* plan = nullptr;
     std::vector<double> x, fret, delta;
     std::vector<int32_t> iters, status;
+    // Levenberg-Marquardt (the second constructor): the components lm_routing.h sends to the resident plan, with the plan's own
+    // lists, and those it sends to a call of their own -- both as indices into the launch's components, ascending
+    rdis_hip_lm_plan* lmplan = nullptr;
+    std::vector<size_t> planned, singles;
+    std::vector<int64_t> p_free_ptr, p_free_vid, p_fac_ptr, p_fac_id;
+    std::vector<double> p_x, p_fret, p_delta, p_info;   // lmStepDetail's staging
 };
 
 HipRDISLevelOptimizer::HipRDISLevelOptimizer(OptimizableFunction& f, HipCGDSubspaceOptimizer& ssopt)
-    : f_(f), ss_(ssopt), blkpct_(0.2), steptol_(1.0e-4), seppct_(0.0), maxSweeps_(20), batch_(true),
+    : f_(f), cgd_(&ssopt), lm_(nullptr), ss_(ssopt), blkpct_(0.2), steptol_(1.0e-4), seppct_(0.0), maxSweeps_(20), batch_(true),
+      ssmaxit_(ssopt.getMaxIters()), ssftol_(ssopt.getFtol()), sweeps_(0), decomp_ms_(0),
+      nrr_per_lvl_(2), nrr_at_top_(2), min_rr_(1), max_na_to_rr_(10), no_assign_limit_at_top_(true), nrr_at_top_set_(false),
+      restart_seed_(0x5D15ull), max_calls_(100000), ref_calls_(0) {}
+
+HipRDISLevelOptimizer::HipRDISLevelOptimizer(OptimizableFunction& f, HipLMSubspaceOptimizer& ssopt)
+    : f_(f), cgd_(nullptr), lm_(&ssopt), ss_(ssopt), blkpct_(0.2), steptol_(1.0e-4), seppct_(0.0), maxSweeps_(20), batch_(true),
       ssmaxit_(ssopt.getMaxIters()), ssftol_(ssopt.getFtol()), sweeps_(0), decomp_ms_(0),
       nrr_per_lvl_(2), nrr_at_top_(2), min_rr_(1), max_na_to_rr_(10), no_assign_limit_at_top_(true), nrr_at_top_set_(false),
       restart_seed_(0x5D15ull), max_calls_(100000), ref_calls_(0) {}
@@ -54,6 +67,7 @@ HipRDISLevelOptimizer::~HipRDISLevelOptimizer() { releasePlans(); }
 void HipRDISLevelOptimizer::releasePlans() {
     for (LevelPlan* lp : plans_) {
         if (lp->plan) rdis_hip_plan_destroy(lp->plan);
+        if (lp->lmplan) rdis_hip_lm_plan_destroy(lp->lmplan);
         delete lp;
     }
     plans_.clear();
@@ -65,6 +79,7 @@ void HipRDISLevelOptimizer::setParameters(const Options& o) {
     if (o.count("maxSweeps")) maxSweeps_ = o.as<int>("maxSweeps");
     if (o.count("batch")) batch_ = o.as<int>("batch") != 0;
     if (o.count("sepPiecePct")) seppct_ = o.as<double>("sepPiecePct");
+    if (o.count("lmStepDetail")) lm_step_detail_ = o.as<int>("lmStepDetail") != 0;
     if (o.count("nRRperLvl")) nrr_per_lvl_ = (unsigned)o.as<int>("nRRperLvl");          // RDISOptimizer.cpp:97, 1781-1782
     if (o.count("nRRatTop")) { nrr_at_top_ = (unsigned)o.as<int>("nRRatTop"); nrr_at_top_set_ = true; }   // :99, 1784-1785
     if (!nrr_at_top_set_) nrr_at_top_ = nrr_per_lvl_;
@@ -258,14 +273,96 @@ void HipRDISLevelOptimizer::buildPlans() {
             const size_t ncomp = lp->node.size();
             lp->x.resize(lp->free_vid.size()); lp->fret.resize(ncomp); lp->delta.resize(ncomp);
             lp->iters.resize(ncomp); lp->status.resize(ncomp);
-            if (batch_ && f_.numDevices() == 1)
+            plans_.push_back(lp);   // (owned from here on: a failed creation below leaves it to releasePlans)
+            if (lm_) {
+                // which components the resident plan takes (lm_routing.h); the plan itself only where a sweep will use it
+                lp->p_free_ptr.assign(1, 0); lp->p_fac_ptr.assign(1, 0);
+                for (size_t c = 0; c < ncomp; ++c) {
+                    const size_t v0 = (size_t)lp->free_ptr[c], v1 = (size_t)lp->free_ptr[c + 1], f0 = (size_t)lp->fac_ptr[c], f1 = (size_t)lp->fac_ptr[c + 1];
+                    if (lm_->routeOf(lp->free_vid, v0, v1, f1 - f0) == LM_ROUTE_SINGLE) { lp->singles.push_back(c); continue; }
+                    lp->planned.push_back(c);
+                    lp->p_free_vid.insert(lp->p_free_vid.end(), lp->free_vid.begin() + (long)v0, lp->free_vid.begin() + (long)v1);
+                    lp->p_fac_id.insert(lp->p_fac_id.end(), lp->fac_id.begin() + (long)f0, lp->fac_id.begin() + (long)f1);
+                    lp->p_free_ptr.push_back((int64_t)lp->p_free_vid.size());
+                    lp->p_fac_ptr.push_back((int64_t)lp->p_fac_id.size());
+                }
+                if (batch_ && f_.numDevices() == 1 && !lp->planned.empty())
+                    check(f_.deviceContext(), rdis_hip_lm_plan_create(p, (int64_t)lp->planned.size(), lp->p_free_ptr.data(), lp->p_free_vid.data(),
+                                                                      lp->p_fac_ptr.data(), lp->p_fac_id.data(),
+                                                                      (int32_t)(lm_->residualModel() | RDIS_HIP_LM_WIDE), 0, &lp->lmplan), "rdis_hip_lm_plan_create");
+            } else if (batch_ && f_.numDevices() == 1)
                 check(f_.deviceContext(), rdis_hip_plan_create(p, (int64_t)ncomp, lp->free_ptr.data(), lp->free_vid.data(),
                                                                lp->fac_ptr.data(), lp->fac_id.data(), &lp->plan), "rdis_hip_plan_create");
-            plans_.push_back(lp);
         }
 }
 
+// A Levenberg-Marquardt step: the resident plan's solve from the device's assigned x, the single calls in list order, the
+// plan's summary.  Nothing but the summary's 128 bytes and the singles' scalars comes back (lmStepDetail: everything).
+double HipRDISLevelOptimizer::runLmPlan(LevelPlan& lp, int sweep, double objective, bool printInfo) {
+    const double t0 = now_ms();
+    const size_t ncomp = lp.node.size();
+    rdis_hip_problem* p = f_.deviceProblem();   // (pushes pending host-side assignments)
+    rdis_hip_ctx* ctx = f_.deviceContext();
+    double sum[RDIS_HIP_LM_SUMMARY_DOUBLES] = {0};
+    if (lp.lmplan) check(ctx, rdis_hip_lm_plan_solve(lp.lmplan, (int32_t)ssmaxit_, ssftol_), "rdis_hip_lm_plan_solve");
+    std::vector<double> s_delta(lp.singles.size()), s_info(8 * lp.singles.size());
+    for (size_t k = 0; k < lp.singles.size(); ++k) {
+        const size_t c = lp.singles[k];
+        check(ctx, rdis_hip_lm_optimize(p, lp.free_ptr[c + 1] - lp.free_ptr[c], lp.free_vid.data() + lp.free_ptr[c], lp.fac_ptr[c + 1] - lp.fac_ptr[c],
+                                        lp.fac_id.data() + lp.fac_ptr[c], nullptr, (int32_t)ssmaxit_, ssftol_, (int32_t)lm_->residualModel(), &lp.fret[c],
+                                        &s_delta[k], s_info.data() + 8 * k, nullptr, 0, nullptr), "rdis_hip_lm_optimize");
+        lp.delta[c] = s_delta[k]; lp.iters[c] = (int32_t)s_info[8 * k]; lp.status[c] = (int32_t)s_info[8 * k + 1];
+    }
+    if (lp.lmplan) check(ctx, rdis_hip_lm_plan_summary(lp.lmplan, sum), "rdis_hip_lm_plan_summary");
+    double dsum = sum[1];
+    long long iters = (long long)sum[2], fevals = (long long)sum[3], invalid = (long long)sum[12], nonfinite = (long long)sum[13];
+    for (size_t k = 0; k < lp.singles.size(); ++k) {
+        dsum += s_delta[k];
+        iters += (long long)s_info[8 * k]; fevals += (long long)s_info[8 * k + 2];
+        if ((int)s_info[8 * k + 1] == 7) ++invalid;
+        const double fr = lp.fret[lp.singles[k]];
+        if (!(fr - fr == 0.0)) ++nonfinite;
+    }
+    if (lm_step_detail_) {
+        // everything a fetch returns, per component, and the host mirror of the step's variables
+        if (lp.lmplan) {
+            const size_t np = lp.planned.size();
+            lp.p_x.resize(lp.p_free_vid.size()); lp.p_fret.resize(np); lp.p_delta.resize(np); lp.p_info.resize(8 * np);
+            check(ctx, rdis_hip_lm_plan_fetch(lp.lmplan, lp.p_x.data(), lp.p_fret.data(), lp.p_delta.data(), lp.p_info.data(), nullptr, nullptr),
+                  "rdis_hip_lm_plan_fetch");
+            for (size_t k = 0; k < np; ++k) {
+                const size_t c = lp.planned[k];
+                lp.fret[c] = lp.p_fret[k]; lp.delta[c] = lp.p_delta[k]; lp.iters[c] = (int32_t)lp.p_info[8 * k]; lp.status[c] = (int32_t)lp.p_info[8 * k + 1];
+                std::copy(lp.p_x.begin() + (long)lp.p_free_ptr[k], lp.p_x.begin() + (long)lp.p_free_ptr[k + 1], lp.x.begin() + (long)lp.free_ptr[c]);
+            }
+        }
+        for (size_t c : lp.singles)
+            check(ctx, rdis_hip_get_x(p, lp.free_ptr[c + 1] - lp.free_ptr[c], lp.free_vid.data() + lp.free_ptr[c], lp.x.data() + lp.free_ptr[c]), "rdis_hip_get_x");
+        f_.adoptDeviceValues(lp.free_vid, lp.x);
+    }
+    objective += dsum;
+    Step s;
+    s.sweep = sweep; s.depth = lp.depth; s.kind = lp.kind; s.ncomp = (long long)ncomp;
+    s.nvars = (long long)lp.free_vid.size(); s.nfactors = (long long)lp.fac_id.size(); s.iters = iters;
+    s.objective = objective; s.ms = now_ms() - t0;
+    s.singles = (long long)lp.singles.size(); s.fevals = fevals; s.invalid = invalid; s.nonfinite = nonfinite;
+    trace_.push_back(s);
+    if (printInfo) {
+        std::cout << "sweep " << sweep << " depth " << lp.depth << (lp.kind == 0 ? " separators: " : " leaves: ") << ncomp << " component(s), "
+                  << lp.singles.size() << " by a call of their own, " << lp.free_vid.size() << " variables, " << lp.fac_id.size() << " factors, "
+                  << iters << " LM iterations -> " << objective << " (" << s.ms << " ms)";
+        if (invalid || nonfinite) std::cout << "; " << invalid << " ended with invalid values (code 7), " << nonfinite << " with a value that is not finite";
+        std::cout << std::endl;
+    }
+    return objective;
+}
+
 double HipRDISLevelOptimizer::runPlan(LevelPlan& lp, int sweep, double objective, bool printInfo) {
+    if (lm_ && batch_) {
+        if (f_.numDevices() > 1)
+            throw std::logic_error("HipRDISLevelOptimizer: Levenberg-Marquardt levels run on one device only (plans are not shared out over several devices)");
+        return runLmPlan(lp, sweep, objective, printInfo);
+    }
     const double t0 = now_ms();
     const VariablePtrVec& vars = f_.getVariables();
     const FactorPtrVec& facs = f_.getFactors();
@@ -285,7 +382,7 @@ double HipRDISLevelOptimizer::runPlan(LevelPlan& lp, int sweep, double objective
             }
             for (int64_t j = lp.fac_ptr[c]; j < lp.fac_ptr[c + 1]; ++j) C.factors.push_back(facs[(size_t)lp.fac_id[(size_t)j]]);
         }
-        ss_.optimizeBatch(comps, false);
+        cgd_->optimizeBatch(comps, false);
         for (size_t c = 0; c < ncomp; ++c) {
             const HipCGDSubspaceOptimizer::Component& C = comps[c];
             lp.fret[c] = C.fret; lp.delta[c] = C.deltaFval; lp.iters[c] = C.iters; lp.status[c] = C.status;
@@ -323,10 +420,12 @@ double HipRDISLevelOptimizer::runPlan(LevelPlan& lp, int sweep, double objective
             for (int64_t j = lp.fac_ptr[c]; j < lp.fac_ptr[c + 1]; ++j) cf.push_back(facs[(size_t)lp.fac_id[(size_t)j]]);
             Numeric delta = 0;
             lp.fret[c] = ss_.optimize(cv, cf, xv, delta, false);
-            lp.delta[c] = delta; lp.iters[c] = ss_.lastIters(); lp.status[c] = ss_.lastStatus();
+            // (CGD: Frprmn's outer iterations, one more than its counter; Levenberg-Marquardt: the iterations, the stop code)
+            const int it = cgd_ ? cgd_->lastIters() + 1 : lm_->lastIters();
+            lp.delta[c] = delta; lp.iters[c] = cgd_ ? cgd_->lastIters() : it; lp.status[c] = cgd_ ? cgd_->lastStatus() : lm_->lastStop();
             for (size_t i = 0; i < xv.size(); ++i) lp.x[(size_t)lp.free_ptr[c] + i] = xv[i];
             dsum += delta;
-            iters += ss_.lastIters() + 1;
+            iters += it;
         }
     }
     objective += dsum;
@@ -357,6 +456,8 @@ Numeric HipRDISLevelOptimizer::optimize(bool printInfo) {
     for (const Variable* v : f_.getVariables())
         if (!v->isAssigned()) throw std::logic_error("HipRDISLevelOptimizer::optimize: assign an initial state first");
     ssmaxit_ = ss_.getMaxIters(); ssftol_ = ss_.getFtol();
+    if (lm_ && f_.numDevices() > 1)
+        throw std::logic_error("HipRDISLevelOptimizer: Levenberg-Marquardt levels run on one device only (plans are not shared out over several devices)");
     buildTree();
     buildPlans();
     trace_.clear();
@@ -373,6 +474,15 @@ Numeric HipRDISLevelOptimizer::optimize(bool printInfo) {
         for (LevelPlan* lp : plans_) objective = runPlan(*lp, sweep, objective, printInfo);
         ++sweeps_;
         if (!(before - objective > steptol_)) break;   // no progress beyond steptol (RDISOptimizer.cpp:1089-1108)
+    }
+    if (lm_ && batch_ && !lm_step_detail_ && sweeps_ > 0) {
+        // the steps left their results on the device only: the host mirror of all values, once
+        std::vector<int64_t> all(f_.getVariables().size());
+        std::iota(all.begin(), all.end(), (int64_t)0);
+        std::vector<double> xs(all.size());
+        (void)f_.deviceProblem();
+        check(f_.deviceContext(), rdis_hip_get_x(f_.deviceProblem(), (int64_t)all.size(), all.data(), xs.data()), "rdis_hip_get_x");
+        f_.adoptDeviceValues(all, xs);
     }
     const double check_f = f_.eval();   // the running sum of the launches' deltas IS the function value
     if (printInfo) std::cout << "level driver: final value " << check_f << " (sum of deltas: " << objective << ") after " << sweeps_ << " sweep(s)" << std::endl;
@@ -458,11 +568,13 @@ void HipRDISLevelOptimizer::runSet(const std::vector<int>& set, const std::vecto
                 for (FactorID fa : valuedFactors(n)) comps[i].factors.push_back(facs[(size_t)fa]);
                 comps[i].xval = start[(size_t)n];
             }
-            ss_.optimizeBatch(comps, false);
+            if (cgd_) cgd_->optimizeBatch(comps, false); else lm_->optimizeBatch(comps, false);
             ref_calls_ += (long long)pending.size();
             ++ref_batches_;
-            for (const HipCGDSubspaceOptimizer::Component& C : comps)
-                if ((C.status & 0xff) != RDIS_HIP_EXIT_EMPTY) { ref_iters_ += C.iters + 1; ref_fevals_ += C.nfeval; }
+            for (const HipCGDSubspaceOptimizer::Component& C : comps) {
+                if (lm_) { ref_iters_ += C.iters; ref_fevals_ += C.nfeval; }   // Levenberg-Marquardt iterations, residual evaluations
+                else if ((C.status & 0xff) != RDIS_HIP_EXIT_EMPTY) { ref_iters_ += C.iters + 1; ref_fevals_ += C.nfeval; }
+            }
             std::vector<int> again;
             const double ftol = steptol_;   // :1083-1084
             for (size_t i = 0; i < pending.size(); ++i) {

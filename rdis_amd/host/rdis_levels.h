@@ -50,9 +50,28 @@ public:
         long long ncomp, nvars, nfactors, iters;
         double objective;                  // of the whole function after the step
         double ms;                         // wall time of the step, host side
+        // Levenberg-Marquardt steps only (0 otherwise): components solved by a call of their own (lm_routing.h), residual
+        // evaluations, components that ended with stop code 7 (invalid values) and components whose value is not finite --
+        // the last two are reported here, not thrown (the entries of include/rdis_hip.h return 0 for them)
+        long long singles = 0, fevals = 0, invalid = 0, nonfinite = 0;
     };
 
     HipRDISLevelOptimizer(OptimizableFunction& f, HipCGDSubspaceOptimizer& ssopt);
+    // optBA's --useCGD false (src/bundleadjust/optBA.cpp:155-158): every node valued by Levenberg-Marquardt.  The same tree,
+    // separators and planLists (the same buildTree).  optimize(): every launch of a sweep is a resident rdis_hip_lm_plan (made
+    // with RDIS_HIP_LM_WIDE) of the components lm_routing.h sends to a plan, plus the list of those it sends to a call of their
+    // own; a step is the plan's solve from the device's assigned x, the single calls in list order, then
+    // rdis_hip_lm_plan_summary -- 128 bytes instead of every component's arrays.  The running objective adds summary [1] and
+    // then the singles' deltas in list order; Step::iters is summary [2] plus theirs (Levenberg-Marquardt iterations, no + 1).
+    // With the level option lmStepDetail = 0 that is all a step brings back, and the host mirror of the values is brought up to
+    // date once, after the last sweep (one rdis_hip_get_x); lmStepDetail = 1 adds a full fetch and mirror after every step (the
+    // per-component arrays are filled) and produces the same bits.  1 is the default: on full ladybug the two were measured
+    // within the spread between rounds of each other, so the summary-only step has not earned its place as
+    // the default.  batch = 0 runs one HipLMSubspaceOptimizer::optimize per component: that is rdis_hip_lm_optimize, a different
+    // kernel family from the plans', so -- unlike CGD -- it is NOT promised to equal the batched run bit for bit.
+    // optimizeReferenceSchedule() calls HipLMSubspaceOptimizer::optimizeBatch; refIterations() then counts Levenberg-Marquardt
+    // iterations and refFEvals() residual evaluations.  One device only (optimize() and optimizeBatch throw otherwise).
+    HipRDISLevelOptimizer(OptimizableFunction& f, HipLMSubspaceOptimizer& ssopt);
     ~HipRDISLevelOptimizer();
     HipRDISLevelOptimizer(const HipRDISLevelOptimizer&) = delete;
     HipRDISLevelOptimizer& operator=(const HipRDISLevelOptimizer&) = delete;
@@ -61,7 +80,7 @@ public:
     // optimizer by the caller), batch (1; 0 = one ssopt.optimize call per component, in the
     // reference's child order: the same results bit for bit, for tests and comparison), sepPiecePct (0: a
     // separator leaves pieces that are leaves; > 0: pieces of up to that fraction of the node, which are
-    // split again -- deeper trees, like the reference's two-way partitions)
+    // split again -- deeper trees, like the reference's two-way partitions), lmStepDetail (1; see the second constructor)
     void setParameters(const Options& options);
 
     // Every variable must be assigned (the initial state, optBA.cpp:189-205).  Returns the final
@@ -145,7 +164,11 @@ private:
     void releasePlans();
     double runPlan(LevelPlan& lp, int sweep, double objective, bool printInfo);
     OptimizableFunction& f_;
-    HipCGDSubspaceOptimizer& ss_;
+    HipCGDSubspaceOptimizer* cgd_;         // exactly one of the two is set
+    HipLMSubspaceOptimizer* lm_;
+    SubspaceOptimizer& ss_;
+    double runLmPlan(LevelPlan& lp, int sweep, double objective, bool printInfo);
+    bool lm_step_detail_ = true;
     double blkpct_, steptol_, seppct_;
     int maxSweeps_;
     bool batch_;

@@ -4,6 +4,7 @@
 #include <chrono>
 #include <cstring>
 #include <iostream>
+#include <memory>
 #include <string>
 
 #include "rdis_levels.h"
@@ -28,18 +29,35 @@ extern "C" int rdis_optba_run_hist(const char* bal_file, int64_t ncams, int64_t 
         f.assignAll(f.getInitialState());                       // "--randinit 0" (optBA.cpp:189-193)
         Options ss, lv;
         static const char* const level_opts[] = {"AVblkpct", "steptol", "maxSweeps", "sepPiecePct", "nRRperLvl", "nRRatTop", "minRR",
-                                                 "maxNAtoRR", "noAssignLimitAtTop", "restartSeed", "maxCalls", "batch"};
+                                                 "maxNAtoRR", "noAssignLimitAtTop", "restartSeed", "maxCalls", "batch", "lmStepDetail"};
+        bool use_cgd = true;
         for (int i = 0; i < nopts; ++i) {
             const std::string n(opt_names[i] ? opt_names[i] : "");
             if (n == "SSmaxit" || n == "SSftol") { ss.set(n, opt_vals[i]); continue; }
+            // optBA's --useCGD (optBA.cpp:155-158) and the Levenberg-Marquardt optimiser's own options: whole numbers only
+            const double ov = opt_vals[i];
+            if (n == "useCGD") { if (ov != 0.0 && ov != 1.0) return -3; use_cgd = ov == 1.0; continue; }
+            if (n == "LMmodel") { if (ov != 1.0 && ov != 2.0) return -3; ss.set(n, ov); continue; }
+            if (n == "LMsingleMinFactors") { if (!(ov >= 0.0) || ov != (double)(long long)ov || ov > 9.0e15) return -3; ss.set(n, ov); continue; }
             bool known = false;
             for (const char* k : level_opts) known = known || n == k;
             if (!known) { std::cerr << "rdis_optba_run: unknown option '" << n << "'" << std::endl; return -3; }
             lv.set(n, opt_vals[i]);
         }
-        HipCGDSubspaceOptimizer ssopt(f);
-        ssopt.setParameters(ss);
-        HipRDISLevelOptimizer rdis(f, ssopt);
+        // (only the optimiser the switch selects is made: the other one's plans, caches and options do not exist)
+        std::unique_ptr<HipCGDSubspaceOptimizer> cgd;
+        std::unique_ptr<HipLMSubspaceOptimizer> lm;
+        std::unique_ptr<HipRDISLevelOptimizer> driver;
+        if (use_cgd) {
+            cgd.reset(new HipCGDSubspaceOptimizer(f));
+            cgd->setParameters(ss);
+            driver.reset(new HipRDISLevelOptimizer(f, *cgd));
+        } else {
+            lm.reset(new HipLMSubspaceOptimizer(f));
+            lm->setParameters(ss);
+            driver.reset(new HipRDISLevelOptimizer(f, *lm));
+        }
+        HipRDISLevelOptimizer& rdis = *driver;
         rdis.setParameters(lv);
         const Numeric before = f.eval();
         for (int i = 0; i < RDIS_OPTBA_NOUT; ++i) out[i] = 0.0;
@@ -70,9 +88,10 @@ extern "C" int rdis_optba_run_hist(const char* bal_file, int64_t ncams, int64_t 
         } else {
             out[0] = rdis.optimize(false);
             const double t1 = now();
-            long long calls = 0, iters = 0;
-            for (const auto& st : rdis.trace()) { calls += st.ncomp; iters += st.iters; }
+            long long calls = 0, iters = 0, fevals = 0;
+            for (const auto& st : rdis.trace()) { calls += st.ncomp; iters += st.iters; fevals += st.fevals; }
             out[2] = (double)calls; out[3] = (double)iters; out[4] = (double)rdis.trace().size();
+            if (!use_cgd) out[8] = (double)fevals;
             out[6] = rdis.decompositionMs() * 1e-3; out[5] = t1 - t0 - out[6];
             out[9] = rdis.sweepsDone();
         }
