@@ -359,7 +359,9 @@ int rdis_hip_plan_fetch_starts(rdis_hip_plan *plan, double *x_out, double *fret,
  *                       "grad_workspace_bytes" (population_eval_grad below; default 2^30; >= 0; lowering it releases scratch).
  *   population_get_info     "eval_members_per_launch" (R of the last evaluation), "eval_launches" (kernels it launched),
  *                       "eval_valid" (1: best / assign_best are served); "grad_members_per_launch", "grad_launches" and
- *                       "grad_branch" of the last gradient call (population_eval_grad below).  Unknown names: RDIS_HIP_EINVAL.
+ *                       "grad_branch" of the last gradient call (population_eval_grad below); "nmembers" and "problem_handle"
+ *                       (the population's rdis_hip_problem* as an integer: what a caller that is handed a population compares
+ *                       with its own problem before it writes a row).  Unknown names: RDIS_HIP_EINVAL.
  *   plan_solve_population   asynchronous on the context's stream.  For every member s and component c exactly what
  *                       plan_set_start(plan, NULL) + plan_solve would do on a problem whose assigned x is X[s] -- the same
  *                       bits in fret, delta, x, iters, status, nfeval, ngeval: the start is X[s][free_vid], clamped at
@@ -440,6 +442,15 @@ int rdis_hip_plan_fetch_starts(rdis_hip_plan *plan, double *x_out, double *fret,
  *                       two buffers swap roles; RDIS_HIP_ENOMEM at that allocation leaves the population as it was.  Rank by
  *                       counting is quadratic in the members: nmembers > 2^18 returns RDIS_HIP_ERANGE before anything is
  *                       launched.
+ *   population_permute  the members put into an order the caller chose: order[nmembers] a permutation of 0 .. nmembers - 1,
+ *                       afterwards X_new[r] = X_old[order[r]] (what a driver does whose members stop at different times: the
+ *                       active ones to the front, so that the solves' contiguous member range covers exactly them).  With a
+ *                       valid last evaluation f_new[r] = f_old[order[r]] and it stays valid, as after population_sort; stale
+ *                       values stay stale.  The kernel, the second buffer, its memory note and RDIS_HIP_ENOMEM are
+ *                       population_sort's.  order is copied before the call returns (staged like every id list: one
+ *                       synchronisation); the permutation itself is enqueued.  order NULL, an entry out of range or a member
+ *                       named twice -- all checked on the host before anything is launched: RDIS_HIP_EINVAL with a message,
+ *                       nothing changed.
  *   plan_solve_population_range   plan_solve_population restricted to members first .. first + count - 1: every (member,
  *                       component) of the range gets the bits a whole-population solve leaves for that member, the rows
  *                       outside the range are untouched.  count >= 1 and the range inside the population, else
@@ -495,6 +506,7 @@ int rdis_hip_population_set_sampling(rdis_hip_population *pop, const double *lo,
 int rdis_hip_population_sample(rdis_hip_population *pop, int64_t first, int64_t count, int64_t n, const int64_t *vid,
                                uint64_t seed, int64_t stream);
 int rdis_hip_population_sort(rdis_hip_population *pop, int64_t *order_out);
+int rdis_hip_population_permute(rdis_hip_population *pop, const int64_t *order);
 int rdis_hip_population_eval_grad(rdis_hip_population *pop, int64_t first, int64_t count, int64_t nf, const int64_t *fac,
                                   double *f, double *g);
 int rdis_hip_population_eval_grad_device(rdis_hip_population *pop, int64_t first, int64_t count, int64_t nf,
@@ -586,7 +598,19 @@ int rdis_hip_plan_objective_device(rdis_hip_plan *plan, void **dev_ptr);
  *                             Every field is added in rdis_hip_lm_plan_objective_device's order, so [0] is that entry's double
  *                             bit for bit and the counts are exact.  Nothing a fetch returns is written.  No wait.
  *                             RDIS_HIP_EINVAL before any solve and after a population solve
- *   rdis_hip_lm_plan_summary  the same, then waits and copies the 128 bytes to out16 (through a pinned host image) */
+ *   rdis_hip_lm_plan_summary  the same, then waits and copies the 128 bytes to out16 (through a pinned host image)
+ *   rdis_hip_lm_plan_summary_population_device   the summary per member of the last rdis_hip_lm_plan_solve_population: enqueues
+ *                             one kernel -- one workgroup per member, the member in the grid's x dimension, one launch for the
+ *                             whole range however "workspace_bytes" split the solve -- and returns a device pointer to
+ *                             [count][RDIS_HIP_LM_SUMMARY_DOUBLES] doubles, valid until the plan's next member summary.  Row i
+ *                             belongs to member first + i of that solve's range and holds the 16 doubles above over that
+ *                             member's result rows, every field added in rdis_hip_lm_plan_objective_device's order: bit for bit
+ *                             what rdis_hip_lm_plan_summary returns after rdis_hip_lm_plan_solve on a problem whose x is that
+ *                             member's.  Nothing a fetch returns is written.  No wait.  Valid after a population solve only:
+ *                             before any solve and after rdis_hip_lm_plan_solve or a multi-start solve RDIS_HIP_EINVAL, nothing
+ *                             changed (rdis_hip_lm_plan_summary and _objective_device keep refusing after a population solve)
+ *   rdis_hip_lm_plan_summary_population   the same, then waits and copies the count x 128 bytes to out (through a pinned host
+ *                             image of that size) */
 #define RDIS_HIP_LM_SUMMARY_DOUBLES 16
 typedef struct rdis_hip_lm_plan rdis_hip_lm_plan;
 int rdis_hip_lm_plan_create(rdis_hip_problem *p, int64_t ncomp, const int64_t *free_ptr, const int64_t *free_vid,
@@ -609,6 +633,8 @@ int rdis_hip_lm_plan_fetch_starts(rdis_hip_lm_plan *plan, double *x_out, double 
 int rdis_hip_lm_plan_objective_device(rdis_hip_lm_plan *plan, void **dev_ptr);
 int rdis_hip_lm_plan_summary_device(rdis_hip_lm_plan *plan, void **dev_ptr);
 int rdis_hip_lm_plan_summary(rdis_hip_lm_plan *plan, double *out16);
+int rdis_hip_lm_plan_summary_population_device(rdis_hip_lm_plan *plan, void **dev_ptr);
+int rdis_hip_lm_plan_summary_population(rdis_hip_lm_plan *plan, double *out /*[count][16]*/);
 int rdis_hip_lm_plan_set_option(rdis_hip_lm_plan *plan, const char *name, int64_t value);
 int rdis_hip_lm_plan_get_info(rdis_hip_lm_plan *plan, const char *name, int64_t *value);
 

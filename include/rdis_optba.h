@@ -11,7 +11,9 @@
  * What is NOT the reference's: the cut (a degree-ordered separator in place of the binary-only PaToH call,
  * src/RDISOptimizer.cpp:779-865) and the random restarts' values (drawn per (node, restart, variable) instead of from
  * one shared generator in visiting order, :1196-1216) -- end-to-end parity with optBA is unpinned; the schedule itself
- * is checked decision by decision by oracle/levels.py (tests/test_host_dropin.py).
+ * is checked decision by decision by oracle/levels.py (tests/test_host_dropin.py).  The same holds for the initial states
+ * rdis_optba_run_samples draws (rdis_optba_samples.h): per (seed, member, variable), not the reference's one shared generator with Boost's
+ * distribution (optBA.cpp:195-205).
  *
  * schedule  0: sweeps over the levels (HipRDISLevelOptimizer::optimize), 1: the reference's per-node schedule with
  *              iterative improvement and random restarts (optimizeReferenceSchedule, src/RDISOptimizer.cpp:253-334,
@@ -65,7 +67,10 @@ int rdis_optba_run_hist(const char *bal_file, int64_t ncams, int64_t npts, int32
                         const char *const *opt_names, const double *opt_vals, int32_t device, double *out, double *x_out,
                         double *hist, int32_t hist_rows);
 
+/* optBA's sample loop as one population run, rdis_optba_run_samples: declared in a header of its own, included here */
+
 #ifdef __cplusplus
 }
 #endif
+#include "rdis_optba_samples.h"
 #endif /* RDIS_OPTBA_H_ */

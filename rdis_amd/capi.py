@@ -99,6 +99,7 @@ SYMBOLS = {
     "rdis_hip_population_set_sampling": (C.c_int, [_vp, _vp, _vp]),
     "rdis_hip_population_sample": (C.c_int, [_vp, _i64, _i64, _i64, _vp, C.c_uint64, _i64]),
     "rdis_hip_population_sort": (C.c_int, [_vp, _vp]),
+    "rdis_hip_population_permute": (C.c_int, [_vp, _vp]),
     "rdis_hip_population_eval_grad": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "rdis_hip_population_eval_grad_device": (C.c_int, [_vp, _i64, _i64, _i64, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "rdis_hip_population_grad_max": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
@@ -136,6 +137,8 @@ SYMBOLS = {
     "rdis_hip_lm_plan_objective_device": (C.c_int, [_vp, C.POINTER(_vp)]),
     "rdis_hip_lm_plan_summary_device": (C.c_int, [_vp, C.POINTER(_vp)]),
     "rdis_hip_lm_plan_summary": (C.c_int, [_vp, _vp]),
+    "rdis_hip_lm_plan_summary_population_device": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "rdis_hip_lm_plan_summary_population": (C.c_int, [_vp, _vp]),
     "rdis_hip_lm_plan_set_option": (C.c_int, [_vp, C.c_char_p, _i64]),
     "rdis_hip_lm_plan_get_info": (C.c_int, [_vp, C.c_char_p, C.POINTER(_i64)]),
     "rdis_hip_components": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
@@ -585,6 +588,14 @@ class Population:
         self.ctx.check(self.ctx.lib.rdis_hip_population_sort(self.h, _ptr(order)))
         return order
 
+    def permute(self, order):
+        """new row r := old row order[r] (order: a permutation of the members; None, an entry out of range or a duplicate: the
+        library refuses, nothing changed).  A valid last evaluation is permuted with the rows and stays valid; enqueued"""
+        order = None if order is None else np.ascontiguousarray(order, dtype=np.int64)
+        if order is not None and order.shape != (self.nmembers,):
+            raise ValueError("order must be [nmembers]")
+        self.ctx.check(self.ctx.lib.rdis_hip_population_permute(self.h, _ptr(order)))
+
     def eval_grad(self, fac=None, first=0, count=None):
         """(f[count], g[count, nvars]) of members first .. first + count - 1 (default: to the last): row k is, bit for bit, what
         Problem.eval_grad(fac) returns with member first + k's x assigned -- all members in one round of three or four kernels
@@ -621,7 +632,8 @@ class Population:
 
     def info(self, name: str) -> int:
         """eval_members_per_launch, eval_launches (kernels of the last evaluation), eval_valid; grad_members_per_launch,
-        grad_launches (kernels of the last gradient call), grad_branch (0 none, 1 fused, 2 short, 3 two-pass)"""
+        grad_launches (kernels of the last gradient call), grad_branch (0 none, 1 fused, 2 short, 3 two-pass); nmembers,
+        problem_handle (the problem's native handle as an integer)"""
         v = _i64()
         self.ctx.check(self.ctx.lib.rdis_hip_population_get_info(self.h, name.encode(), C.byref(v)))
         return int(v.value)
@@ -739,6 +751,14 @@ class LmPlan:
         out = np.zeros(LM_SUMMARY_DOUBLES)
         self.ctx.check(self.ctx.lib.rdis_hip_lm_plan_summary(self.h, _ptr(out)))
         return out
+
+    def summary_population(self) -> np.ndarray:
+        """[count, 16] after solve_population(): row i is summary()'s 16 doubles over the result rows of member first + i -- bit for
+        bit what summary() returns after solve() on a problem whose x is that member's; one launch, a workgroup per member; waits.
+        Before any solve and after solve() / solve_starts(): the library refuses"""
+        out = np.zeros((max(self._nmembers, 1), LM_SUMMARY_DOUBLES))
+        self.ctx.check(self.ctx.lib.rdis_hip_lm_plan_summary_population(self.h, _ptr(out)))
+        return out[:self._nmembers]
 
     def summary_device_ptr(self) -> int:
         p = _vp()

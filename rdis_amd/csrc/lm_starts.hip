@@ -107,6 +107,50 @@ k_lm_plan_summary(long long ncomp, const double* __restrict__ res, long long str
     }
 }
 
+// k_lm_plan_summary for every member of a population solve at once: workgroup blockIdx.x (striding beyond the grid) sums member
+// m's result rows res + m * member_stride + c * stride into out + m * LM_SUMMARY_DOUBLES.  Per member the very sequence of
+// additions of k_lm_plan_summary -- the lane's stride, the butterfly, the waves in wave order -- so a member's block is bit for
+// bit that kernel's over the same rows.  Lane 0 stores the member's block; nothing else is written.
+__global__ void __launch_bounds__(256)
+k_lm_plan_summary_members(long long nmembers, long long ncomp, const double* __restrict__ res, long long member_stride, long long stride,
+                          double* __restrict__ out) {
+    __shared__ double red[4][LM_SUMMARY_FIELDS];
+    for (long long m = blockIdx.x; m < nmembers; m += gridDim.x) {
+        const double* __restrict__ rows = res + m * member_stride;
+        double acc[LM_SUMMARY_FIELDS];
+        for (int k = 0; k < LM_SUMMARY_FIELDS; ++k) acc[k] = 0.0;
+        for (long long c = threadIdx.x; c < ncomp; c += 256) {
+            const double* __restrict__ r = rows + c * stride;
+            const double fret = r[LM_ROW_FRET];
+            acc[LM_SUMMARY_FRET] += fret;
+            acc[LM_SUMMARY_DELTA] += fret - r[LM_ROW_F0];
+            acc[LM_SUMMARY_ITERS] += r[LM_ROW_INFO + 0];
+            acc[LM_SUMMARY_NFEV] += r[LM_ROW_INFO + 2];
+            acc[LM_SUMMARY_NJEV] += r[LM_ROW_INFO + 3];
+            acc[LM_SUMMARY_NSOLVE] += r[LM_ROW_INFO + 4];
+            const int stop = (int)r[LM_ROW_INFO + 1];
+            for (int k = 1; k <= 7; ++k) acc[LM_SUMMARY_STOP1 + k - 1] += stop == k ? 1.0 : 0.0;
+            acc[LM_SUMMARY_NONFINITE] += (fret - fret == 0.0) ? 0.0 : 1.0;
+        }
+        for (int k = 0; k < LM_SUMMARY_FIELDS; ++k) {
+            double a = acc[k];
+            for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = a;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double* __restrict__ to = out + m * LM_SUMMARY_DOUBLES;
+            for (int k = 0; k < LM_SUMMARY_FIELDS; ++k) {
+                double s = 0.0;
+                for (int w = 0; w < 4; ++w) s += red[w][k];
+                to[k] = s;
+            }
+            for (int k = LM_SUMMARY_FIELDS; k < LM_SUMMARY_DOUBLES; ++k) to[k] = 0.0;
+        }
+        __syncthreads();   // (red is free again before the next member of this workgroup)
+    }
+}
+
 // blocks of 256 lanes over `work` items, at most `cap` (the kernels stride beyond)
 unsigned blocks_for(long long work, long long cap) {
     const long long b = (work + 255) / 256;
@@ -143,6 +187,13 @@ hipError_t lm_plan_objective_launch(hipStream_t stream, long long ncomp, const d
 
 hipError_t lm_plan_summary_launch(hipStream_t stream, long long ncomp, const double* res, long long stride, double* out) {
     k_lm_plan_summary<<<1, 256, 0, stream>>>(ncomp, res, stride, out);
+    return hipGetLastError();
+}
+
+hipError_t lm_plan_summary_members_launch(hipStream_t stream, long long nmembers, long long ncomp, const double* res, long long member_stride,
+                                          long long stride, double* out) {
+    if (nmembers <= 0) return hipSuccess;
+    k_lm_plan_summary_members<<<(unsigned)(nmembers < 65535 ? nmembers : 65535), 256, 0, stream>>>(nmembers, ncomp, res, member_stride, stride, out);
     return hipGetLastError();
 }
 

@@ -75,6 +75,11 @@ hipError_t lm_plan_objective_launch(hipStream_t stream, long long ncomp, const d
 // out[0 .. LM_SUMMARY_DOUBLES): the fields above over the rows res + c * stride, c < ncomp, every field in that same order; one
 // workgroup of 256, lane 0 stores the block with plain stores
 hipError_t lm_plan_summary_launch(hipStream_t stream, long long ncomp, const double* res, long long stride, double* out);
+// the same per member of a population solve, in one launch: out[m][0 .. LM_SUMMARY_DOUBLES) over the rows res + m * member_stride +
+// c * stride, c < ncomp, m < nmembers; one workgroup of 256 per member (the member in the grid's x dimension, striding beyond 65535
+// workgroups), every field in lm_plan_summary_launch's order -- member m's block is bit for bit that launch's over the same rows
+hipError_t lm_plan_summary_members_launch(hipStream_t stream, long long nmembers, long long ncomp, const double* res, long long member_stride,
+                                          long long stride, double* out);
 #endif
 
 }  // namespace rdis_hip

@@ -2584,8 +2584,10 @@ extern "C" int rdis_hip_population_get_info(rdis_hip_population* pop, const char
     else if (n == "grad_members_per_launch") *value = pop->grad_per_launch;
     else if (n == "grad_launches") *value = pop->grad_launches;
     else if (n == "grad_branch") *value = pop->grad_branch;
+    else if (n == "nmembers") *value = pop->nmembers;
+    else if (n == "problem_handle") *value = (int64_t)reinterpret_cast<intptr_t>(pop->prob);   // (to compare with the caller's rdis_hip_problem*)
     else return fail(pop->prob->ctx, RDIS_HIP_EINVAL, "population_get_info: unknown name '" + n + "' (eval_members_per_launch, eval_launches, eval_valid, "
-                                                     "grad_members_per_launch, grad_launches, grad_branch)");
+                                                     "grad_members_per_launch, grad_launches, grad_branch, nmembers, problem_handle)");
     return 0;
 }
 
@@ -2663,6 +2665,44 @@ extern "C" int rdis_hip_population_sort(rdis_hip_population* pop, int64_t* order
         HIPCHK(c, hipMemcpyAsync(order_out, pop->order.p, (size_t)S_n * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
+    return 0;
+}
+
+// X_new[r] = X_old[order[r]] for an order the caller chose (population_sort: the order of the values): the sort's permute kernel
+// and second buffer.  The list is checked on the host -- a permutation, nothing less -- before anything is allocated or launched.
+extern "C" int rdis_hip_population_permute(rdis_hip_population* pop, const int64_t* order) {
+    if (!pop) return RDIS_HIP_EINVAL;
+    rdis_hip_problem* p = pop->prob;
+    rdis_hip_ctx* c = p->ctx;
+    const int64_t S_n = pop->nmembers;
+    if (!order) return fail(c, RDIS_HIP_EINVAL, "population_permute: order is NULL (order[r]: the row that becomes row r)");
+    std::vector<uint8_t> seen((size_t)S_n, 0);
+    for (int64_t r = 0; r < S_n; ++r) {
+        const int64_t s = order[r];
+        if (s < 0 || s >= S_n)
+            return fail(c, RDIS_HIP_EINVAL, "population_permute: order[" + std::to_string(r) + "] = " + std::to_string(s) + " is out of range (the population has " +
+                                            std::to_string(S_n) + " members)");
+        if (seen[(size_t)s])
+            return fail(c, RDIS_HIP_EINVAL, "population_permute: member " + std::to_string(s) + " is named twice (order[" + std::to_string(r) + "]): not a permutation");
+        seen[(size_t)s] = 1;
+    }
+    USE_DEVICE(c);
+    int rc;
+    // (a failure here leaves the population as it was: nothing has been launched)
+    if ((rc = ensure(c, pop->X2, pop->X.bytes)) || (rc = ensure(c, pop->f2, (size_t)S_n * sizeof(double))) ||
+        (rc = ensure(c, pop->order, (size_t)S_n * sizeof(long long))))
+        return rc;
+    static_assert(sizeof(long long) == sizeof(int64_t), "order is copied in as it lies");
+    HIPCHK(c, hipMemcpyAsync(pop->order.p, order, (size_t)S_n * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (staged: the caller's array is free again)
+    HIPCHK(c, population_permute_rows_launch(c->stream, S_n, p->N, pop->order.as<long long>(), pop->X.as<double>(), pop->f.as<double>(),
+                                             pop->X2.as<double>(), pop->f2.as<double>()));
+    // as population_sort: X and X2 swap roles, f keeps its address and takes the permuted values (stale ones stay stale: eval_valid
+    // is left as it is)
+    std::swap(pop->X.p, pop->X2.p);
+    std::swap(pop->X.bytes, pop->X2.bytes);
+    HIPCHK(c, hipMemcpyAsync(pop->f.p, pop->f2.p, (size_t)S_n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    pop->best_current = false;
     return 0;
 }
 
@@ -2987,6 +3027,10 @@ struct rdis_hip_lm_plan {
     DevBuf summary, summary_pin;
     double summary_host[RDIS_HIP_LM_SUMMARY_DOUBLES] = {};
     bool summary_pin_tried = false;
+    // rdis_hip_lm_plan_summary_population: [count][16] on the device and a pinned image of that size, both grown on demand (no
+    // pinned memory to be had: the copy goes to the caller's array directly)
+    DevBuf member_summary, member_summary_pin;
+    bool member_summary_pin_failed = false;
     hipEvent_t starts_stage_ev = nullptr;
     bool starts_stage_busy = false;
     ~rdis_hip_lm_plan() { if (starts_stage_ev) (void)hipEventDestroy(starts_stage_ev); }
@@ -3319,6 +3363,45 @@ extern "C" int rdis_hip_lm_plan_summary(rdis_hip_lm_plan* L, double* out16) {
     HIPCHK(c, hipMemcpyAsync(img, dev, sizeof(L->summary_host), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::memcpy(out16, img, sizeof(L->summary_host));
+    return 0;
+}
+
+// The summary per member of the last population solve: one launch over the whole range (the outputs of a solve that was split by
+// workspace_bytes lie in one block all the same), one workgroup per member.
+extern "C" int rdis_hip_lm_plan_summary_population_device(rdis_hip_lm_plan* L, void** dev_ptr) {
+    if (!L || !dev_ptr) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = L->prob->ctx;
+    if (L->last_kind != 2)
+        return fail(c, RDIS_HIP_EINVAL, L->last_kind == 0 ? "lm_plan_summary_population: nothing was solved yet"
+                                                          : "lm_plan_summary_population: the last solve was not a population solve (rdis_hip_lm_plan_summary)");
+    USE_DEVICE(c);
+    const int64_t count = L->last_count;
+    const int rc = ensure(c, L->member_summary, (size_t)count * sizeof(double) * LM_SUMMARY_DOUBLES);
+    if (rc) return rc;
+    const long long member_stride = L->layout.out.doubles(LM_PLAN_RES);
+    const long long stride = L->ncomp > 0 ? member_stride / L->ncomp : 0;
+    HIPCHK(c, lm_plan_summary_members_launch(c->stream, count, L->ncomp, L->ncomp > 0 ? L->res_dev(L->last_rows) : nullptr, member_stride, stride,
+                                             L->member_summary.as<double>()));
+    *dev_ptr = L->member_summary.p;
+    return 0;
+}
+
+extern "C" int rdis_hip_lm_plan_summary_population(rdis_hip_lm_plan* L, double* out) {
+    if (!L || !out) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = L->prob->ctx;
+    void* dev = nullptr;
+    const int rc = rdis_hip_lm_plan_summary_population_device(L, &dev);
+    if (rc) return rc;
+    USE_DEVICE(c);
+    const size_t bytes = (size_t)L->last_count * sizeof(double) * LM_SUMMARY_DOUBLES;
+    if (L->member_summary_pin.bytes < bytes && !L->member_summary_pin_failed) {
+        const std::string err = c->err;
+        if (halloc(c, L->member_summary_pin, bytes) != 0) { (void)hipGetLastError(); c->err = err; L->member_summary_pin_failed = true; }   // pageable, and no error
+    }
+    void* const img = L->member_summary_pin.bytes >= bytes ? L->member_summary_pin.p : static_cast<void*>(out);
+    HIPCHK(c, hipMemcpyAsync(img, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (img != out) std::memcpy(out, img, bytes);
     return 0;
 }
 

@@ -10,6 +10,7 @@
 #include <numeric>
 
 #include "../../include/rdis_hip.h"
+#include "level_members.h"
 #include "lm_routing.h"
 
 namespace rdis {
@@ -246,7 +247,7 @@ void HipRDISLevelOptimizer::buildTree() {
     decomp_ms_ = now_ms() - t0;
 }
 
-void HipRDISLevelOptimizer::buildPlans() {
+void HipRDISLevelOptimizer::buildPlans(bool forPopulation) {
     releasePlans();
     int maxDepth = 0;
     for (const Node& nd : nodes_) maxDepth = std::max(maxDepth, nd.depth);
@@ -279,7 +280,8 @@ void HipRDISLevelOptimizer::buildPlans() {
                 lp->p_free_ptr.assign(1, 0); lp->p_fac_ptr.assign(1, 0);
                 for (size_t c = 0; c < ncomp; ++c) {
                     const size_t v0 = (size_t)lp->free_ptr[c], v1 = (size_t)lp->free_ptr[c + 1], f0 = (size_t)lp->fac_ptr[c], f1 = (size_t)lp->fac_ptr[c + 1];
-                    if (lm_->routeOf(lp->free_vid, v0, v1, f1 - f0) == LM_ROUTE_SINGLE) { lp->singles.push_back(c); continue; }
+                    // (a population run: every component into the plan -- a call of its own cannot take a member)
+                    if (!forPopulation && lm_->routeOf(lp->free_vid, v0, v1, f1 - f0) == LM_ROUTE_SINGLE) { lp->singles.push_back(c); continue; }
                     lp->planned.push_back(c);
                     lp->p_free_vid.insert(lp->p_free_vid.end(), lp->free_vid.begin() + (long)v0, lp->free_vid.begin() + (long)v1);
                     lp->p_fac_id.insert(lp->p_fac_id.end(), lp->fac_id.begin() + (long)f0, lp->fac_id.begin() + (long)f1);
@@ -293,6 +295,7 @@ void HipRDISLevelOptimizer::buildPlans() {
             } else if (batch_ && f_.numDevices() == 1)
                 check(f_.deviceContext(), rdis_hip_plan_create(p, (int64_t)ncomp, lp->free_ptr.data(), lp->free_vid.data(),
                                                                lp->fac_ptr.data(), lp->fac_id.data(), &lp->plan), "rdis_hip_plan_create");
+            if (forPopulation && lp->plan) check(f_.deviceContext(), rdis_hip_plan_set_option(lp->plan, "population_tiny", 1), "rdis_hip_plan_set_option");
         }
 }
 
@@ -487,6 +490,165 @@ Numeric HipRDISLevelOptimizer::optimize(bool printInfo) {
     const double check_f = f_.eval();   // the running sum of the launches' deltas IS the function value
     if (printInfo) std::cout << "level driver: final value " << check_f << " (sum of deltas: " << objective << ") after " << sweeps_ << " sweep(s)" << std::endl;
     return check_f;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The sweeps on a population (header comment).  One step: the plan's population solve on rows 0 .. active - 1, then per active
+// member the single-state step's sums -- runLmPlan's (no singles) or runPlan's -- added to that member's running objective.
+void HipRDISLevelOptimizer::stepPopulation(LevelPlan& lp, rdis_hip_population* pop, int sweep, const std::vector<int64_t>& rowToMember, int64_t active,
+                                           std::vector<double>& objective) {
+    const double t0 = now_ms();
+    const size_t ncomp = lp.node.size(), A = (size_t)active;
+    rdis_hip_ctx* ctx = f_.deviceContext();
+    std::vector<Step> steps(A);
+    if (lm_) {
+        check(ctx, rdis_hip_lm_plan_solve_population(lp.lmplan, pop, 0, active, (int32_t)ssmaxit_, ssftol_), "rdis_hip_lm_plan_solve_population");
+        std::vector<double> sum(A * RDIS_HIP_LM_SUMMARY_DOUBLES);
+        check(ctx, rdis_hip_lm_plan_summary_population(lp.lmplan, sum.data()), "rdis_hip_lm_plan_summary_population");
+        for (size_t r = 0; r < A; ++r) {
+            const double* m = sum.data() + r * RDIS_HIP_LM_SUMMARY_DOUBLES;
+            Step& s = steps[r];
+            objective[(size_t)rowToMember[r]] += m[1];
+            s.iters = (long long)m[2]; s.fevals = (long long)m[3]; s.invalid = (long long)m[12]; s.nonfinite = (long long)m[13];
+        }
+    } else {
+        check(ctx, rdis_hip_plan_solve_population_range(lp.plan, pop, 0, active, (int32_t)ssmaxit_, ssftol_), "rdis_hip_plan_solve_population_range");
+        std::vector<double> delta(A * ncomp);
+        std::vector<int32_t> iters(A * ncomp), status(A * ncomp);
+        check(ctx, rdis_hip_plan_fetch_population(lp.plan, nullptr, nullptr, delta.data(), iters.data(), status.data(), nullptr, nullptr),
+              "rdis_hip_plan_fetch_population");
+        for (size_t r = 0; r < A; ++r) {
+            double dsum = 0.0;
+            long long it = 0;
+            for (size_t c = 0; c < ncomp; ++c) {
+                const int st = status[r * ncomp + c] & 0xff;
+                if (st == RDIS_HIP_EXIT_SYNC_TIMEOUT) throw HipError(RDIS_HIP_EDEVICE, "level driver: device-side exchange timed out");
+                if (st == RDIS_HIP_EXIT_EMPTY) continue;
+                dsum += delta[r * ncomp + c];
+                it += iters[r * ncomp + c] + 1;
+            }
+            objective[(size_t)rowToMember[r]] += dsum;
+            steps[r].iters = it;
+        }
+    }
+    const double ms = now_ms() - t0;
+    for (size_t r = 0; r < A; ++r) {
+        Step& s = steps[r];
+        s.sweep = sweep; s.depth = lp.depth; s.kind = lp.kind; s.ncomp = (long long)ncomp;
+        s.nvars = (long long)lp.free_vid.size(); s.nfactors = (long long)lp.fac_id.size();
+        s.objective = objective[(size_t)rowToMember[r]]; s.ms = ms;
+        member_traces_[(size_t)rowToMember[r]].push_back(s);
+    }
+}
+
+Numeric HipRDISLevelOptimizer::optimizePopulation(rdis_hip_population* pop, bool printInfo) {
+    if (!pop) throw std::invalid_argument("HipRDISLevelOptimizer::optimizePopulation: no population");
+    if (!batch_) throw std::logic_error("HipRDISLevelOptimizer::optimizePopulation: batch = 0 has no population form (a call per component cannot take a member)");
+    if (f_.numDevices() > 1)
+        throw std::logic_error("HipRDISLevelOptimizer::optimizePopulation: a population run is on one device only (a population lives on one device)");
+    rdis_hip_problem* p = f_.deviceProblem();   // (pushes pending host-side assignments)
+    rdis_hip_ctx* ctx = f_.deviceContext();
+    int64_t handle = 0, S = 0;
+    if (rdis_hip_population_get_info(pop, "problem_handle", &handle) != 0 || rdis_hip_population_get_info(pop, "nmembers", &S) != 0)
+        throw std::logic_error("HipRDISLevelOptimizer::optimizePopulation: the population cannot be queried");
+    if (handle != (int64_t)reinterpret_cast<intptr_t>(p))
+        throw std::logic_error("HipRDISLevelOptimizer::optimizePopulation: the population belongs to another problem than this function's device problem");
+    ssmaxit_ = ss_.getMaxIters(); ssftol_ = ss_.getFtol();
+    buildTree();
+    if (lm_) {
+        const BundleAdjustmentFunction* ba = dynamic_cast<const BundleAdjustmentFunction*>(&f_);
+        if (!ba) throw std::logic_error("HipLMSubspaceOptimizer: bundle adjustment functions only");
+        for (size_t i = 0; i < nodes_.size(); ++i) {
+            const Node& nd = nodes_[i];
+            if (nd.factors.empty()) continue;
+            const std::vector<VariableID>& v = nd.leaf ? nd.vars : nd.separator;
+            const std::vector<int64_t> ids(v.begin(), v.end());
+            const long long cams = lmActiveCameras(ids.data(), ids.size(), ba->getNumCameras());
+            if (cams > RDIS_HIP_LM_WIDE_MAX_CAMERAS)
+                throw std::logic_error("HipRDISLevelOptimizer::optimizePopulation: node " + std::to_string(i) + " (depth " + std::to_string(nd.depth) +
+                                       (nd.leaf ? ", a leaf" : ", a separator") + ") has " + std::to_string(cams) + " cameras, more than the " +
+                                       std::to_string((int)RDIS_HIP_LM_WIDE_MAX_CAMERAS) + " a Levenberg-Marquardt plan takes; a population run has no single call to route it to");
+        }
+    }
+    buildPlans(true);
+    std::vector<int64_t> every(f_.getFactors().size());   // (the factor list OptimizableFunction::eval hands over)
+    std::iota(every.begin(), every.end(), (int64_t)0);
+    if (!lm_) {
+        // what the population entry refuses it refuses for the plan, not for a member's values: every plan once on a scratch
+        // population of one member (the problem's x), so that a refusal comes before any of the caller's rows is written
+        rdis_hip_population* scratch = nullptr;
+        check(ctx, rdis_hip_population_create(p, 1, nullptr, &scratch), "rdis_hip_population_create");
+        int rc = 0;
+        std::string msg;
+        for (LevelPlan* lp : plans_) {
+            rc = rdis_hip_plan_solve_population_range(lp->plan, scratch, 0, 1, 1, ssftol_);
+            if (rc != 0) { msg = rdis_hip_last_error(ctx); break; }
+        }
+        if (rc == 0) rc = rdis_hip_synchronize(ctx);
+        rdis_hip_population_destroy(scratch);
+        if (rc != 0) throw HipError(rc, "HipRDISLevelOptimizer::optimizePopulation: " + (msg.empty() ? std::string(rdis_hip_last_error(ctx)) : msg));
+    }
+    const size_t nS = (size_t)S;
+    member_results_.assign(nS, MemberResult());
+    member_traces_.assign(nS, std::vector<Step>());
+    best_member_ = -1; permute_s_ = 0; permutes_ = 0;
+    trace_.clear(); sweeps_ = 0;
+    std::vector<double> objective(nS);
+    check(ctx, rdis_hip_population_eval(pop, (int64_t)every.size(), every.data(), objective.data()), "rdis_hip_population_eval");
+    for (size_t s = 0; s < nS; ++s) member_results_[s].initial = objective[s];
+    if (printInfo) {
+        size_t nleaf = 0, nsplit = 0;
+        for (const Node& nd : nodes_) (nd.leaf ? nleaf : nsplit)++;
+        std::cout << "level driver: " << S << " members; " << nodes_.size() << " components (" << nsplit << " split by a separator, " << nleaf
+                  << " leaves) in " << plans_.size() << " launches per sweep; decomposition " << decomp_ms_ << " ms" << std::endl;
+    }
+    auto permute = [&](const std::vector<int64_t>& order) {
+        const double t0 = now_ms();
+        check(ctx, rdis_hip_population_permute(pop, order.data()), "rdis_hip_population_permute");
+        permute_s_ += (now_ms() - t0) * 1e-3;
+        ++permutes_;
+    };
+    LevelMembers rows(S);
+    std::vector<int64_t> order;
+    std::vector<double> before(nS);
+    for (int sweep = 0; sweep < maxSweeps_ && rows.active() > 0; ++sweep) {
+        const int64_t A = rows.active();
+        for (int64_t r = 0; r < A; ++r) before[(size_t)rows.memberOfRow(r)] = objective[(size_t)rows.memberOfRow(r)];
+        for (LevelPlan* lp : plans_) stepPopulation(*lp, pop, sweep, rows.rowToMember(), A, objective);
+        std::vector<char> stopped((size_t)A, 0);
+        int64_t nstopped = 0;
+        for (int64_t r = 0; r < A; ++r) {
+            const size_t s = (size_t)rows.memberOfRow(r);
+            ++member_results_[s].sweeps;
+            if (levelMemberStops(before[s], objective[s], steptol_)) { stopped[(size_t)r] = 1; ++nstopped; }
+        }
+        if (printInfo) std::cout << "sweep " << sweep << ": " << A << " member(s) solved, " << nstopped << " stopped" << std::endl;
+        // (all or none stopped: the identity, nothing moves; after the last sweep nothing is solved again: the rows stay)
+        if (sweep + 1 < maxSweeps_ && rows.partition(stopped, order)) permute(order);
+    }
+    if (rows.restore(order)) permute(order);
+    std::vector<double> fin(nS);
+    check(ctx, rdis_hip_population_eval(pop, (int64_t)every.size(), every.data(), fin.data()), "rdis_hip_population_eval");
+    int64_t best = 0;
+    double fbest = 0;
+    check(ctx, rdis_hip_population_best(pop, &best, &fbest), "rdis_hip_population_best");
+    check(ctx, rdis_hip_population_assign_best(pop), "rdis_hip_population_assign_best");
+    for (size_t s = 0; s < nS; ++s) {
+        MemberResult& m = member_results_[s];
+        m.final = fin[s]; m.sumOfDeltas = objective[s];
+        for (const Step& st : member_traces_[s]) { m.calls += st.ncomp; m.iters += st.iters; m.fevals += st.fevals; m.invalid += st.invalid; m.nonfinite += st.nonfinite; }
+    }
+    best_member_ = best;
+    trace_ = member_traces_[(size_t)best];
+    sweeps_ = member_results_[(size_t)best].sweeps;
+    // the host mirror of all values, once: the problem's x is the best member's row now
+    std::vector<int64_t> all(f_.getVariables().size());
+    std::iota(all.begin(), all.end(), (int64_t)0);
+    std::vector<double> xs(all.size());
+    check(ctx, rdis_hip_get_x(p, (int64_t)all.size(), all.data(), xs.data()), "rdis_hip_get_x");
+    f_.adoptDeviceValues(all, xs);
+    if (printInfo) std::cout << "level driver: best member " << best << ", final value " << fbest << " after " << sweeps_ << " sweep(s)" << std::endl;
+    return fin[(size_t)best];
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -31,6 +31,7 @@
 #include "rdis_host.h"
 
 struct rdis_hip_plan;
+struct rdis_hip_population;
 
 namespace rdis {
 
@@ -86,6 +87,45 @@ public:
     // Every variable must be assigned (the initial state, optBA.cpp:189-205).  Returns the final
     // value of the function; the variables are left assigned to the optimum found.
     Numeric optimize(bool printInfo = false);
+
+    // optimize() for every member of a population at once: optBA's loop over nsamples initial states (src/bundleadjust/
+    // optBA.cpp:184-211, 224-297) as ONE run.  The tree and the per-depth lists are buildTree()'s -- they depend on the structure
+    // only --, the plans are made for this run (a later optimize() makes its own): Levenberg-Marquardt plans with
+    // RDIS_HIP_LM_WIDE holding EVERY component of their launch (LMsingleMinFactors is ignored here: a call of its own cannot take
+    // a member), CGD plans with the plan option population_tiny = 1 and nothing else.  The run: obj[s] =
+    // rdis_hip_population_eval over all factors; all S rows active; in every sweep every plan solves rows 0 .. A - 1
+    // (rdis_hip_lm_plan_solve_population / rdis_hip_plan_solve_population_range) and each active member's running objective
+    // takes the step's delta sum on the host in the single-state step's order (Levenberg-Marquardt: field [1] of the member's row
+    // of rdis_hip_lm_plan_summary_population; CGD: plan_fetch_population's deltas in component order, RDIS_HIP_EXIT_EMPTY skipped,
+    // iterations counted + 1, RDIS_HIP_EXIT_SYNC_TIMEOUT thrown -- runPlan's loop); after the sweep's last plan every active
+    // member is tested with optimize()'s stop rule (level_members.h); where some but not all stopped, the rows are permuted
+    // (rdis_hip_population_permute, the stable partition: active rows first) and A shrinks -- not after sweep maxSweeps, which no
+    // solve follows --; the loop ends at A == 0 or maxSweeps.
+    // Then one permute puts member s back into row s, rdis_hip_population_eval gives every member's final value,
+    // rdis_hip_population_assign_best makes the best member the problem's x, the host mirror of the values is brought up to date
+    // once, and that member's value is returned.
+    // The contract: for every member s, row s afterwards, memberResults()[s] and memberTrace(s) (sweep, depth, kind, ncomp, iters,
+    // objective, fevals, invalid, nonfinite) are bit for bit what optimize() leaves and records when it runs alone from that
+    // member's start (Levenberg-Marquardt: with LMsingleMinFactors = 0); a member is never solved again once it has stopped; the
+    // only rows written are the members'.  Step::ms is the step's wall time, shared by the members of the step.  trace() and
+    // sweepsDone() afterwards describe the best member.
+    // Throws, before anything is solved or written, with a message that names the cause: batch = 0; several devices; a population
+    // of another problem than f.deviceProblem(); Levenberg-Marquardt and a component of more than RDIS_HIP_LM_WIDE_MAX_CAMERAS
+    // cameras (the message names the node and its camera count: beyond every plan, and refused rather than routed); a CGD plan the
+    // population entry refuses -- cooperative, pipelined or grid components, point-major components in groups -- with that
+    // entry's own message (every plan is proved on a scratch population of one member first, so no row has been written).
+    struct MemberResult {
+        double initial, final, sumOfDeltas;   // f at the start; f evaluated at the end; the running objective (initial + the deltas)
+        int sweeps;
+        long long calls, iters, fevals, invalid, nonfinite;   // summed over the member's steps as Step counts them (calls: ncomp)
+    };
+    Numeric optimizePopulation(rdis_hip_population* pop, bool printInfo = false);
+    const std::vector<MemberResult>& memberResults() const { return member_results_; }
+    const std::vector<Step>& memberTrace(size_t s) const { return member_traces_.at(s); }
+    long long bestMember() const { return best_member_; }
+    // of the last optimizePopulation: seconds in rdis_hip_population_permute calls (waits included), and how many there were
+    double permuteSeconds() const { return permute_s_; }
+    int permutes() const { return permutes_; }
 
     // The same tree under the REFERENCE'S schedule (round 4): what doOptimization / getValueFromDomain do at every node
     // (src/RDISOptimizer.cpp:253-334, 971-1147, 1507-1577) with branch and bound and the component cache off --
@@ -160,7 +200,7 @@ public:
 private:
     struct LevelPlan;
     void buildTree();
-    void buildPlans();
+    void buildPlans(bool forPopulation = false);
     void releasePlans();
     double runPlan(LevelPlan& lp, int sweep, double objective, bool printInfo);
     OptimizableFunction& f_;
@@ -179,6 +219,14 @@ private:
     std::vector<Step> trace_;
     int sweeps_;
     double decomp_ms_;
+    // population run
+    void stepPopulation(LevelPlan& lp, rdis_hip_population* pop, int sweep, const std::vector<int64_t>& rowToMember, int64_t active,
+                        std::vector<double>& objective);
+    std::vector<MemberResult> member_results_;
+    std::vector<std::vector<Step> > member_traces_;
+    long long best_member_ = -1;
+    double permute_s_ = 0;
+    int permutes_ = 0;
     // reference schedule
     struct NodeState;
     void runSet(const std::vector<int>& set, const std::vector<char>& randomInit, std::vector<NodeState>& st, bool printInfo);
