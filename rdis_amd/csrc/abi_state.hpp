@@ -1,7 +1,8 @@
 // abi_state.hpp -- what the translation units of the C ABI (include/rdis_hip.h) share: the handles' structs, the small helpers
-// every entry point uses (errors, the current device, device memory) and prepare_partition.  Internal to librdis_hip.so.
+// every entry point uses (errors, the current device, device memory) and the two functions of rdis_hip.hip another unit calls
+// (prepare_partition, problem_scratch).  Internal to librdis_hip.so.
 // No kernel and no header with a kernel is seen from here: rdis_hip.hip is the one translation unit of the ABI with device
-// code, the others (comm.hip, plan_query.hip) are host code.
+// code, the others (comm.hip, plan_query.hip, lm_api.hip) are host code.
 #pragma once
 #include "../../include/rdis_hip.h"
 
@@ -32,6 +33,9 @@ namespace rdis_hip {
 // sees both, asserts each equal to its original.
 constexpr int ABI_LDS_MAX_BYTES = 160 * 1024 - 4096;   // solver_lds.hpp: LDS_MAX_BYTES
 constexpr int ABI_PIPE_TM = 48;                        // solver_pipe.hpp: PIPE_TM
+// the caller's starts of a multi-start solve go through pinned memory up to this size (rdis_hip_plan_solve_starts,
+// rdis_hip_lm_plan_solve_starts)
+constexpr size_t STARTS_STAGE_MAX_BYTES = 64u << 20;
 }  // namespace rdis_hip
 
 struct rdis_hip_ctx {
@@ -398,4 +402,5 @@ struct rdis_hip_plan : PlanOptions, PlanIndex {
 // rdis_hip.hip: decide which solver takes each component and build what it needs (plan_query.hip asks before it answers)
 namespace rdis_hip {
 int prepare_partition(rdis_hip_plan* L);
+int problem_scratch(rdis_hip_problem* p);   // rdis_hip.hip's ensure_problem_scratch (the problem's shared scratch, at first use) for lm_api.hip
 }

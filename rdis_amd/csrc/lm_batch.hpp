@@ -27,7 +27,7 @@ namespace rdis_hip {
 
 constexpr int LM_BATCH_MAX_CAMERAS = 16;   // include/rdis_hip.h: RDIS_HIP_LM_BATCH_MAX_CAMERAS
 constexpr int LM_BATCH_WIDE_MAX_CAMERAS = 64;   // include/rdis_hip.h: RDIS_HIP_LM_WIDE_MAX_CAMERAS (with the option RDIS_HIP_LM_WIDE)
-constexpr int LM_BATCH_EINVAL = -1, LM_BATCH_ERANGE = -5;   // include/rdis_hip.h's codes (rdis_hip.hip asserts them equal)
+constexpr int LM_BATCH_EINVAL = -1, LM_BATCH_ERANGE = -5;   // include/rdis_hip.h's codes (lm_api.hip asserts them equal)
 
 // ---- component classes: the workgroup and its dynamic LDS are a function of the component alone ---------------------------
 // class 0: no active camera block (points only: no reduced system);  1: up to 6 camera blocks;  2: up to 16;

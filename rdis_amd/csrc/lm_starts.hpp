@@ -46,7 +46,7 @@ RDIS_SELECT_FN long long lm_starts_best(long long nstarts, const double* f, long
 // summed (lm_batch.hip writes the row: fret, the value at the start, then info8) and where each sum stands in the block; the
 // counts of stop codes 1..7 follow LM_SUMMARY_STOP1, the last two doubles are zero.
 constexpr int LM_ROW_FRET = 0, LM_ROW_F0 = 1, LM_ROW_INFO = 2;
-constexpr int LM_SUMMARY_DOUBLES = 16;   // RDIS_HIP_LM_SUMMARY_DOUBLES (rdis_hip.hip asserts both equal)
+constexpr int LM_SUMMARY_DOUBLES = 16;   // RDIS_HIP_LM_SUMMARY_DOUBLES (lm_api.hip asserts both equal)
 constexpr int LM_SUMMARY_FRET = 0, LM_SUMMARY_DELTA = 1, LM_SUMMARY_ITERS = 2, LM_SUMMARY_NFEV = 3, LM_SUMMARY_NJEV = 4, LM_SUMMARY_NSOLVE = 5,
               LM_SUMMARY_STOP1 = 6, LM_SUMMARY_NONFINITE = 13, LM_SUMMARY_FIELDS = 14;
 

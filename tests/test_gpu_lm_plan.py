@@ -291,3 +291,50 @@ def test_a_plan_with_all_three_classes(gctx):
     g.set_x(X[1])
     plan.solve(5)                                                    # ... and on the problem's own x
     assert plan.info("launches") == 3 and _all_same(plan.fetch(), rows[1]) and g.get_x().tobytes() == pop.get_x(1).tobytes()
+
+
+# ---- 9. the six readers at every kind of last solve ---------------------------------------------------------------------------------------
+def test_every_reader_at_every_kind_of_last_solve(gctx):
+    """nothing solved -> solve -> solve_population (2 members) -> solve_starts (2 starts): at each stage the readers that
+    tests/test_lm_rules_cpu.py's table allows succeed, every other returns EINVAL with the table's whole message as the context's
+    last error; afterwards the plan solves and fetches what a fresh plan does"""
+    import ctypes as C
+    from test_lm_rules_cpu import REFUSALS
+    name, model = "ladybug-5-30-whole", 2
+    pp, comps, iters = S.shape(name)[:3]
+    X = M.members(name)[:2]
+    g = capi.Problem(gctx, pp)
+    plan = _plan(g, comps, model)
+    lib, h = gctx.lib, plan.h
+    dev = C.c_void_p()
+    readers = {
+        "fetch": lambda: lib.rdis_hip_lm_plan_fetch(h, None, None, None, None, None, None),
+        "fetch_population": lambda: lib.rdis_hip_lm_plan_fetch_population(h, None, None, None, None, None, None),
+        "fetch_starts": lambda: lib.rdis_hip_lm_plan_fetch_starts(h, None, None, None, None, None, None, None),
+        "objective_device": lambda: lib.rdis_hip_lm_plan_objective_device(h, C.byref(dev)),
+        "summary_device": lambda: lib.rdis_hip_lm_plan_summary_device(h, C.byref(dev)),
+        "summary_population_device": lambda: lib.rdis_hip_lm_plan_summary_population_device(h, C.byref(dev)),
+    }
+    assert list(readers) == [r[0] for r in REFUSALS]
+    pop = capi.Population(g, x=X)
+    free = S.csr(comps)[1]
+    stages = [lambda: None, lambda: plan.solve(iters), lambda: plan.solve_population(pop, maxiters=iters),
+              lambda: plan.solve_starts(X[:, free], maxiters=iters)]
+    for kind, solve in enumerate(stages):
+        solve()
+        for reader, allowed, nothing, wrong in REFUSALS:
+            rc = readers[reader]()
+            if kind in allowed:
+                assert rc == 0, (kind, reader, lib.rdis_hip_last_error(gctx.h).decode())
+            else:
+                assert rc == EINVAL, (kind, reader)
+                assert lib.rdis_hip_last_error(gctx.h).decode() == (nothing if kind == 0 else wrong), (kind, reader)
+    # the refusals left the plan usable: a solve and a fetch == a fresh plan's
+    g.set_x(pp.x0)
+    plan.solve(iters)
+    got, xgot = plan.fetch(), g.get_x()
+    g2 = capi.Problem(gctx, pp)
+    fresh = _plan(g2, comps, model)
+    fresh.solve(iters)
+    assert any(len(r.history) > 0 for r in got)
+    assert _all_same(got, fresh.fetch()) and xgot.tobytes() == g2.get_x().tobytes()
