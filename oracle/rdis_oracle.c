@@ -1683,6 +1683,16 @@ typedef struct {
     const ro_hooks *hk;   /* optional value overrides (replay); NULL normally */
 } line_t;
 
+/* The device's solvers do not evaluate again what they know bit for bit: f at step 0 of a new line is the value the last line
+ * ended on (minimizer.hpp: start_line; counted and traced like the reference's call, nrc :87).  The same point gives the same
+ * bits -- unless the new direction has an entry that is not finite: p + 0 * xi is then not p.  ro_cgd_optimize sets this for
+ * the duration of a solve without the stale-cache emulation (with it the device evaluates, noskip), so that a run that met a
+ * NaN goes on exactly as long as the device's; a finite run keeps its bits either way. */
+static int g_carry_fa = 0;
+static double g_carry_fp = 0.0;
+/* a slope along the line that is not a number (line_df): minimizer.hpp takes it for a NaN like a value (saw_nan) */
+static int g_slope_nan = 0;
+
 /* Df1dim::operator() (minimize_nrc.h:432-436) */
 static double line_f(line_t *L, double a)
 {
@@ -1705,6 +1715,7 @@ static double line_df(line_t *L)
         for (int j = 0; j < L->n; ++j) sabs += fabs(L->dft[j] * L->xi[j]);
         s = L->hk->on_slope(L->hk->ctx, s, sabs, L->xi, L->n);
     }
+    if (isnan(s)) g_slope_nan = 1;
     return s;
 }
 
@@ -1718,6 +1729,7 @@ static void bracket_min(bracket_t *B, double a, double b, line_t *L)
     const double GOLD = 1.618034, GLIMIT = 100.0, TINY = 1.0e-20;
     double ax = a, bx = b, cx, fa, fb, fc, fu, tmp;
     fa = line_f(L, ax);
+    if (g_carry_fa) fa = g_carry_fp;
     fb = line_f(L, bx);
     if (fb > fa) {
         tmp = ax; ax = bx; bx = tmp;
@@ -1851,6 +1863,7 @@ static int frprmn_ex(int n, double *x, ro_func_cb f, ro_grad_cb df, void *ctx,
         bracket_t B;
         double amin, fmin;
         if (hk && hk->on_vectors) hk->on_vectors(hk->ctx, its, n, p, xi, h);
+        g_carry_fp = fp;
         bracket_min(&B, 0.0, 1.0, &L);
         if (dbrent_min(&B, &L, &amin, &fmin)) { reason = RO_EXIT_DBRENT_ITMAX; goto done; }
         for (int j = 0; j < n; ++j) { xi[j] *= amin; p[j] += xi[j]; }
@@ -1925,7 +1938,9 @@ static double sub_f(void *ctx, const double *x)
     sub_t *S = ctx;
     ++S->nfeval;
     sub_assign(S, x);
-    return ro_eval_factors(S->p, S->nf, S->fac);
+    const double f = ro_eval_factors(S->p, S->nf, S->fac);
+    if (isnan(f)) S->saw_nan = 1;   /* (minimizer.hpp: every reply r0 != r0) */
+    return f;
 }
 
 static double sum_tree(const double *t, int64_t lo, int64_t hi)
@@ -2232,6 +2247,8 @@ void ro_cgd_optimize(ro_problem *p, int64_t nfree, const int64_t *free_vid,
     double *xw = malloc(sizeof(double) * (size_t)(nfree + 1));
 
     if (p->topo == RO_SUM_TOPOLOGY_PTM && p->kind == RO_KIND_BA) { ptm_free(p->ptm); p->ptm = ptm_build(p, nf, fac); p->ptm_at_start = 0; }
+    g_carry_fa = !p->emulate;
+    g_slope_nan = 0;
     /* SubspaceOptimizer::quickAssignVals(vars, xval, true) then sfd(xval) */
     const double finit = sub_f(&S, xval);
     memcpy(xinit, xval, sizeof(double) * (size_t)nfree);
@@ -2287,11 +2304,18 @@ void ro_cgd_optimize(ro_problem *p, int64_t nfree, const int64_t *free_vid,
     } else {
         reason = ro_frprmn((int)nfree, xw, sub_f, sub_df, &S, maxiters, ftol, &fret, &iter);
     }
+    g_carry_fa = 0;
+    /* (the device also has the slope of every bracketing trial, which the reference never forms: a direction with a NaN in it
+     * shows in the coordinates here at once; a finite trial point whose value is a number and whose gradient is not shows here
+     * only once Brent's method asks for a slope) */
+    if (g_slope_nan) S.saw_nan = 1;
     if (S.saw_nan) reason = RO_EXIT_NAN;
 
     sub_assign(&S, xw); /* assign gdmin.p with sanitisation (.cpp:61) */
     int status = reason;
-    if (fret > finit) { /* negative progress: restore (.cpp:66-80) */
+    /* negative progress: restore (.cpp:66-80).  A NaN (an assert in the reference, .cpp:175) ends the same way, as on the
+     * device (minimizer.hpp: finish_request): no comparison with it holds, so nothing that was reached can be trusted */
+    if (fret > finit || S.saw_nan) {
         status |= RO_STATUS_ROLLED_BACK;
         p->ptm_at_start = 1;
         fret = sub_f(&S, xinit);
@@ -2300,6 +2324,7 @@ void ro_cgd_optimize(ro_problem *p, int64_t nfree, const int64_t *free_vid,
     for (int64_t i = 0; i < nfree; ++i) xval[i] = p->x[free_vid[i]]; /* .cpp:84-86 */
 
     out->fret = fret; out->finit = finit; out->delta = fret - finit;
+    if ((status & RO_STATUS_ROLLED_BACK) && isnan(out->delta)) out->delta = 0.0;   /* (minimizer.hpp: delta_fval) */
     out->iters = iter; out->status = status;
     out->nfeval = S.nfeval; out->ngeval = S.ngeval;
     free(S.gdense); free(xinit); free(xw);

@@ -35,6 +35,13 @@ enum : int {
 };
 constexpr int STATUS_ROLLED_BACK = 0x100;
 
+// deltaFval of a finished solve: fret - finit.  A restored start made no progress: where its value is not a number
+// (fret and finit are the same NaN, or the same infinity) that is 0, not NaN - NaN.
+__host__ __device__ __forceinline__ double delta_fval(double fret, double finit, bool rolled_back) {
+    const double d = fret - finit;
+    return (rolled_back && d != d) ? 0.0 : d;
+}
+
 // trace record tags (the replay check in tests/ reads the same tags)
 enum : int { TR_NONE = 0, TR_F = 1, TR_FD = 2, TR_ITER = 3, TR_START = 4, TR_LINMIN = 5 };
 
@@ -218,6 +225,10 @@ struct CgdMachine {
     double ftol;
     int st, its, iter, reason;
     double finit, fp, fret;
+    // saw_nan: a value OR a slope along the line that is not a number.  The reference asserts on a NaN coordinate (CGD .cpp:175);
+    // here a NaN coordinate never reaches a factor -- the clamp sends it to the upper bound -- so a direction with a NaN in it (the
+    // gradient of a start whose value is an infinity, say) would turn every trial into a jump to the bounds, with a finite value
+    // that beats the start.  Its slope, a sum over the direction's entries, is what shows it.
     bool saw_nan, rolled_back;
     long long nfeval, ngeval;
     // bracket (nrc :80-151); every trial also yields the slope along the line (it costs no extra
@@ -370,7 +381,7 @@ struct CgdMachine {
         const double dnew = accept ? dacc : 0.5 * ebis;
         const bool tn = !(fabs(dnew) >= tol1);
         un = tn ? x1 + copysign(tol1, dnew) : x1 + dnew;
-        if (fu != fu) saw_nan = true;
+        if (fu != fu || du != du) saw_nan = true;
         a = a1; b = b1; v = v1; fv = fv1; dv = dv1; w = w1; fw = fw1; dw = dw1; x = x1; fx = fx1; dx = dx1;
         e = enew; d = dnew; tiny = tn; uu = un;
         it = it_ + 1;
@@ -477,7 +488,7 @@ struct CgdMachine {
         const bool tn = !(fabs(dnew) >= tol1);
         un = tn ? x1 + copysign(tol1, dnew) : x1 + dnew;
         const bool taken = !((s.tiny && fu > s.fx) || P.stop || conv);
-        const bool nan = s.saw_nan || fu != fu;
+        const bool nan = s.saw_nan || fu != fu || du != du;
         const long long nfe = s.nfeval + 1, nge = s.ngeval + 1;
         const int it1 = s.it + 1;
         n.a = a1; n.b = b1; n.v = v1; n.fv = fv1; n.dv = dv1; n.w = w1; n.fw = fw1; n.dw = dw1; n.x = x1; n.fx = fx1; n.dx = dx1;
@@ -517,7 +528,7 @@ struct CgdMachine {
                 st = S_BR_FB;
                 return want_fd(bx);
             case S_BR_FB:
-                fb = r0; sb = r1; vb = true; if (r0 != r0) saw_nan = true;
+                fb = r0; sb = r1; vb = true; if (r0 != r0 || r1 != r1) saw_nan = true;
                 if (fb > fa) {
                     double t = ax; ax = bx; bx = t; t = fa; fa = fb; fb = t;
                     t = sa; sa = sb; sb = t; const bool tv = va; va = vb; vb = tv;
@@ -526,7 +537,7 @@ struct CgdMachine {
                 st = S_BR_FC;
                 return want_fd(cx);
             case S_BR_FC:
-                fc = r0; sc = r1; vc = true; if (r0 != r0) saw_nan = true;
+                fc = r0; sc = r1; vc = true; if (r0 != r0 || r1 != r1) saw_nan = true;
                 st = S_BR_HEAD;
                 break;
             case S_BR_HEAD: {
@@ -544,7 +555,7 @@ struct CgdMachine {
                 return want_fd(u);
             }
             case S_BR_CASE1: {  // parabolic u between b and c
-                const double fu = r0, su = r1; if (r0 != r0) saw_nan = true;
+                const double fu = r0, su = r1; if (r0 != r0 || r1 != r1) saw_nan = true;
                 if (fu < fc) { ax = bx; bx = u; fa = fb; fb = fu; sa = sb; va = vb; sb = su; vb = true; st = S_DB_START; break; }
                 if (fu > fb) { cx = u; fc = fu; sc = su; vc = true; st = S_DB_START; break; }
                 u = cx + GOLD * (cx - bx);
@@ -552,7 +563,7 @@ struct CgdMachine {
                 return want_fd(u);
             }
             case S_BR_CASE2: {  // parabolic u between c and its limit
-                const double fu = r0, su = r1; if (r0 != r0) saw_nan = true;
+                const double fu = r0, su = r1; if (r0 != r0 || r1 != r1) saw_nan = true;
                 if (fu < fc) {
                     const double unew = u + GOLD * (u - cx);
                     bx = cx; cx = u; u = unew;
@@ -568,7 +579,7 @@ struct CgdMachine {
                 break;
             }
             case S_BR_SHIFT: {
-                const double fu = r0, su = r1; if (r0 != r0) saw_nan = true;
+                const double fu = r0, su = r1; if (r0 != r0 || r1 != r1) saw_nan = true;
                 ax = bx; bx = cx; cx = u;
                 fa = fb; fb = fc; fc = fu;
                 sa = sb; va = vb; sb = sc; vb = vc; sc = su; vc = true;
@@ -593,7 +604,7 @@ struct CgdMachine {
                 st = S_DB_FIRST;
                 return want_fd(x);
             case S_DB_FIRST:
-                fx = r0; dx = r1; if (r0 != r0) saw_nan = true;
+                fx = r0; dx = r1; if (r0 != r0 || r1 != r1) saw_nan = true;
                 ++ngeval;
                 fw = fv = fx;
                 dw = dv = dx;
@@ -633,7 +644,7 @@ struct CgdMachine {
                 return with_pending(want_fd(uu));
             }
             case S_DB_EVAL: {
-                const double fu = r0, du = r1; if (r0 != r0) saw_nan = true;
+                const double fu = r0, du = r1; if (r0 != r0 || r1 != r1) saw_nan = true;
                 if (tiny && fu > fx) return line_done();  // the minimal downhill step goes uphill: done (no df call, nrc :369-376)
                 ++ngeval;
                 if (fu <= fx) {

@@ -472,7 +472,7 @@ __device__ __forceinline__ void coop_solve(const ProblemView& P, const PlanView&
     E.write_back(E.lv, restore, true);
     E.write_back(E.wv, restore, (threadIdx.x & 63) == 0);
     if (gt == 0) {
-        L.fret[comp] = M.fret; L.delta[comp] = M.fret - M.finit; L.iters[comp] = M.iter;
+        L.fret[comp] = M.fret; L.delta[comp] = delta_fval(M.fret, M.finit, M.rolled_back); L.iters[comp] = M.iter;
         L.status[comp] = status; L.nfeval[comp] = M.nfeval; L.ngeval[comp] = M.ngeval;
         if (L.trace_n) L.trace_n[comp] = E.trn;
         E.X.tm[7] = coop_clock() - tk0;

@@ -74,7 +74,7 @@ cgd_lds_starts_kernel(ProblemView P, PlanView L0, StartsView S, int maxiters, do
         if (fi >= 0) L.xout[f0 + fi] = E.X[s];
     }
     if (E.tid == 0) {
-        L.fret[comp] = M.fret; L.delta[comp] = M.fret - M.finit; L.iters[comp] = M.iter;
+        L.fret[comp] = M.fret; L.delta[comp] = delta_fval(M.fret, M.finit, M.rolled_back); L.iters[comp] = M.iter;
         L.status[comp] = M.status(); L.nfeval[comp] = M.nfeval; L.ngeval[comp] = M.ngeval;
     }
 }

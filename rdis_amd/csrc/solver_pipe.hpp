@@ -1123,7 +1123,7 @@ __device__ __forceinline__ void pipe_solve(const ProblemView& P, const PlanView&
     }
     __syncthreads();
     if (wg == 0 && tid == 0) {
-        L.fret[comp] = S.fret; L.delta[comp] = S.fret - S.finit; L.iters[comp] = S.iter;
+        L.fret[comp] = S.fret; L.delta[comp] = delta_fval(S.fret, S.finit, S.rolled_back != 0); L.iters[comp] = S.iter;
         L.status[comp] = S.status; L.nfeval[comp] = S.nfeval; L.ngeval[comp] = S.ngeval;
         if (L.trace_n) L.trace_n[comp] = E.trn;
         // the plan's objective where this launch is the whole solve (rdis_hip_plan_solve then launches no objective_sum_kernel):

@@ -75,7 +75,7 @@ cgd_ptm_population_kernel(ProblemView P0, PlanView L0, StartsView S, PtmReplicas
     run_machine(E, M, Q, maxiters, ftol);
     E.write_back(M.rolled_back);
     if (E.tid == 0) {
-        L.fret[comp] = M.fret; L.delta[comp] = M.fret - M.finit; L.iters[comp] = M.iter;
+        L.fret[comp] = M.fret; L.delta[comp] = delta_fval(M.fret, M.finit, M.rolled_back); L.iters[comp] = M.iter;
         L.status[comp] = M.status(); L.nfeval[comp] = M.nfeval; L.ngeval[comp] = M.ngeval;
     }
 }

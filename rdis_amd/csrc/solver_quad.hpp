@@ -115,7 +115,7 @@ struct GroupEnv {
                     L.xout[f0 + t] = xf;
                 }
             }
-            L.fret[comp] = M.fret; L.delta[comp] = M.fret - M.finit; L.iters[comp] = M.iter;
+            L.fret[comp] = M.fret; L.delta[comp] = delta_fval(M.fret, M.finit, M.rolled_back); L.iters[comp] = M.iter;
             L.status[comp] = M.status(); L.nfeval[comp] = M.nfeval; L.ngeval[comp] = M.ngeval;
             if (L.trace_n) L.trace_n[comp] = trn;
         }

@@ -210,7 +210,7 @@ cgd_stream_kernel(ProblemView P, PlanView L, StreamArgs A, int maxiters, double 
         L.dir[v] = 0.0;         // dir is shared by all plans of the problem: leave it zero
     }
     if (gt == 0) {
-        L.fret[comp] = M.fret; L.delta[comp] = M.fret - M.finit; L.iters[comp] = M.iter;
+        L.fret[comp] = M.fret; L.delta[comp] = delta_fval(M.fret, M.finit, M.rolled_back); L.iters[comp] = M.iter;
         L.status[comp] = status; L.nfeval[comp] = M.nfeval; L.ngeval[comp] = M.ngeval;
         if (L.trace_n) L.trace_n[comp] = E.trn;
         E.X.tm[7] = coop_clock() - tk0;

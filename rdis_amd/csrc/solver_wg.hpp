@@ -552,7 +552,7 @@ cgd_wg_kernel(ProblemView P, PlanView L, int maxiters, double ftol) {
         L.dir[E.fv[i]] = 0.0;  // dir is shared by all plans of the problem: leave it zero
     }
     if (E.tid == 0) {
-        L.fret[comp] = M.fret; L.delta[comp] = M.fret - M.finit; L.iters[comp] = M.iter;
+        L.fret[comp] = M.fret; L.delta[comp] = delta_fval(M.fret, M.finit, M.rolled_back); L.iters[comp] = M.iter;
         L.status[comp] = M.status(); L.nfeval[comp] = M.nfeval; L.ngeval[comp] = M.ngeval;
         if (L.trace_n) L.trace_n[comp] = E.trn;
     }

@@ -81,7 +81,7 @@ cgd_wg_starts_kernel(ProblemView P0, PlanView L0, StartsView S, int maxiters, do
         L.dir[E.fv[i]] = 0.0;  // the replica's dir is zero between launches
     }
     if (E.tid == 0) {
-        L.fret[comp] = M.fret; L.delta[comp] = M.fret - M.finit; L.iters[comp] = M.iter;
+        L.fret[comp] = M.fret; L.delta[comp] = delta_fval(M.fret, M.finit, M.rolled_back); L.iters[comp] = M.iter;
         L.status[comp] = M.status(); L.nfeval[comp] = M.nfeval; L.ngeval[comp] = M.ngeval;
     }
 }

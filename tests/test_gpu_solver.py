@@ -1564,8 +1564,10 @@ def test_batch_solvers_with_active_bounds_partial_blocks_and_rollback(gctx, solv
     the LDS-resident one (default), the point-major streaming one alone and with two workgroups per component, the
     plain one: domains tight enough that the clamp is active during the line searches (the objective is evaluated at
     clamp(p + a xi) while CG keeps the unclamped iterate, .cpp:165-168), camera and point blocks only partly free,
-    constants untouched, results inside their domains and some on a bound; and the roll-back (.cpp:66-80): a component
-    whose start is already better than anything 2 iterations from a hopeless start reach is returned restored."""
+    constants untouched, results inside their domains and some on a bound; and the roll-back (.cpp:66-80) by the one
+    way that reaches it, a start whose value is not a number.  (Without the cache emulation no finite run ends rolled back: a line search starts from
+    fa = the value the last one ended on, the bracketing keeps fb <= fa through every swap and shift, Brent's best point
+    only moves to a trial with fu <= fx, so fret never rises above finit -- tests/cgd_exit_cases.py has the argument.)"""
     opts = {"lds": {}, "point-major": {"ptm_stream": 2, "ptm_group": 1}, "point-major x2": {"ptm_stream": 2, "ptm_group": 2, "ptm_threads": 256},
             "plain": {"lds_resident": 0, "ptm_stream": 0}}[solver]
     opts = {"coop_group_min_factors": 0, "coop_min_factors": 0, **opts}
