@@ -1,4 +1,4 @@
-// population_api.hpp -- what rdis_hip.hip sees of the population entries of the LDS-resident solver (solver_lds_population.hpp)
+// population_api.hpp -- what rdis_hip.hip and population_entries.hip see of the population entries of the LDS-resident solver (solver_lds_population.hpp)
 // and of the plain one-workgroup solver (solver_wg_population.hpp), whose kernels are a translation unit of their own (population_kernels.hip),
 // and of the point-major streaming solver (solver_ptm_population.hpp; ptm_population_kernels.hip).  The per-solve arrays are the multi-start
 // entry's (starts_api.hpp: StartsView); the population itself is X[members][N], row-major.
@@ -53,5 +53,28 @@ hipError_t population_rank_launch(hipStream_t stream, long long members, const d
 // population_permute_rows_kernel: X2[r] = X[order[r]], f2[r] = f[order[r]]
 hipError_t population_permute_rows_launch(hipStream_t stream, long long members, long long N, const long long* order, const double* X, const double* f,
                                           double* X2, double* f2);
+
+// ---- a population's evaluation, argmin and gradient (population_eval_kernels.hpp); the shapes are the callers' ----
+// The member a population keeps: the minimum of f[members] by better() (population_select.hpp)
+struct MemberValue { double f; long long s; };
+// population_eval_sum_kernel<kind>: grid (nb, members_of_launch); partial[members_of_launch][nb]
+hipError_t population_eval_sum_launch(hipStream_t stream, int kind, int nb, int members_of_launch, const ProblemView& P, double* X, long long first, int nf,
+                                      const int* fac, double* partial);
+// population_final_sum_kernel: f[first + r] = the sum of partial[r][0 .. n), r < members_of_launch
+hipError_t population_final_sum_launch(hipStream_t stream, int members_of_launch, int n, const double* partial, long long first, double* f);
+// population_argmin_kernel (one workgroup) and population_copy_best_kernel (grid blocks): x = X[best->s]
+hipError_t population_argmin_launch(hipStream_t stream, long long members, const double* f, MemberValue* best);
+hipError_t population_copy_best_launch(hipStream_t stream, int grid, const double* X, long long N, const MemberValue* best, double* x);
+// population_partials_kernel, population_eval_sum_grad_kernel<kind>, population_gather_grad_kernel: grid (grid, members_of_launch);
+// gfac[members_of_launch][nslots], member first + r's gradient is row row0 + r of G.  The first two kernels are eval_kernels.hpp's and
+// their launches rdis_hip.hip's (elsewhere they compile to other text), the third is population_kernels.hip's like the rest
+hipError_t population_partials_launch(hipStream_t stream, int grid, int members_of_launch, const ProblemView& P, double* X, long long first, int nf,
+                                      const int* fac, double* gfac, long long nslots);
+hipError_t population_eval_sum_grad_launch(hipStream_t stream, int kind, int grid, int members_of_launch, const ProblemView& P, double* X, long long first,
+                                           int nf, const int* fac, double* gfac, long long nslots, double* partial);
+hipError_t population_gather_grad_launch(hipStream_t stream, int grid, int members_of_launch, int nvars, const int* v2s_ptr, const int* v2s_idx,
+                                         const double* gfac, long long nslots, double* G, long long row0);
+// population_grad_max_kernel: gmax[k] = max |G[k][.]| for k < rows, a workgroup a row
+hipError_t population_grad_max_launch(hipStream_t stream, long long rows, long long N, const double* G, double* gmax);
 
 }  // namespace rdis_hip

@@ -1,7 +1,7 @@
 // population_kernels.hip -- the population kernels of the LDS-resident solver (solver_lds_population.hpp) and of the plain
 // one-workgroup solver (solver_wg_population.hpp) and their launches, a
 // translation unit of their own (rdis_hip.hip sees them through population_api.hpp), and the kernels that draw, rank and reorder
-// the members (population_select.hpp).  A workgroup size becomes a template
+// the members (population_select.hpp) and evaluate them (population_eval_kernels.hpp).  A workgroup size becomes a template
 // argument through launch_dispatch.hpp, with the list of starts_kernels.hip: 64 ... 768, 1024 for everything else.
 #define RDIS_POPULATION_SELECT_KERNELS   // (population_select.hpp: its three kernels are defined here and nowhere else)
 #define RDIS_LDS_NO_LAUNCHER   // (cgd_lds_kernel is instantiated where it is launched: rdis_hip.hip, refround_kernels.hip)
@@ -10,6 +10,7 @@
 #include "solver_wg_population.hpp"
 #include "solver_quad_population.hpp"   // (the tiny-component solver's entry: plan option population_tiny)
 #include "population_select.hpp"        // (draw, rank, permute: what a restart loop does between two solves)
+#include "population_eval_kernels.hpp"  // (evaluation, argmin, gradient: the population forms of eval_kernels.hpp)
 #include "population_api.hpp"
 
 namespace rdis_hip {
@@ -101,6 +102,44 @@ hipError_t population_permute_rows_launch(hipStream_t stream, long long members,
     if (members <= 0) return hipSuccess;
     const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>((N + 255) / 256, 4096)), (unsigned)std::min<long long>(members, 65535));
     population_permute_rows_kernel<<<grid, 256, 0, stream>>>(members, N, order, X, f, X2, f2);
+    return hipGetLastError();
+}
+
+// ---- evaluation, argmin, gradient: the grids are the callers' (population_entries.hip), which take them from the single-x entries ----
+
+hipError_t population_eval_sum_launch(hipStream_t stream, int kind, int nb, int members_of_launch, const ProblemView& P, double* X, long long first, int nf,
+                                      const int* fac, double* partial) {
+    const dim3 grid((unsigned)nb, (unsigned)members_of_launch);
+    if (kind == KIND_BA) population_eval_sum_kernel<KIND_BA><<<grid, 256, 0, stream>>>(P, X, first, nf, fac, partial);
+    else population_eval_sum_kernel<KIND_NLP><<<grid, 256, 0, stream>>>(P, X, first, nf, fac, partial);
+    return hipGetLastError();
+}
+
+hipError_t population_final_sum_launch(hipStream_t stream, int members_of_launch, int n, const double* partial, long long first, double* f) {
+    population_final_sum_kernel<<<members_of_launch, 256, 0, stream>>>(n, partial, first, f);
+    return hipGetLastError();
+}
+
+hipError_t population_argmin_launch(hipStream_t stream, long long members, const double* f, MemberValue* best) {
+    population_argmin_kernel<<<1, 256, 0, stream>>>(members, f, best);
+    return hipGetLastError();
+}
+
+hipError_t population_copy_best_launch(hipStream_t stream, int grid, const double* X, long long N, const MemberValue* best, double* x) {
+    population_copy_best_kernel<<<grid, 256, 0, stream>>>(X, N, best, x);
+    return hipGetLastError();
+}
+
+// (population_partials_launch, population_eval_sum_grad_launch: rdis_hip.hip, where their kernels compile to the text they had)
+
+hipError_t population_gather_grad_launch(hipStream_t stream, int grid, int members_of_launch, int nvars, const int* v2s_ptr, const int* v2s_idx,
+                                         const double* gfac, long long nslots, double* G, long long row0) {
+    population_gather_grad_kernel<<<dim3((unsigned)grid, (unsigned)members_of_launch), 256, 0, stream>>>(nvars, v2s_ptr, v2s_idx, gfac, nslots, G, row0);
+    return hipGetLastError();
+}
+
+hipError_t population_grad_max_launch(hipStream_t stream, long long rows, long long N, const double* G, double* gmax) {
+    population_grad_max_kernel<<<(unsigned)rows, 256, 0, stream>>>(N, G, gmax);
     return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
-// population_state.hpp -- struct rdis_hip_population, for the two translation units of the C ABI that use it: rdis_hip.hip, which
-// holds the population's entries, and lm_api.hip, whose plans solve on a population's rows.
+// population_state.hpp -- struct rdis_hip_population, for the translation units of the C ABI that use it: population_entries.hip,
+// which holds the population's entries, and rdis_hip.hip and lm_api.hip, whose plans solve on a population's rows.
 #pragma once
 #include "abi_state.hpp"
 
@@ -31,4 +31,14 @@ struct rdis_hip_population {
     int64_t grad_per_launch = 0, grad_launches = 0;    // of the last gradient call: members of a launch, kernels launched
     int grad_branch = 0;       // ... and its form (GradBranch)
     double* row(int64_t s) const { return X.as<double>() + (size_t)s * (size_t)prob->N; }
+    void x_written() { eval_valid = false; best_current = false; }   // X is written: the values of the last evaluation are stale
 };
+
+namespace rdis_hip {
+// `bytes` of device memory into the caller's array, waited for: what every entry that hands values to the host ends in
+inline int read_back(rdis_hip_ctx* c, void* dst, const void* src, size_t bytes) {
+    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+}  // namespace rdis_hip
