@@ -4,8 +4,11 @@ variable's sampling interval, the level driver's sweeps (the 46-camera separator
 -- every step one launch over the members still running, a member that has stopped is not solved again -- with
 Levenberg-Marquardt, the two pixel residuals a factor (useCGD 0, LMmodel 2), through the C entry rdis_optba_run_samples.
 Prints per member the start value, the final value and the sweeps, then the best.
+With `cgd` as the last argument: the reference's default configuration instead, useCGD 1 -- the separator and the camera level
+run on the cooperative solver, a cooperative group per (member, component) (the level option populationCooperative = 1;
+without it this tree is refused).
 
-  python examples/ba_levels_population.py [samples] [sweeps] [SSmaxit] [seed]"""
+  python examples/ba_levels_population.py [samples] [sweeps] [SSmaxit] [seed] [cgd]"""
 import ctypes as C
 import gzip
 import os
@@ -25,6 +28,7 @@ def main():
     sweeps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
     maxit = int(sys.argv[3]) if len(sys.argv) > 3 else 25
     seed = int(sys.argv[4]) if len(sys.argv) > 4 else 20240611
+    cgd = len(sys.argv) > 5 and sys.argv[5] == "cgd"
     lib = C.CDLL(os.path.join(ROOT, "rdis_amd", "lib", "librdis_host.so"))
     lib.rdis_optba_run_samples.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.c_int32,
                                            C.c_int64, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -34,6 +38,8 @@ def main():
         with gzip.open(P.LADYBUG_PATH, "rb") as src, open(path, "wb") as dst:
             shutil.copyfileobj(src, dst)
         o = {"useCGD": 0.0, "LMmodel": 2.0, "SSmaxit": float(maxit), "maxSweeps": float(sweeps)}
+        if cgd:
+            o = {"useCGD": 1.0, "populationCooperative": 1.0, "SSmaxit": float(maxit), "maxSweeps": float(sweeps)}
         names, vals = [n.encode() for n in o], list(o.values())
         out, members = np.zeros(10), np.zeros((samples, 8))
         rc = lib.rdis_optba_run_samples(path.encode(), 0, 0, len(names), (C.c_char_p * len(names))(*names), (C.c_double * len(vals))(*vals), 0,

@@ -408,7 +408,8 @@ int rdis_hip_plan_fetch_starts(rdis_hip_plan *plan, double *x_out, double *fret,
  * "ptm_group" = 1; the lanes are "ptm_threads", else 768: plan_get_info "population_point_major_threads"), otherwise
  * RDIS_HIP_EINVAL with a message that names "ptm_group" and the group size plan_solve would pick.  A
  * persistent plan; default factor_rounding; emulate_stale_cache, trace_records and dump_iters off; the population must be
- * the plan's problem's.  Not yet: the cooperative and grid solvers and point-major components shared by several workgroups;
+ * the plan's problem's.  Not yet: the grid solver and point-major components shared by several workgroups (the cooperative
+ * solver: plan_solve_population_cooperative, below);
  * bundle-adjustment components on the plain batch solver; tiny and point-major components in plan_solve_starts.  Anything
  * else: RDIS_HIP_EINVAL and a message that names the cause; the plan and the population stay usable.
  *
@@ -458,6 +459,25 @@ int rdis_hip_plan_fetch_starts(rdis_hip_plan *plan, double *x_out, double *fret,
  *                       member first + i.  The splitting by "starts_workspace_bytes" ("starts_per_launch" /
  *                       "starts_launches" of count members), plan_last_kernel_ms and every refusal are the whole-population
  *                       entry's.
+ *   plan_solve_population_cooperative   plan_solve_population_range for plans with components on the cooperative solver,
+ *                       single large components and group mode alike (plan_get_info "components_cooperative"; ladybug's
+ *                       separator, its camera level), which the two entries above refuse: a cooperative group per (member,
+ *                       component), the groups of all members of a launch side by side in one cooperative launch per launch of
+ *                       the plan's ordinary solve (rdis_amd/csrc/solver_coop_population.hpp).  Every (member, component) gets the
+ *                       bits rdis_hip_plan_solve leaves on a problem whose x is that member's -- in the plain cooperative
+ *                       layout and, since the pipelined layout returns the same bits, in that one too.  The plan's other
+ *                       components (tiny, point-major, LDS-resident) follow as in plan_solve_population, under the options that
+ *                       admit them there; everything runs on the context's stream.  A member of a launch has replicas of the
+ *                       solver's gfac and published directions and an exchange state a group (0.5 MiB each), the plan's own,
+ *                       within "starts_workspace_bytes"; the problem's exchange state is not used.  Every workgroup of a
+ *                       cooperative launch must be resident, so the members of a launch are bounded a second time:
+ *                       R workgroups-a-member <= the resident workgroups of the kernel (plan_get_info
+ *                       "population_cooperative_workgroups", "population_cooperative_cap"; "starts_per_launch" is R,
+ *                       "starts_launches" the kernel launches).  No bit depends on R.  Refused, RDIS_HIP_EINVAL with a
+ *                       message, before any row is written: a plan whose ordinary solve uses the pipelined layout (set the plan
+ *                       option "coop_pipeline" = 0), components on the grid solver, and what plan_solve_population refuses
+ *                       ("factor_rounding" = 1, "emulate_stale_cache", "trace_records", "dump_iters", a transient plan, another
+ *                       problem's population).  rdis_hip_plan_solve_starts has no such form.
  *
  * The members' gradients, the member a grid dimension (computeGradient(facs, pg) on every member at once):
  *   population_eval_grad   f[count] and g[count][N], row-major, for members first .. first + count - 1; nf / fac as in
@@ -515,6 +535,8 @@ int rdis_hip_population_grad_max(rdis_hip_population *pop, double *gmax, void **
 int rdis_hip_plan_solve_population(rdis_hip_plan *plan, rdis_hip_population *pop, int32_t maxiters, double ftol);
 int rdis_hip_plan_solve_population_range(rdis_hip_plan *plan, rdis_hip_population *pop, int64_t first, int64_t count,
                                          int32_t maxiters, double ftol);
+int rdis_hip_plan_solve_population_cooperative(rdis_hip_plan *plan, rdis_hip_population *pop, int64_t first, int64_t count,
+                                               int32_t maxiters, double ftol);
 int rdis_hip_plan_fetch_population(rdis_hip_plan *plan, double *x_out, double *fret, double *delta, int32_t *iters,
                                    int32_t *status, int64_t *nfeval, int64_t *ngeval);
 /* sum of fret over the plan's components, left on the device (for the RCCL
@@ -770,7 +792,9 @@ int rdis_hip_plan_set_option(rdis_hip_plan *plan, const char *name, int64_t valu
  * a wide group with local camera numbering holds), "starts_per_launch" / "starts_launches" (starts a launch of the last multi-start
  * solve held; its number of launches), "population_tiny_blocks" (blocks per member of the tiny-component solver's launch in the
  * last population solve, 0 = it had none), "population_point_major_threads" (lanes of the point-major kernel's workgroups in
- * the last population solve, 0 = it had none) */
+ * the last population solve, 0 = it had none), "population_cooperative_workgroups" / "population_cooperative_cap" (of the last
+ * population solve: the most workgroups a member of a cooperative launch; the resident workgroups such a launch may have over all
+ * its members -- 0, 0: it had no cooperative launch) */
 int rdis_hip_plan_get_info(rdis_hip_plan *plan, const char *name, int64_t *value);
 /* device memory the plan holds beyond the problem's (index tables, workspace, per-factor
  * partials, results): what a host-side cache of plans budgets with

@@ -22,7 +22,11 @@ extern "C" {
  *             0: nsamples must be 1 and the member is the file's state (optBA.cpp:189-193).
  *   options   rdis_optba_run's for schedule 0: SSmaxit, SSftol, AVblkpct, steptol, maxSweeps, sepPiecePct, batch (must stay 1),
  *             useCGD, LMmodel; LMsingleMinFactors and lmStepDetail are accepted and ignored (every component goes into its
- *             launch's plan; a component of more than 64 cameras with useCGD 0 is refused: -2).  The options of schedule 1
+ *             launch's plan; a component of more than 64 cameras with useCGD 0 is refused: -2); populationCooperative (0 or
+ *             1, default 0; with useCGD 1 only it has an effect): 1 lets the run take trees with components on the cooperative
+ *             solver -- full ladybug, optBA's default configuration, refused (-2) without it -- a cooperative group per
+ *             (member, component) through rdis_hip_plan_solve_population_cooperative; every member's result keeps the bits
+ *             of rdis_optba_run from its start.  The options of schedule 1
  *             (nRRperLvl, nRRatTop, minRR, maxNAtoRR, noAssignLimitAtTop, restartSeed, maxCalls) have no meaning here: -3.
  *   out       rdis_optba_run's meaning for the BEST member (lowest final value, lowest index on a tie, never one that is not a
  *             number), except: [1] that member's start value; [2], [3] and [8] summed over all members; [9] the largest sweep

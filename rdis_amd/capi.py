@@ -105,6 +105,7 @@ SYMBOLS = {
     "rdis_hip_population_grad_max": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "rdis_hip_plan_solve_population": (C.c_int, [_vp, _vp, C.c_int32, C.c_double]),
     "rdis_hip_plan_solve_population_range": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int32, C.c_double]),
+    "rdis_hip_plan_solve_population_cooperative": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int32, C.c_double]),
     "rdis_hip_plan_fetch_population": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rdis_hip_plan_objective_device": (C.c_int, [_vp, C.POINTER(_vp)]),
     "rdis_hip_comm_unique_id": (C.c_int, [_vp]),
@@ -903,7 +904,7 @@ class Plan:
                                                                _ptr(r.status), _ptr(r.nfeval), _ptr(r.ngeval), _ptr(r.best)))
         return r
 
-    def solve_population(self, pop: "Population", maxiters=50, ftol=3e-8, first=0, count=None):
+    def solve_population(self, pop: "Population", maxiters=50, ftol=3e-8, first=0, count=None, cooperative=False):
         """every component on every member of pop in one launch (asynchronous): member s starts from its own x at the plan's free
         variables, reads its constants from its own x and is left assigned to its result -- what set_start(None) + solve does on a
         problem whose x is that member's.  The problem's x and the plan's ordinary outputs are not touched.  Bundle adjustment,
@@ -917,7 +918,17 @@ class Plan:
         the others in any mix -- info("population_point_major_threads") tells the lanes of that kernel; anything
         else -- a nonlinear-product plan, tiny or point-major components without their option included -- raises RdisHipError
         (EINVAL) with the cause.  first / count given: members first .. first + count - 1 only (rdis_hip_plan_solve_population_range:
-        the same bits for them, the other rows untouched); fetch_population then returns count rows, row i member first + i"""
+        the same bits for them, the other rows untouched); fetch_population then returns count rows, row i member first + i.
+        cooperative=True (rdis_hip_plan_solve_population_cooperative): components on the cooperative solver
+        (info("components_cooperative")) are taken too, a cooperative group per (member, component), the members of a launch side
+        by side -- the plan needs set_option("coop_pipeline", 0); info("population_cooperative_workgroups") and
+        info("population_cooperative_cap") tell the workgroups a member and the resident workgroups that bound
+        info("starts_per_launch")"""
+        if cooperative:
+            first, count = pop._range(first, count)
+            self.ctx.check(self.ctx.lib.rdis_hip_plan_solve_population_cooperative(self.h, pop.h, first, count, maxiters, ftol))
+            self._nmembers = count
+            return
         if first == 0 and count is None:
             self.ctx.check(self.ctx.lib.rdis_hip_plan_solve_population(self.h, pop.h, maxiters, ftol))
             self._nmembers = pop.nmembers

@@ -51,6 +51,7 @@ struct rdis_hip_ctx {
     // resident-workgroup caps of the cooperative layouts on THIS device (occupancy queries, asked once per context)
     int cap_pipe = -1, cap_coop[3] = {-1, -1, -1};
     int cap_pipe_rr = -1, cap_coop_rr[3] = {-1, -1, -1};   // ... of the reference-rounding instantiations (refround_api.hpp)
+    int cap_coop_pop[3] = {-1, -1, -1}, cap_coop_pop_rr[3] = {-1, -1, -1};   // ... of the cooperative population kernel (solver_coop_population.hpp), over all members of a launch
     // dynamic LDS a launch may ask for on THIS device: what a compute unit has, less the solvers' static share (at most
     // solver_lds.hpp's LDS_MAX_BYTES, which is gfx950's); components that do not fit go to the solvers that need none
     size_t lds_limit = ABI_LDS_MAX_BYTES;
@@ -323,6 +324,7 @@ struct rdis_hip_plan : PlanOptions, PlanIndex {
     // "starts_workspace_bytes" (ms_work: ws, gfac and, for the plain solver, x; ms_dir: that solver's dir, zero between launches)
     DevBuf ms_in, ms_out, ms_work, ms_dir, ms_best, ms_stage;   // (ms_stage: pinned host memory the caller's starts are uploaded through)
     DevBuf ms_queue;                  // the tiny-component population launch: a queue counter for each of its members
+    DevBuf ms_coop;                   // the cooperative population launch (rdis_hip_plan_solve_population_cooperative): a replica of gfac and of the groups' xi_glob and an exchange state a group for each of its members (within "starts_workspace_bytes" too)
     DevBuf ms_ptm;                    // the point-major population launch: a replica of pm_rec, pm_gh, pm_bex and pm_cbox for each of its members (within "starts_workspace_bytes" too)
 
     // ---- the last solve ----
@@ -339,6 +341,7 @@ struct rdis_hip_plan : PlanOptions, PlanIndex {
     bool ms_population = false;       // ... which was a population solve (rdis_hip_plan_solve_population: the members are the starts; no ms_best)
     int64_t ms_per_launch = 0, ms_launches = 0;
     int ms_tiny_blocks = 0;           // blocks a member of the tiny-component launch in the last population solve (plan_get_info "population_tiny_blocks")
+    int ms_coop_wg = 0, ms_coop_cap = 0;   // the cooperative launches of the last population solve: the most workgroups a member, and the resident workgroups a launch may have over all its members (0, 0: it had none; plan_get_info "population_cooperative_workgroups", "population_cooperative_cap")
     int ms_ptm_threads = 0;           // the lanes of the point-major kernel in the last population solve, 0 = it had none (plan_get_info "population_point_major_threads")
 
     ~rdis_hip_plan() { if (ms_stage_ev) (void)hipEventDestroy(ms_stage_ev); }

@@ -36,6 +36,8 @@ extern "C" int rdis_hip_plan_get_info(rdis_hip_plan* L, const char* name, int64_
     else if (n == "starts_launches") *value = L->ms_launches;
     else if (n == "population_tiny_blocks") *value = L->ms_tiny_blocks;
     else if (n == "population_point_major_threads") *value = L->ms_ptm_threads;
+    else if (n == "population_cooperative_workgroups") *value = L->ms_coop_wg;
+    else if (n == "population_cooperative_cap") *value = L->ms_coop_cap;
     else return fail(c, RDIS_HIP_EINVAL, "plan_get_info: unknown name '" + n + "'");
     return 0;
 }

@@ -67,4 +67,28 @@ inline std::string population_no_values_refusal(int reader) {
            (reader == POPULATION_READ_SORT ? "population_set_x / population_sample / plan_solve_population)" : "population_set_x / plan_solve_population)");
 }
 
+// ---- rdis_hip_plan_solve_population_cooperative (`who`), before any row is written: what it refuses beyond the refusals it
+// shares with rdis_hip_plan_solve_population.  The pipelined layout's lane tables are built for another lane layout than the
+// population kernel's (solver_coop_population.hpp runs the plain one); the grid solver has no population entry.
+inline std::string population_coop_pipelined_refusal(const char* who) {
+    return std::string(who) + ": cooperative components are solved on a population in the plain cooperative layout, and this plan's ordinary solve "
+                              "runs them in the pipelined layout (other lane tables; the same bits): set the plan option coop_pipeline = 0";
+}
+inline std::string population_coop_grid_refusal(const char* who, int64_t components) {
+    return std::string(who) + ": " + std::to_string(components) + " component(s) of the plan run on the grid solver, which has no population entry "
+                              "(too large for a cooperative group of resident workgroups)";
+}
+// a cooperative launch of the plan (packed under the ordinary kernel's residency) has more workgroups a member than the
+// population kernel can have resident at all: not one member fits a launch
+inline std::string population_coop_residency_refusal(const char* who, int64_t launch_workgroups, int64_t cap_workgroups) {
+    return std::string(who) + ": a cooperative launch of the plan has " + std::to_string(launch_workgroups) + " workgroups a member, and the population "
+                              "kernel can have " + std::to_string(cap_workgroups) + " resident: not one member fits a launch (set the plan option "
+                              "coop_workgroups to at most that)";
+}
+// ... and what rdis_hip_plan_solve_population and _range add to their refusal of a plan with cooperative components
+inline std::string population_coop_hint() {
+    return " (cooperative components are solved on a population by rdis_hip_plan_solve_population_cooperative, a group per member: "
+           "solver_coop_population.hpp)";
+}
+
 }  // namespace rdis_hip

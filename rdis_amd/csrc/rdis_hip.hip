@@ -19,6 +19,7 @@
 #include "grad_tables.hpp"
 #include "refround_api.hpp"
 #include "solver_coop.hpp"
+#include "solver_coop_population.hpp"
 #include "solver_lds.hpp"
 #include "population_api.hpp"
 #include "population_grid.hpp"
@@ -37,11 +38,13 @@ static_assert(sizeof(IntPair) == sizeof(int2) && offsetof(IntPair, x) == offseto
 static_assert(ABI_LDS_MAX_BYTES == LDS_MAX_BYTES && ABI_PIPE_TM == PIPE_TM && OPTION_QUAD_MAX_VARS == QUAD_MAX_VARS &&
               OPTION_COOP_MAX_WG == COOP_MAX_WG && OPTION_PTM_MAX_GROUP == PTM_WIDE_MAX_GROUP && GRAD_MEMBER_REC == GRAD_REC &&
               REPLICA_PT_REC == PT_REC, "a restated constant differs from its original");
+static_assert(sizeof(CoopState) % 32 == 0, "population_coop_layout keeps every state of ms_coop on 32 bytes");
 
 // The one place that knows there are two roundings: a solver's launches in the default rounding (fused multiply-adds), and
 // the set to use (refround_api.hpp).  A plan asks with coop_reference_rounding() or batch_reference_rounding().
 static const SolverSet& solver_set(bool reference_rounding) {
-    static const SolverSet fused = {launch_pipe, launch_coop, pipe_max_workgroups, coop_max_workgroups, launch_lds};
+    static const SolverSet fused = {launch_pipe, launch_coop, pipe_max_workgroups, coop_max_workgroups, launch_lds,
+                                    launch_coop_population, coop_population_max_workgroups};
     return reference_rounding ? refround_solvers() : fused;
 }
 
@@ -952,8 +955,8 @@ extern "C" int rdis_hip_plan_set_option(rdis_hip_plan* L, const char* name, int6
     if (effect & PLAN_OPTION_ROUNDS) L->rounds_threads = L->rounds_K = 0;   // (the round tables are built for one choice)
     if (effect & PLAN_OPTION_LOCAL) L->ptm_local_off = false;
     // (the bound holds from now on: replicas beyond it go; releasing device memory waits for the work that uses it)
-    if ((effect & PLAN_OPTION_WORKSPACE) && L->ms_work.bytes + L->ms_ptm.bytes > (size_t)value) {
-        for (DevBuf* b : {&L->ms_work, &L->ms_ptm})
+    if ((effect & PLAN_OPTION_WORKSPACE) && L->ms_work.bytes + L->ms_ptm.bytes + L->ms_coop.bytes > (size_t)value) {
+        for (DevBuf* b : {&L->ms_work, &L->ms_ptm, &L->ms_coop})
             if (b->p) { L->dev_bytes -= std::min(L->dev_bytes, b->bytes); b->release(); }
     }
     if ((effect & PLAN_OPTION_TRACE) && value > 0) {
@@ -1968,8 +1971,10 @@ namespace {
 // adjustment), or a nonlinear-product problem with every component on the plain batch solver -- *plain_solver says which
 // (entry: "multi-start" or "population" -- rdis_hip_plan_solve_population shares these checks)
 // (allow_tiny: the population entry with the plan option population_tiny -- tiny components beside LDS-resident ones pass;
-// allow_ptm: with population_point_major, point-major components too -- the entry itself then asks for one workgroup a component)
-int starts_refusal(rdis_hip_plan* L, const char* who, bool* plain_solver, const char* entry = "multi-start", bool allow_tiny = false, bool allow_ptm = false) {
+// allow_ptm: with population_point_major, point-major components too -- the entry itself then asks for one workgroup a component;
+// allow_coop: rdis_hip_plan_solve_population_cooperative -- cooperative components pass, in the plain layout and beside no grid solver)
+int starts_refusal(rdis_hip_plan* L, const char* who, bool* plain_solver, const char* entry = "multi-start", bool allow_tiny = false, bool allow_ptm = false,
+                   bool allow_coop = false) {
     rdis_hip_problem* p = L->prob;
     rdis_hip_ctx* c = p->ctx;
     const std::string w(who), en(entry);
@@ -1987,9 +1992,11 @@ int starts_refusal(rdis_hip_plan* L, const char* who, bool* plain_solver, const 
         if (L->h_fac_ptr[(size_t)cc + 1] == L->h_fac_ptr[(size_t)cc]) continue;
         if (r < (size_t)L->rest_tiny) ++tiny; else if (r >= r_ptm) ++ptm; else ++plain;
     }
+    if (allow_coop && !L->stream.empty()) return fail(c, RDIS_HIP_EINVAL, population_coop_grid_refusal(who, (int64_t)L->stream.size()));
+    if (allow_coop && !L->coop.empty() && L->use_pipe) return fail(c, RDIS_HIP_EINVAL, population_coop_pipelined_refusal(who));
     std::string others;
     auto note = [&](int64_t count, const char* solver) { if (count > 0) others += (others.empty() ? " " : ", ") + std::to_string(count) + " to the " + solver; };
-    note((int64_t)L->coop.size(), "cooperative solver");
+    if (!allow_coop) note((int64_t)L->coop.size(), "cooperative solver");
     note((int64_t)L->stream.size(), "grid solver");
     if (!allow_tiny) note(tiny, "tiny-component solver");
     if (!allow_ptm) note(ptm, "point-major streaming solver");
@@ -2004,9 +2011,10 @@ int starts_refusal(rdis_hip_plan* L, const char* who, bool* plain_solver, const 
                                                                                       "population_tiny = 1: solver_quad_population.hpp)" : "";
         const std::string ptm_hint = ptm > 0 && !allow_ptm && en == "population" ? " (point-major components are solved on a population, one workgroup each, with "
                                                                                    "the plan option population_point_major = 1: solver_ptm_population.hpp)" : "";
+        const std::string coop_hint = !L->coop.empty() && !allow_coop && en == "population" ? population_coop_hint() : "";
         return fail(c, RDIS_HIP_EINVAL, w + ": every component of the plan must run on the LDS-resident solver (bundle adjustment, variables fitting a "
                                         "compute unit's LDS) or, all of them, on the plain batch solver of a nonlinear-product problem; this plan sends" +
-                                        others + ba_plain + tiny_hint + ptm_hint);
+                                        others + ba_plain + tiny_hint + ptm_hint + coop_hint);
     }
     *plain_solver = plain_ok;
     return 0;
@@ -2164,13 +2172,19 @@ extern "C" int rdis_hip_plan_fetch_starts(rdis_hip_plan* L, double* x_out, doubl
 // =====================================================================================
 // populations: S complete states on the device, a plan solved on all of them at once (solver_lds_population.hpp; with the plan
 // option population_plain, solver_wg_population.hpp for nonlinear-product plans)
+// (rdis_hip_plan_solve_population_cooperative: the components of the cooperative solver too, solver_coop_population.hpp)
 // (struct rdis_hip_population: population_state.hpp; the rdis_hip_population_* entries: population_entries.hip)
 // =====================================================================================
 namespace {
 // rdis_hip_plan_solve_population on members first0 .. first0 + S_n - 1: the member base is X + first0 N, the per-call arrays
 // (start rows, outputs, replicas) are sized and indexed for the S_n members of the range, so member first0 + i is row i of
 // plan_fetch_population.  `who` names the entry in messages.
-int solve_population_range(rdis_hip_plan* L, rdis_hip_population* pop, int64_t first0, const int64_t S_n, int32_t maxiters, double ftol, const char* who_name) {
+// `cooperative` (rdis_hip_plan_solve_population_cooperative): the components rdis_hip_plan_solve sends to the cooperative solver are
+// taken too -- per range of R members one launch of cgd_coop_population_kernel for each CoopLaunch of the plan, on the context's
+// stream, before the other kinds (the overlap_batch side stream is not used).  The replicas and exchange states are the plan's own
+// (ms_coop): the problem's coop_state is neither used nor moved, so no other plan's group tables go stale.
+int solve_population_range(rdis_hip_plan* L, rdis_hip_population* pop, int64_t first0, const int64_t S_n, int32_t maxiters, double ftol, const char* who_name,
+                           bool cooperative = false) {
     rdis_hip_problem* p = L->prob;
     rdis_hip_ctx* c = p->ctx;
     const std::string who(who_name);
@@ -2183,7 +2197,7 @@ int solve_population_range(rdis_hip_plan* L, rdis_hip_population* pop, int64_t f
         return fail(c, RDIS_HIP_ERANGE, who + ": too many members");
     if (int rc = refuse_late_exponential(L, who_name)) return rc;   // (nonlinear products only: no bundle-adjustment factor is exponential)
     bool plain = false;
-    if (int rc = starts_refusal(L, who_name, &plain, "population", L->population_tiny != 0, L->population_point_major != 0)) return rc;
+    if (int rc = starts_refusal(L, who_name, &plain, "population", L->population_tiny != 0, L->population_point_major != 0, cooperative)) return rc;
     // point-major components (option population_point_major: the refusal above let them pass) run as one workgroup a component, the
     // bits of launch_ptm -- a group, a wide group or local camera numbering changes the order of every sum
     const int nptm = (L->population_point_major && !plain) ? L->rest_ptm : 0;
@@ -2196,6 +2210,23 @@ int solve_population_range(rdis_hip_plan* L, rdis_hip_population* pop, int64_t f
             return fail(c, RDIS_HIP_EINVAL, who + ": point-major components are solved on a population as one workgroup a component, and this plan's "
                                             "ordinary solve would run them as " + std::string(wide ? "wide " : "") + "groups of " + std::to_string(K) +
                                             " workgroups (other sums, other bits): set the plan option ptm_group = 1");
+    }
+    // What the cooperative launches need of a member: gfac, the groups' directions and an exchange state a group; every workgroup of
+    // such a launch is resident, which bounds R a second time -- by the NEW kernel's occupancy (solver_coop_population.hpp).  The
+    // plan's launches were packed under the ordinary kernel's cap (pack_coop_launches): one that does not fit the new kernel's even
+    // with a single member is refused here, before any row is written, not left to the runtime to reject
+    const bool coop = cooperative && !L->coop.empty();
+    const SolverSet& CS = solver_set(L->coop_reference_rounding());
+    int64_t coop_groups = 0, coop_wg = 0, xi_doubles = 0;
+    int coop_cap_wg = 0;
+    if (coop) {
+        for (const CoopLaunch& cl : L->coop_launches) { coop_groups = std::max<int64_t>(coop_groups, cl.count); coop_wg = std::max<int64_t>(coop_wg, cl.total_wg); }
+        for (const CoopItem& it : L->coop) xi_doubles += L->h_free_ptr[(size_t)it.comp + 1] - L->h_free_ptr[(size_t)it.comp];
+        const int ti = L->coop_threads == 128 ? 0 : L->coop_threads == 256 ? 1 : 2;
+        int& cap = L->coop_reference_rounding() ? c->cap_coop_pop_rr[ti] : c->cap_coop_pop[ti];   // (asked once per context and layout: coop_cap)
+        if (cap < 0) cap = CS.coop_population_max_workgroups(L->coop_threads, c->num_cus);
+        coop_cap_wg = cap;
+        if (coop_wg > coop_cap_wg) return fail(c, RDIS_HIP_EINVAL, population_coop_residency_refusal(who_name, coop_wg, coop_cap_wg));
     }
     pop->x_written();
     if (L->ncomp == 0) { note_empty_solve(L, true, S_n); return 0; }
@@ -2215,8 +2246,11 @@ int solve_population_range(rdis_hip_plan* L, rdis_hip_population* pop, int64_t f
     const ReplicaLayout work = population_work_layout(nlisted > 0, L->nfree, L->ngfac, tiny_records, p->N), dir = solve_dir_layout(plain, p->N);
     // ... and the four per-solve arrays of the point-major solver
     const ReplicaLayout ptm = population_ptm_layout(nptm > 0 ? L->pm_blocks : 0, L->pm_cptr_len);
-    const int64_t R = members_per_launch(S_n, L->starts_workspace_bytes, work.member_bytes() + dir.member_bytes() + ptm.member_bytes());
+    const ReplicaLayout cw = population_coop_layout(L->ngfac, xi_doubles, coop_groups, (int64_t)sizeof(CoopState));
+    const int64_t R = coop_members_per_launch(S_n, L->starts_workspace_bytes, work.member_bytes() + dir.member_bytes() + ptm.member_bytes() + cw.member_bytes(),
+                                              coop_cap_wg, coop_wg);
     int rc = 0;
+    if (coop && L->ms_coop.bytes < (size_t)cw.total_bytes(R) && (rc = plan_alloc(L, L->ms_coop, (size_t)cw.total_bytes(R)))) return rc;
     if (nptm > 0) {
         // the round tables of that workgroup size, one workgroup a component, before the first launch (launch_ptm's)
         rc = ptm_build_rounds(L, ptm_threads, 1);
@@ -2252,7 +2286,20 @@ int solve_population_range(rdis_hip_plan* L, rdis_hip_population* pop, int64_t f
         RP.bex = ptm.at<double>(base, PTM_REPLICA_BEX, R); RP.cbox = ptm.at<float>(base, PTM_REPLICA_CBOX, R);
     }
     const size_t ptm_dyn = nptm > 0 ? ptm_bytes_for(L->ptm_ncb_cap, ptm_threads, L->rounds_slots) : 0;
+    // the cooperative launches' view of the per-solve arrays: gfac is their own replica (a member's stride: the padded part)
+    StartsView SC = S;
+    // (RC.timing, the trailing null, must stay a value the kernel learns at run time: written into the kernel as a constant it
+    // stops this compiler's gfx950 backend on the reference-rounding instantiation -- solver_coop_population.hpp; both SolverSet
+    // tables launch with this RC)
+    CoopReplicas RC{nullptr, L->xi_glob.as<double>(), 0, nullptr, (int)coop_groups, nullptr};
+    if (coop) {
+        void* const base = L->ms_coop.p;
+        SC.gfac = cw.at<double>(base, COOP_REPLICA_GFAC, R); SC.ngfac = cw.doubles(COOP_REPLICA_GFAC);
+        RC.xi = cw.at<double>(base, COOP_REPLICA_XI, R); RC.xi_doubles = cw.doubles(COOP_REPLICA_XI);
+        RC.st = cw.at<CoopState>(base, COOP_REPLICA_STATE, R);
+    }
     L->last_launches = 0;
+    L->ms_coop_wg = (int)coop_wg; L->ms_coop_cap = coop ? coop_cap_wg : 0;
     L->ms_tiny_blocks = 0;
     L->ms_ptm_threads = nptm > 0 ? ptm_threads : 0;
     L->timed = false;
@@ -2260,6 +2307,15 @@ int solve_population_range(rdis_hip_plan* L, rdis_hip_population* pop, int64_t f
     for (int64_t first = 0; first < S_n; first += R) {   // (launches on one stream: the next takes the replicas when this one is done)
         S.first = first;
         const int ns = (int)std::min(R, S_n - first);
+        if (coop) {
+            SC.first = first;
+            for (const CoopLaunch& cl : L->coop_launches) {   // (the states of this launch's groups are armed in front of it, for its members)
+                const int e = CS.launch_coop_population(c->stream, p->kind, P, V, SC, RC, Xb, cl.groups.as<CoopGroup>(), cl.wg_group.as<int>(), cl.count,
+                                                        cl.total_wg, ns, L->coop_threads, maxiters, ftol);
+                if (e != 0) return fail(c, RDIS_HIP_EDEVICE, who + ": cooperative solver launch: " + hipGetErrorString((hipError_t)e));
+                ++L->last_launches;
+            }
+        }
         if (ntiny > 0) {
             // the records of THIS launch's members: the replicas held another launch's until now (solver_quad_population.hpp)
             if (tiny_records) HIPCHK(c, population_rotations_launch(c->stream, Xb, p->N, first, ns, p->cam_blocks.as<int>(), (int)p->ncam_blocks, XR));
@@ -2302,6 +2358,16 @@ extern "C" int rdis_hip_plan_solve_population_range(rdis_hip_plan* L, rdis_hip_p
     if (count < 1 || first < 0 || first > pop->nmembers || count > pop->nmembers - first)
         return fail(c, RDIS_HIP_EINVAL, "plan_solve_population_range: members out of range (count >= 1, first + count <= nmembers)");
     return solve_population_range(L, pop, first, count, maxiters, ftol, "plan_solve_population_range");
+}
+
+extern "C" int rdis_hip_plan_solve_population_cooperative(rdis_hip_plan* L, rdis_hip_population* pop, int64_t first, int64_t count, int32_t maxiters,
+                                                          double ftol) {
+    if (!L || !pop) return RDIS_HIP_EINVAL;
+    rdis_hip_ctx* c = L->prob->ctx;
+    USE_DEVICE(c);
+    if (count < 1 || first < 0 || first > pop->nmembers || count > pop->nmembers - first)
+        return fail(c, RDIS_HIP_EINVAL, "plan_solve_population_cooperative: members out of range (count >= 1, first + count <= nmembers)");
+    return solve_population_range(L, pop, first, count, maxiters, ftol, "plan_solve_population_cooperative", true);
 }
 
 extern "C" int rdis_hip_plan_fetch_population(rdis_hip_plan* L, double* x_out, double* fret, double* delta, int32_t* iters, int32_t* status,

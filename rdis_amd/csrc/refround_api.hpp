@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include "device_views.hpp"
+#include "starts_api.hpp"   // StartsView, CoopReplicas
 
 namespace rdis_views {
 
@@ -26,6 +27,11 @@ struct SolverSet {
     // solver_lds.hpp: launch_lds
     hipError_t (*launch_lds)(int rot, int stale, int threads, int grid, size_t dyn, hipStream_t stream, const ProblemView& P, const PlanView& V,
                              int maxiters, double ftol, int ns_cap, int ncb_cap, int chunk_cap);
+    // solver_coop_population.hpp: launch_coop_population and the resident workgroups a launch of it may have, over all its members
+    int (*launch_coop_population)(hipStream_t stream, int kind, const ProblemView& P, const PlanView& V, const StartsView& S, const CoopReplicas& RC,
+                                  double* X, const CoopGroup* groups, const int* wg_group, int ngroups, int total_wg, int members_of_launch,
+                                  int threads, int maxiters, double ftol);
+    int (*coop_population_max_workgroups)(int threads, int num_cus);
 };
 
 }  // namespace rdis_views

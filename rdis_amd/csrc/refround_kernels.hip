@@ -6,6 +6,7 @@
 #define rdis_hip rdis_hip_refround
 #include "solver_lds.hpp"
 #include "solver_pipe.hpp"
+#include "solver_coop_population.hpp"
 #undef rdis_hip
 #include "refround_api.hpp"
 
@@ -14,7 +15,8 @@ namespace rr = ::rdis_hip_refround;
 
 // (the views and groups are namespace rdis_views' own in either instantiation: the launches go into the set as they are)
 const rdis_views::SolverSet& refround_solvers() {
-    static const rdis_views::SolverSet set = {rr::launch_pipe, rr::launch_coop, rr::pipe_max_workgroups, rr::coop_max_workgroups, rr::launch_lds};
+    static const rdis_views::SolverSet set = {rr::launch_pipe, rr::launch_coop, rr::pipe_max_workgroups, rr::coop_max_workgroups, rr::launch_lds,
+                                              rr::launch_coop_population, rr::coop_population_max_workgroups};
     return set;
 }
 

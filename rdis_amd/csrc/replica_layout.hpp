@@ -6,6 +6,8 @@
 // The Levenberg-Marquardt plan's solves (rdis_hip_lm_plan_solve, rdis_hip_lm_plan_solve_population) describe their two buffers the
 // same way (lm_plan_layout) and split their members by the same rule; its multi-start solves (rdis_hip_lm_plan_solve_starts,
 // rdis_hip_lm_plan_solve_starts_population) add a winners' row, best[ncomp] and a scratch row of x a start (lm_starts_layout).
+// rdis_hip_plan_solve_population_cooperative adds a buffer for its cooperative launches (population_coop_layout) and bounds the
+// members of a launch by the resident workgroups as well (coop_members_per_launch).
 // Pure host functions: no HIP call, no plan, no population (tests/cpp/replica_layout_test.cpp runs them without a device).
 #pragma once
 #include <algorithm>
@@ -61,6 +63,18 @@ enum { PTM_REPLICA_REC = 0, PTM_REPLICA_GH = 1, PTM_REPLICA_BEX = 2, PTM_REPLICA
 inline ReplicaLayout population_ptm_layout(int64_t pm_blocks, int64_t pm_cptr_len) {
     const int64_t plane = 8 * REPLICA_PT_REC * pm_blocks;
     return pm_blocks > 0 ? ReplicaLayout(4, plane, plane, plane, 4 * 8 * pm_cptr_len) : ReplicaLayout(4, 0);
+}
+
+// ms_coop, a buffer of its own, of rdis_hip_plan_solve_population_cooperative (solver_coop_population.hpp): the cooperative
+// solver's gfac[ngfac], the groups' published directions (xi_doubles: the free variables of the plan's cooperative components,
+// each group at its offset in the plan's xi_glob) and one exchange state (state_bytes: sizeof CoopState) for each of `groups`
+// groups -- the most a launch of the plan has.  The two parts of doubles are padded to whole 32 bytes a member (a member's
+// stride is doubles(part), not the count), so that every state lies on the 32 bytes its granule pairs ask for whatever R is
+// (state_bytes is a multiple of 32).  A plan without cooperative components has no such part.
+enum { COOP_REPLICA_GFAC = 0, COOP_REPLICA_XI = 1, COOP_REPLICA_STATE = 2 };
+inline ReplicaLayout population_coop_layout(int64_t ngfac, int64_t xi_doubles, int64_t groups, int64_t state_bytes) {
+    const auto pad = [](int64_t doubles) { return (8 * std::max<int64_t>(doubles, 0) + 31) / 32 * 32; };
+    return groups > 0 ? ReplicaLayout(3, pad(ngfac), pad(xi_doubles), groups * state_bytes) : ReplicaLayout(3, 0);
 }
 
 // ---- rdis_hip_population_eval ----
@@ -130,6 +144,17 @@ inline LmStartsLayout lm_starts_layout(int64_t ncomp, int64_t res_doubles, int64
 inline int64_t members_per_launch(int64_t count, int64_t budget_bytes, int64_t member_bytes) {
     const int64_t fit = member_bytes > 0 ? std::max<int64_t>(1, budget_bytes / member_bytes) : count;
     return std::min(std::min(fit, count), (int64_t)65535);
+}
+
+// ... of a call whose launches include cooperative ones (rdis_hip_plan_solve_population_cooperative): every workgroup of a
+// cooperative launch must be resident, so a launch of R members with `launch_workgroups` workgroups a member (the largest
+// total_wg among the plan's cooperative launches) has R launch_workgroups <= cap_workgroups, the resident workgroups of the
+// population kernel -- at least one member a launch (a launch too large for the device is rejected by the runtime, not hung).
+// launch_workgroups <= 0: the plan has no cooperative launch, and the cap bounds nothing.
+inline int64_t coop_members_per_launch(int64_t count, int64_t budget_bytes, int64_t member_bytes, int64_t cap_workgroups, int64_t launch_workgroups) {
+    const int64_t R = members_per_launch(count, budget_bytes, member_bytes);
+    if (launch_workgroups <= 0) return R;
+    return std::max<int64_t>(1, std::min(R, cap_workgroups / launch_workgroups));
 }
 
 }  // namespace rdis_hip

@@ -26,6 +26,19 @@ struct StartsView {
     long long first;        // the launch's first start
 };
 
+// The replicas of the cooperative solver's per-solve arrays on a population (solver_coop_population.hpp; the replica of gfac is
+// StartsView::gfac): replica r of the launch publishes the direction of a group whose CoopArgs::xi_glob is xi_plan + off at
+// xi + r xi_doubles + off, and group g of the launch exchanges through st[r groups + g].  Both instantiations of the kernel
+// (refround_api.hpp) take this very struct.
+struct CoopReplicas {
+    double* xi;              // [replicas][xi_doubles]
+    const double* xi_plan;   // the plan's own xi_glob: the base the groups' offsets are taken from
+    long long xi_doubles;
+    CoopState* st;           // [replicas][groups]
+    int groups;              // states per replica: the most groups a launch of the plan has
+    long long* timing;       // CoopArgs::timing of every group: null (no member's group writes the problem's debug counters)
+};
+
 }  // namespace rdis_views
 
 namespace rdis_hip {

@@ -81,6 +81,7 @@ void HipRDISLevelOptimizer::setParameters(const Options& o) {
     if (o.count("batch")) batch_ = o.as<int>("batch") != 0;
     if (o.count("sepPiecePct")) seppct_ = o.as<double>("sepPiecePct");
     if (o.count("lmStepDetail")) lm_step_detail_ = o.as<int>("lmStepDetail") != 0;
+    if (o.count("populationCooperative")) population_cooperative_ = o.as<int>("populationCooperative") != 0;
     if (o.count("nRRperLvl")) nrr_per_lvl_ = (unsigned)o.as<int>("nRRperLvl");          // RDISOptimizer.cpp:97, 1781-1782
     if (o.count("nRRatTop")) { nrr_at_top_ = (unsigned)o.as<int>("nRRatTop"); nrr_at_top_set_ = true; }   // :99, 1784-1785
     if (!nrr_at_top_set_) nrr_at_top_ = nrr_per_lvl_;
@@ -296,6 +297,9 @@ void HipRDISLevelOptimizer::buildPlans(bool forPopulation) {
                 check(f_.deviceContext(), rdis_hip_plan_create(p, (int64_t)ncomp, lp->free_ptr.data(), lp->free_vid.data(),
                                                                lp->fac_ptr.data(), lp->fac_id.data(), &lp->plan), "rdis_hip_plan_create");
             if (forPopulation && lp->plan) check(f_.deviceContext(), rdis_hip_plan_set_option(lp->plan, "population_tiny", 1), "rdis_hip_plan_set_option");
+            // (populationCooperative: the population kernel runs the plain cooperative layout -- the pipelined layout's bits)
+            if (forPopulation && lp->plan && population_cooperative_)
+                check(f_.deviceContext(), rdis_hip_plan_set_option(lp->plan, "coop_pipeline", 0), "rdis_hip_plan_set_option");
         }
 }
 
@@ -512,7 +516,10 @@ void HipRDISLevelOptimizer::stepPopulation(LevelPlan& lp, rdis_hip_population* p
             s.iters = (long long)m[2]; s.fevals = (long long)m[3]; s.invalid = (long long)m[12]; s.nonfinite = (long long)m[13];
         }
     } else {
-        check(ctx, rdis_hip_plan_solve_population_range(lp.plan, pop, 0, active, (int32_t)ssmaxit_, ssftol_), "rdis_hip_plan_solve_population_range");
+        if (population_cooperative_)
+            check(ctx, rdis_hip_plan_solve_population_cooperative(lp.plan, pop, 0, active, (int32_t)ssmaxit_, ssftol_), "rdis_hip_plan_solve_population_cooperative");
+        else
+            check(ctx, rdis_hip_plan_solve_population_range(lp.plan, pop, 0, active, (int32_t)ssmaxit_, ssftol_), "rdis_hip_plan_solve_population_range");
         std::vector<double> delta(A * ncomp);
         std::vector<int32_t> iters(A * ncomp), status(A * ncomp);
         check(ctx, rdis_hip_plan_fetch_population(lp.plan, nullptr, nullptr, delta.data(), iters.data(), status.data(), nullptr, nullptr),
@@ -581,7 +588,8 @@ Numeric HipRDISLevelOptimizer::optimizePopulation(rdis_hip_population* pop, bool
         int rc = 0;
         std::string msg;
         for (LevelPlan* lp : plans_) {
-            rc = rdis_hip_plan_solve_population_range(lp->plan, scratch, 0, 1, 1, ssftol_);
+            rc = population_cooperative_ ? rdis_hip_plan_solve_population_cooperative(lp->plan, scratch, 0, 1, 1, ssftol_)
+                                         : rdis_hip_plan_solve_population_range(lp->plan, scratch, 0, 1, 1, ssftol_);
             if (rc != 0) { msg = rdis_hip_last_error(ctx); break; }
         }
         if (rc == 0) rc = rdis_hip_synchronize(ctx);
@@ -591,7 +599,7 @@ Numeric HipRDISLevelOptimizer::optimizePopulation(rdis_hip_population* pop, bool
     const size_t nS = (size_t)S;
     member_results_.assign(nS, MemberResult());
     member_traces_.assign(nS, std::vector<Step>());
-    best_member_ = -1; permute_s_ = 0; permutes_ = 0;
+    best_member_ = -1; permute_s_ = 0; permutes_ = 0; members_per_launch_ = 0;
     trace_.clear(); sweeps_ = 0;
     std::vector<double> objective(nS);
     check(ctx, rdis_hip_population_eval(pop, (int64_t)every.size(), every.data(), objective.data()), "rdis_hip_population_eval");
@@ -615,6 +623,17 @@ Numeric HipRDISLevelOptimizer::optimizePopulation(rdis_hip_population* pop, bool
         const int64_t A = rows.active();
         for (int64_t r = 0; r < A; ++r) before[(size_t)rows.memberOfRow(r)] = objective[(size_t)rows.memberOfRow(r)];
         for (LevelPlan* lp : plans_) stepPopulation(*lp, pop, sweep, rows.rowToMember(), A, objective);
+        if (sweep == 0) {   // (membersPerLaunch: the fewest over the plans with cooperative launches; without any, over all CGD plans)
+            long long all = 0, cooperative = 0;
+            for (LevelPlan* lp : plans_) {
+                int64_t per = 0, wg = 0;
+                if (!lp->plan || rdis_hip_plan_get_info(lp->plan, "starts_per_launch", &per) != 0 || per <= 0) continue;
+                all = all == 0 ? per : std::min<long long>(all, per);
+                if (rdis_hip_plan_get_info(lp->plan, "population_cooperative_workgroups", &wg) == 0 && wg > 0)
+                    cooperative = cooperative == 0 ? per : std::min<long long>(cooperative, per);
+            }
+            members_per_launch_ = cooperative > 0 ? cooperative : all;
+        }
         std::vector<char> stopped((size_t)A, 0);
         int64_t nstopped = 0;
         for (int64_t r = 0; r < A; ++r) {

@@ -81,7 +81,8 @@ public:
     // optimizer by the caller), batch (1; 0 = one ssopt.optimize call per component, in the
     // reference's child order: the same results bit for bit, for tests and comparison), sepPiecePct (0: a
     // separator leaves pieces that are leaves; > 0: pieces of up to that fraction of the node, which are
-    // split again -- deeper trees, like the reference's two-way partitions), lmStepDetail (1; see the second constructor)
+    // split again -- deeper trees, like the reference's two-way partitions), lmStepDetail (1; see the second constructor),
+    // populationCooperative (0; 1: optimizePopulation takes CGD trees with components on the cooperative solver, see there)
     void setParameters(const Options& options);
 
     // Every variable must be assigned (the initial state, optBA.cpp:189-205).  Returns the final
@@ -114,6 +115,12 @@ public:
     // cameras (the message names the node and its camera count: beyond every plan, and refused rather than routed); a CGD plan the
     // population entry refuses -- cooperative, pipelined or grid components, point-major components in groups -- with that
     // entry's own message (every plan is proved on a scratch population of one member first, so no row has been written).
+    // With the level option populationCooperative = 1 the CGD plans of the run also get the plan option coop_pipeline = 0, and
+    // their population steps and that proof go through rdis_hip_plan_solve_population_cooperative: cooperative components --
+    // full ladybug's 46-camera separator, its camera level as groups side by side -- are solved a group per member, in the
+    // plain cooperative layout, whose bits are the pipelined layout's (what optimize() runs): the contract above holds as it
+    // stands.  Still refused then: components on the grid solver, point-major components in groups.  Default 0: the run and
+    // its refusals as they were.
     struct MemberResult {
         double initial, final, sumOfDeltas;   // f at the start; f evaluated at the end; the running objective (initial + the deltas)
         int sweeps;
@@ -126,6 +133,10 @@ public:
     // of the last optimizePopulation: seconds in rdis_hip_population_permute calls (waits included), and how many there were
     double permuteSeconds() const { return permute_s_; }
     int permutes() const { return permutes_; }
+    // ... and, of the first sweep's steps, the fewest members a launch held (plan_get_info "starts_per_launch") among the CGD
+    // plans that had cooperative launches (populationCooperative: the resident workgroups bound it as well as the budget); where
+    // no plan had one, among all CGD plans (the budget alone); 0 without CGD plans.  Later sweeps run fewer members: not read
+    long long membersPerLaunch() const { return members_per_launch_; }
 
     // The same tree under the REFERENCE'S schedule (round 4): what doOptimization / getValueFromDomain do at every node
     // (src/RDISOptimizer.cpp:253-334, 971-1147, 1507-1577) with branch and bound and the component cache off --
@@ -209,6 +220,7 @@ private:
     SubspaceOptimizer& ss_;
     double runLmPlan(LevelPlan& lp, int sweep, double objective, bool printInfo);
     bool lm_step_detail_ = true;
+    bool population_cooperative_ = false;   // level option populationCooperative
     double blkpct_, steptol_, seppct_;
     int maxSweeps_;
     bool batch_;
@@ -227,6 +239,7 @@ private:
     long long best_member_ = -1;
     double permute_s_ = 0;
     int permutes_ = 0;
+    long long members_per_launch_ = 0;
     // reference schedule
     struct NodeState;
     void runSet(const std::vector<int>& set, const std::vector<char>& randomInit, std::vector<NodeState>& st, bool printInfo);

@@ -126,7 +126,7 @@ extern "C" int rdis_optba_run_samples(const char* bal_file, int64_t ncams, int64
         f.assignAll(f.getInitialState());
         Options ss, lv;
         // (schedule 0 only: the options of the reference's per-node schedule have no meaning here)
-        static const char* const level_opts[] = {"AVblkpct", "steptol", "maxSweeps", "sepPiecePct", "batch"};
+        static const char* const level_opts[] = {"AVblkpct", "steptol", "maxSweeps", "sepPiecePct", "batch", "populationCooperative"};
         bool use_cgd = true;
         for (int i = 0; i < nopts; ++i) {
             const std::string n(opt_names[i] ? opt_names[i] : "");

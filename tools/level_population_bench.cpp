@@ -20,10 +20,12 @@ double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock:
 
 // loop_s, pop_s, permute_s: [rounds] seconds; info = {members whose final value differs between the two (bits), best value of the
 // loop, best value of the population run, sum of the members' sweeps, largest sweep count, permutes of a run, launches a sweep,
-// members with a final value that is not finite}.  Returns 0; 1: the population run was refused (msg says why); < 0: an error.
-extern "C" int bench_level_population(const char* path, long long ncams, long long npts, int use_cgd, int maxit, int max_sweeps, int model, long long S,
-                                      unsigned long long seed, int rounds, double* loop_s, double* pop_s, double* permute_s, double* info, char* msg,
-                                      long long msg_cap) {
+// members with a final value that is not finite, the fewest members a launch of a CGD plan held}.  cooperative: the level option
+// populationCooperative of the population run (the loop is optimize() as it is).  Returns 0; 1: the population run was refused
+// (msg says why); < 0: an error.
+extern "C" int bench_level_population_option(const char* path, long long ncams, long long npts, int use_cgd, int maxit, int max_sweeps, int model,
+                                             long long S, unsigned long long seed, int rounds, int cooperative, double* loop_s, double* pop_s,
+                                             double* permute_s, double* info, char* msg, long long msg_cap) {
     try {
         BundleAdjustmentFunction f;
         if (!f.load(path, ncams, npts)) return -1;
@@ -47,7 +49,7 @@ extern "C" int bench_level_population(const char* path, long long ncams, long lo
             lm.reset(new HipLMSubspaceOptimizer(f)); lm->setParameters(o);
             driver.reset(new HipRDISLevelOptimizer(f, *lm));
         }
-        Options ro; ro.set("maxSweeps", max_sweeps); ro.set("lmStepDetail", 0);
+        Options ro; ro.set("maxSweeps", max_sweeps); ro.set("lmStepDetail", 0); ro.set("populationCooperative", cooperative);
         driver->setParameters(ro);
         rdis_hip_problem* p = f.deviceProblem();
         rdis_hip_ctx* ctx = f.deviceContext();
@@ -96,10 +98,21 @@ extern "C" int bench_level_population(const char* path, long long ncams, long lo
         }
         best_pop = res[(size_t)driver->bestMember()].final;
         info[0] = (double)differ; info[1] = best_loop; info[2] = best_pop; info[3] = (double)sweeps; info[4] = (double)most;
-        info[5] = driver->permutes(); info[6] = (double)driver->numPlans(); info[7] = (double)bad;
+        info[5] = driver->permutes(); info[6] = (double)driver->numPlans(); info[7] = (double)bad; info[8] = (double)driver->membersPerLaunch();
         return 0;
     } catch (const std::exception& e) {
         std::cerr << "bench_level_population: " << e.what() << std::endl;
         return -2;
     }
+}
+
+// (info: eight doubles, as before the option existed)
+extern "C" int bench_level_population(const char* path, long long ncams, long long npts, int use_cgd, int maxit, int max_sweeps, int model, long long S,
+                                      unsigned long long seed, int rounds, double* loop_s, double* pop_s, double* permute_s, double* info, char* msg,
+                                      long long msg_cap) {
+    double all[9] = {0};
+    const int rc = bench_level_population_option(path, ncams, npts, use_cgd, maxit, max_sweeps, model, S, seed, rounds, 0, loop_s, pop_s, permute_s, all, msg,
+                                                 msg_cap);
+    for (int i = 0; i < 8; ++i) info[i] = all[i];
+    return rc;
 }
